@@ -71,6 +71,10 @@ def parse_args(argv=None):
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher / timing protocol only: gloo backend, no GPU, no model (CPU test of the N-rank path)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="self-launched ranks are stopped after this many seconds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32; at most 64 MB in all, a fixed seeded row sample beyond that): the inputs are seeded, so two "
+                         "builds run with the same arguments can be compared output for output")
     ap.add_argument("--probe-collective", action="store_true", help=argparse.SUPPRESS)     # internal: capture probe child
     return ap.parse_args(argv)
 
@@ -160,6 +164,33 @@ def timed_steps(step, steps, warmup, barrier, after_warmup=None):
         step()
     barrier()
     return time.perf_counter() - t0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: {name: tensor or array} -> dirname/<name>.npy, float32 (float64 stays float64).  Above DUMP_LIMIT_BYTES
+    in all, every array keeps the same fraction of its rows, drawn with a fixed seed (the same rows from run to run)."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):                # a tensor (bf16 has no numpy dtype: cast on the torch side)
+            import torch
+            a = a.detach().to(torch.float64 if a.dtype == torch.float64 else torch.float32).cpu().numpy()
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        for name, a in out.items():
+            if a.ndim and a.shape[0] > 1:
+                k = max(1, int(a.shape[0] * frac))
+                out[name] = a[np.sort(np.random.RandomState(seed).choice(a.shape[0], k, replace=False))]
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES, "dump exceeds %d bytes" % DUMP_LIMIT_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def max_over_ranks(dt, dist, device):
@@ -353,7 +384,10 @@ def dry_run(args, rank, world):
         total = world * b_local if scaling == "weak" else GLOBAL_BATCH
         res[scaling] = {"value": total / (dt_max / args.steps), "ms_per_step": dt_max / args.steps * 1e3, "dt_ranks": dts,
                         "seeds": seeds, "gathered_rows": int(state["out"].shape[0]),
-                        "gathered_checksum": float(state["out"].double().sum())}
+                        "gathered_checksum": float(state["out"].double().sum()), "_out": state["out"]}
+    outs = {s: r.pop("_out") for s, r in res.items()}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": outs[args.scaling]})
     if d is not None:
         d.barrier()
         d.destroy_process_group()
@@ -421,6 +455,8 @@ def stress_run(args, rank, local_rank, world):
         blocks = [(c, b0, b1) + tuple(v.shape) for (c, b0, b1), v in state["out"].items()]
     dt = timed_steps(step, args.steps, args.warmup, barrier)
     dt_max, dts = max_over_ranks(dt, dist, device)
+    if args.dump_outputs and not dry:           # every rank its own read-out blocks (disjoint names)
+        dump_outputs(args.dump_outputs, {"readout_c%d_b%d_%d" % k: v for k, v in state["out"].items()})
     every = [blocks]
     if dist is not None:
         every = [None] * world
@@ -1074,6 +1110,8 @@ def run_rank(args):
     else:
         weak = measure("weak")
         strong = measure("strong") if (world > 1 or os.environ.get("MGNNS_BENCH_FORCE_STRONG") == "1") else None
+    if args.dump_outputs and rank == 0:         # the headline's logits of its last timed step (gathered over the ranks)
+        dump_outputs(args.dump_outputs, {"logits": (weak if (args.scaling == "weak" or strong is None) else strong)["logits"]})
 
     # ---- roofline leg: every C-ABI launch timed with HIP events on the stream it runs on, over eager single-stream
     #      forwards right after the timed region (events cannot sit inside a graph); rank 0's shard ----

@@ -7,7 +7,9 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -170,3 +172,38 @@ def test_emit_prints_the_compact_line_last(tmp_path, capsys, monkeypatch):
     huge["config"] = dict(huge["config"], **{"workload": "x" * 100000})
     bench.emit(huge)                                            # over-long strings are cut, not fatal
     assert len(capsys.readouterr().out.splitlines()[-1]) < 8000
+
+
+# ---- --dump-outputs: the last timed step's outputs, the same from run to run ----
+def test_dump_outputs_are_the_gathered_last_step_and_repeat(tmp_path):
+    """Two ranks, weak scaling: DIR/logits.npy is the all-gathered output of the last timed step (every rank's seeded shard,
+    in rank order), float32, and a second run with the same arguments writes the same bytes."""
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-launch", "--steps", "3", "--warmup", "1", "--batch", "16",
+                            "--dump-outputs", str(tmp_path / run)],
+                           env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert sorted(os.listdir(tmp_path / run)) == ["logits.npy"]
+        dumps.append(np.load(tmp_path / run / "logits.npy"))
+        line = json.loads(r.stdout.strip())
+        assert dumps[-1].sum(dtype=np.float64) == pytest.approx(line["weak_scaling"]["gathered_checksum"], rel=1e-6)
+    want = np.concatenate([np.random.RandomState(1237 + 1000 * r).standard_normal((16, 3)).astype(np.float32) for r in range(2)])
+    assert dumps[0].dtype == np.float32 and np.array_equal(dumps[0], want)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_caps_the_size_with_a_fixed_row_sample(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    a = np.arange(1000 * 4, dtype=np.float64).reshape(1000, 4)           # 32 KB: float64 is kept as float64
+    b = torch.arange(500 * 2, dtype=torch.bfloat16).reshape(500, 2)      # other dtypes arrive as float32
+    for run in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / run), {"a": a, "b": b})
+    ga, gb = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert ga.dtype == np.float64 and gb.dtype == np.float32
+    assert ga.nbytes + gb.nbytes <= 4096 and ga.shape[1] == 4 and gb.shape[1] == 2
+    rows = (ga[:, 0] / 4).astype(int)                                    # sampled rows, in order, each one whole
+    assert np.all(np.diff(rows) > 0) and np.array_equal(ga, a[rows])
+    assert np.array_equal(ga, np.load(tmp_path / "y" / "a.npy")) and np.array_equal(gb, np.load(tmp_path / "y" / "b.npy"))
