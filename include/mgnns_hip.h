@@ -52,6 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
+#define MGNNS_ABI_VERSION 19
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -526,6 +527,47 @@ int mgnns_classifier_part_fwd(const float* f, int part, int nparts, int B, int D
  */
 int mgnns_layernorm_fwd(const float* x, int rows, int D, const float* gamma, const float* beta,
                         float eps, float* y, mgnns_stream_t stream);
+
+/* ---- training mode of one MyMultiHeadAttention layer (moudles.py:198-230, submodules.py:15-156), fp32 ----------------------
+ * Dropout keeps element i of site s iff hash(seed, s, i) >= rate (a counter-based hash; the same seed draws the same mask) and
+ * scales the kept values by 1 / (1 - rate).  Sites: 0 = attention probabilities (index (h*B + b)*L + l), 1 = after fc,
+ * 2 = after w_2 (index r*D + d).  Every reduction over rows runs in a fixed order: one seed gives bit-identical results.
+ *
+ * mgnns_mha_train_fwd: the folded attention core with attention dropout.  qh [B, H*dk] = w_qs(q); bank fp32 [B, L, D]; mask
+ * [B, L] (0 = masked) or NULL.  Outputs (all [H][B][...]): U [H,B,D] = W_k,h^T qh_h; P [H,B,L] softmax before dropout;
+ * attn [H*B, L] after dropout (the reference's returned attn); keep [H,B,L] bytes or NULL; Z [H,B,D] = X^T p'; SP [H,B] =
+ * sum_l p'; o [B, H*dk] = W_v,h z_h + b_v,h SP.  D <= 320, D % 4 == 0, H <= 8, dk % 4 == 0, L <= 208, 0 <= rate <= 1.
+ * mgnns_mha_train_bwd: its backward from dO [B, H*dk] and the forward's saved tensors (keep required): dqh [B, H*dk],
+ * dWk / dWv [H*dk, D], dbv [H*dk] (written, not accumulated), dbank [B, L, D] or NULL (masked rows: 0).  b_k has no gradient
+ * (it drops out of the softmax).  workspace: mgnns_mha_train_bwd_workspace_bytes(B, D, H, dk) bytes, 16-byte aligned.
+ */
+int mgnns_mha_train_fwd(const float* qh, const float* bank, const float* mask, int B, int L, int D, int H, int dk,
+                        const float* Wk, const float* Wv, const float* bv, uint64_t seed, float rate, float* U, float* P,
+                        float* attn, uint8_t* keep, float* Z, float* SP, float* o, mgnns_stream_t stream);
+size_t mgnns_mha_train_bwd_workspace_bytes(int B, int D, int H, int dk);
+int mgnns_mha_train_bwd(const float* dO, const float* qh, const float* bank, const float* mask, int B, int L, int D, int H,
+                        int dk, const float* Wk, const float* Wv, const float* bv, float rate, const float* U, const float* P,
+                        const float* attn, const uint8_t* keep, const float* Z, const float* SP, float* dqh, float* dWk,
+                        float* dWv, float* dbv, float* dbank, void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
+/* Weight gradient of a linear layer: dW[N,K] = dY[M,N]^T X[M,K], db[N] = column sums of dY (db NULL: none).  Row slabs + an
+ * ordered combine, no atomics.  workspace: mgnns_wgrad_workspace_bytes(M, N, K) bytes. */
+size_t mgnns_wgrad_workspace_bytes(int M, int N, int K);
+int mgnns_wgrad_fwd(const float* dY, int M, int N, const float* X, int K, float* dW, float* db, void* workspace,
+                    size_t workspace_bytes, mgnns_stream_t stream);
+/* v = dropout(x) + res;  y = gamma (v - mean) / (std_unbiased + eps) + beta  (rows x D, D <= 1024).  Saves xhat [rows, D],
+ * sig [rows] (the unbiased std) and keep [rows, D] (bytes) for the backward. */
+int mgnns_drop_res_ln_fwd(const float* x, const float* res, int rows, int D, const float* gamma, const float* beta, float eps,
+                          uint64_t seed, int site, float rate, float* y, float* xhat, float* sig, uint8_t* keep,
+                          mgnns_stream_t stream);
+/* Its backward for dy (+ dy2 when not NULL): dres = dL/dv (the residual's gradient), dx = dres keep / (1 - rate),
+ * dgamma / dbeta [D] (written). */
+int mgnns_drop_res_ln_bwd(const float* dy, const float* dy2, const float* xhat, const float* sig, const uint8_t* keep, int rows,
+                          int D, const float* gamma, float eps, float rate, float* dres, float* dx, float* dgamma, float* dbeta,
+                          mgnns_stream_t stream);
+/* y = a + b (MGNNS_ELT_ADD) or y = a * (b > 0) (MGNNS_ELT_RELU_BWD: ReLU backward, b = the ReLU's output), n elements. */
+#define MGNNS_ELT_ADD      0
+#define MGNNS_ELT_RELU_BWD 1
+int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float* y, mgnns_stream_t stream);
 
 /* ---- dense bf16 GEMM (BASELINE configs[4] (i): dense [N,N] adjacency x support on the bf16 MFMA; any large X.W) ------
  * C[M,N] = act(A[M,K] . Bt[N,K]^T + bias): A and Bt are bf16 with K-contiguous rows of Kp elements (Kp % 64 == 0, zero

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _c = ctypes
 _P = _c.c_void_p
@@ -16,6 +16,7 @@ _I = _c.c_int
 _L = _c.c_int64
 _F = _c.c_float
 _SZ = _c.c_size_t
+_U64 = _c.c_uint64
 _PP = _c.POINTER(_c.c_void_p)
 
 # name -> argtypes, in the order of include/mgnns_hip.h
@@ -91,6 +92,13 @@ SIGNATURES = {
     "mgnns_debug_stamp": [_P, _I, _P],
     "mgnns_debug_spin": [_I, _P, _I, _P],
     "mgnns_layernorm_fwd": [_P, _I, _I, _P, _P, _F, _P, _P],
+    "mgnns_mha_train_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _U64, _F, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mgnns_mha_train_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                            _P, _SZ, _P],
+    "mgnns_wgrad_fwd": [_P, _I, _I, _P, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_drop_res_ln_fwd": [_P, _P, _I, _I, _P, _P, _F, _U64, _I, _F, _P, _P, _P, _P, _P],
+    "mgnns_drop_res_ln_bwd": [_P, _P, _P, _P, _P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
+    "mgnns_train_eltwise": [_I, _P, _P, _L, _P, _P],
     "mgnns_comm_unique_id": [_P, _SZ],
     "mgnns_comm_init_rank": [_I, _I, _P, _SZ, _PP],
     "mgnns_comm_init_all": [_I, _P, _PP],
@@ -119,6 +127,8 @@ SIZE_GETTERS = {
     "mgnns_bilstm_bf16_fold_workspace_bytes": [_I],
     "mgnns_label_gcn_scratch_bytes": [_I, _I, _I],
     "mgnns_mha_tail_c16_scratch_floats": [_I, _I],
+    "mgnns_mha_train_bwd_workspace_bytes": [_I, _I, _I, _I],
+    "mgnns_wgrad_workspace_bytes": [_I, _I, _I],
 }
 
 _lib = None

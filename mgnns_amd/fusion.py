@@ -6,14 +6,16 @@ MyAnotherMultiHeadAttention :298-324): same class names, constructor arguments, 
 names and shapes (so reference checkpoints load with strict=True), same return values.
 The arithmetic is in libmgnns_hip.so; these classes only hold parameters and sequence kernels.
 
-Eval/forward only: the kernels implement no dropout and no backward, so forward() refuses to
-run in training mode instead of silently diverging from the reference.
+MultiHeadAttention, PositionwiseFeedForward and MyMultiHeadAttention also train: in training mode (fp32 precision) they
+run the dropout + backward kernels of csrc/mha_train.hip through mgnns_amd/train.py.  run_stack (the fused eval chain)
+refuses training mode.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
+from . import train as _train
 
 
 import os as _os
@@ -132,15 +134,24 @@ class MultiHeadAttention(nn.Module):
         self.fc = nn.Linear(n_head * d_v, d_model)
         nn.init.xavier_normal_(self.fc.weight)
         self.dropout = nn.Dropout(dropout)
+        # ScaledDotProductAttention's dropout on the attention probabilities (submodules.py:97-103: attn_dropout=0.1 whatever
+        # the layer's `dropout`): stands in for the reference's `attention.dropout` (`attention` is the mode string here)
+        self.attn_dropout = nn.Dropout(0.1)
+        self.last_dropout_seed = None
 
     def forward(self, q, k, v, mask=None):
-        """q [B,1,d]; k = v = memory bank [B,L,d]; mask [B,1,L] or None -> (out [B,1,d], attn [H*B,1,L])."""
-        _require_eval(self)
+        """q [B,1,d]; k = v = memory bank [B,L,d]; mask [B,1,L] or None -> (out [B,1,d], attn [H*B,1,L]).
+        Training mode: fp32 only, attn after dropout; gradients reach every parameter, q and the bank (a MemoryBank's .f32)."""
         if q.dim() != 3 or q.shape[1] != 1:
             raise ValueError("the fusion attention is single-query: q must be [B,1,d], got %s" % (tuple(q.shape),))
         if k is not v and (isinstance(k, MemoryBank) or isinstance(v, MemoryBank) or
                            k.data_ptr() != v.data_ptr() or k.shape != v.shape):
             raise ValueError("key and value must be the same memory bank (as at every reference call site)")
+        if self.training:
+            x = k.f32 if isinstance(k, MemoryBank) else k
+            if x is None:
+                raise ValueError("training mode needs the fp32 memory bank")
+            return _train.mha_train_forward(self, q, x, mask)
         bank = k if isinstance(k, MemoryBank) else MemoryBank(f32=k.contiguous())
         B = q.shape[0]
         q2 = q.reshape(B, -1).contiguous()
@@ -205,9 +216,11 @@ class PositionwiseFeedForward(nn.Module):
         self.w_2 = nn.Conv1d(d_hid, d_in, 1)
         self.layer_norm = LayerNorm(d_in)
         self.dropout = nn.Dropout(dropout)
+        self.last_dropout_seed = None
 
     def forward(self, x):
-        _require_eval(self)
+        if self.training:
+            return _train.ffn_train_forward(self, x)
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).contiguous()
         w1 = self.w_1.weight.detach().view(self.w_1.out_channels, self.w_1.in_channels)

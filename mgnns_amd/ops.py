@@ -1579,3 +1579,165 @@ def stamp(name):
         raise RuntimeError("timeline full")
     names.append(name)
     _lib.check(_lib.lib().mgnns_debug_stamp(_p(slots), len(names) - 1, _stream()), "mgnns_debug_stamp")
+
+
+# ---- training mode of the fusion layers (csrc/mha_train.hip; fp32, GPU only) ----------------------------------------------
+# dropout sites of the counter-based masks: (seed, site, element index) -> keep
+DROP_ATTN, DROP_FC, DROP_FFN = 0, 1, 2
+ELT_ADD, ELT_RELU_BWD = 0, 1
+TRAIN_MAX_L, TRAIN_MAX_D, TRAIN_MAX_H = 208, 320, 8
+
+
+def _chk_rate(rate):
+    rate = float(rate)
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError("dropout rate %g outside [0, 1]" % rate)
+    return rate
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def mha_attn_train(qh, bank, mask, n_head, d_kv, wk, wv, bv, seed, rate, return_masks=False):
+    """Training forward of the single-query attention core (mgnns_mha_train_fwd): the folded attention of sq_mha_folded with
+    dropout(rate) on the probabilities.  bank fp32 [B, L, D]; mask [B, L] (0 = masked) or None.
+    -> (o [B, H*dk], attn [H*B, 1, L] after dropout, saved) (+ keep [H*B, 1, L] bool with return_masks); `saved` is what
+    mha_attn_train_backward takes."""
+    _chk(qh, "qh", ndim=2)
+    _chk(bank, "memory bank", ndim=3)
+    B, L_, D = bank.shape
+    for n, t in (("w_ks.weight", wk), ("w_vs.weight", wv)):
+        _chk(t, n, ndim=2)
+    _chk(bv, "w_vs.bias", ndim=1)
+    if qh.shape != (B, n_head * d_kv):
+        raise ValueError("qh shape %s, expected %s" % (tuple(qh.shape), (B, n_head * d_kv)))
+    if wk.shape != (n_head * d_kv, D) or wv.shape != (n_head * d_kv, D) or bv.shape != (n_head * d_kv,):
+        raise ValueError("w_ks %s / w_vs %s / b_vs %s do not match H=%d d_kv=%d D=%d" % (tuple(wk.shape), tuple(wv.shape),
+                                                                                        tuple(bv.shape), n_head, d_kv, D))
+    if not (0 < L_ <= TRAIN_MAX_L and 0 < D <= TRAIN_MAX_D and D % 4 == 0 and 0 < n_head <= TRAIN_MAX_H and d_kv % 4 == 0):
+        raise ValueError("training attention supports L <= %d, d_model <= %d (multiple of 4), n_head <= %d, d_kv %% 4 == 0; "
+                         "got L=%d d_model=%d n_head=%d d_kv=%d" % (TRAIN_MAX_L, TRAIN_MAX_D, TRAIN_MAX_H, L_, D, n_head, d_kv))
+    if mask is not None:
+        _chk(mask, "mask", ndim=2)
+        if mask.shape != (B, L_):
+            raise ValueError("mask shape %s, expected %s" % (tuple(mask.shape), (B, L_)))
+    rate = _chk_rate(rate)
+    dev, f32 = qh.device, torch.float32
+    U = torch.empty(n_head, B, D, device=dev, dtype=f32)
+    P = torch.empty(n_head, B, L_, device=dev, dtype=f32)
+    attn = torch.empty(n_head * B, 1, L_, device=dev, dtype=f32)
+    keep = torch.empty(n_head * B, 1, L_, device=dev, dtype=torch.uint8)
+    Z = torch.empty(n_head, B, D, device=dev, dtype=f32)
+    SP = torch.empty(n_head, B, device=dev, dtype=f32)
+    o = torch.empty(B, n_head * d_kv, device=dev, dtype=f32)
+    L = _lib.lib()
+    _launch("mgnns_mha_train_fwd", ("mgnns_mha_train_fwd", L_), L.mgnns_mha_train_fwd, _p(qh), _p(bank), _p(mask), B, L_, D,
+            n_head, d_kv, _p(wk), _p(wv), _p(bv), _seed64(seed), rate, _p(U), _p(P), _p(attn), _p(keep), _p(Z), _p(SP), _p(o),
+            _stream())
+    saved = dict(U=U, P=P, attn=attn, keep=keep, Z=Z, SP=SP, rate=rate, n_head=n_head, d_kv=d_kv)
+    if return_masks:
+        return o, attn, saved, keep.bool()
+    return o, attn, saved
+
+
+def mha_attn_train_backward(dO, qh, bank, mask, wk, wv, bv, saved, want_dbank=True):
+    """Backward of mha_attn_train (mgnns_mha_train_bwd): one streaming pass pair over the bank.
+    -> (dqh [B, H*dk], dWk, dWv [H*dk, D], dbv [H*dk], dbank [B, L, D] or None).  b_k has no gradient (it drops out of the
+    softmax)."""
+    _chk(dO, "dO", ndim=2)
+    _chk(bank, "memory bank", ndim=3)
+    B, L_, D = bank.shape
+    H, dk = saved["n_head"], saved["d_kv"]
+    if dO.shape != (B, H * dk):
+        raise ValueError("dO shape %s, expected %s" % (tuple(dO.shape), (B, H * dk)))
+    dev, f32 = dO.device, torch.float32
+    dqh = torch.empty(B, H * dk, device=dev, dtype=f32)
+    dWk = torch.empty(H * dk, D, device=dev, dtype=f32)
+    dWv = torch.empty(H * dk, D, device=dev, dtype=f32)
+    dbv = torch.empty(H * dk, device=dev, dtype=f32)
+    dbank = torch.empty(B, L_, D, device=dev, dtype=f32) if want_dbank else None
+    L = _lib.lib()
+    nbytes = L.mgnns_mha_train_bwd_workspace_bytes(B, D, H, dk)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    s = saved
+    _launch("mgnns_mha_train_bwd", ("mgnns_mha_train_bwd", L_), L.mgnns_mha_train_bwd, _p(dO), _p(qh), _p(bank), _p(mask), B, L_,
+            D, H, dk, _p(wk), _p(wv), _p(bv), s["rate"], _p(s["U"]), _p(s["P"]), _p(s["attn"]), _p(s["keep"]), _p(s["Z"]),
+            _p(s["SP"]), _p(dqh), _p(dWk), _p(dWv), _p(dbv), _p(dbank), _p(ws), nbytes, _stream())
+    return dqh, dWk, dWv, dbv, dbank
+
+
+def wgrad(dy, x, bias=True):
+    """Weight gradient of y = x W^T + b: (dW = dy^T x [N, K], db = dy.sum(0) [N] or None); rows reduced in a fixed order."""
+    _chk(dy, "dy", ndim=2)
+    _chk(x, "x", ndim=2)
+    if dy.shape[0] != x.shape[0]:
+        raise ValueError("wgrad rows: dy %s, x %s" % (tuple(dy.shape), tuple(x.shape)))
+    M, N = dy.shape
+    K = x.shape[1]
+    dW = torch.empty(N, K, device=dy.device, dtype=torch.float32)
+    db = torch.empty(N, device=dy.device, dtype=torch.float32) if bias else None
+    L = _lib.lib()
+    nbytes = L.mgnns_wgrad_workspace_bytes(M, N, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    _launch("mgnns_wgrad_fwd", ("mgnns_wgrad_fwd", M, N, K), L.mgnns_wgrad_fwd, _p(dy), M, N, _p(x), K, _p(dW), _p(db), _p(ws),
+            nbytes, _stream())
+    return dW, db
+
+
+def dropout_residual_layernorm(x, res, gamma, beta, eps, seed, site, rate, return_masks=False):
+    """y = LayerNorm(dropout(x) + res) with the reference's LayerNorm (unbiased std, eps added to the std), training mode
+    (mgnns_drop_res_ln_fwd).  -> (y, saved) (+ keep bool [rows, D] with return_masks)."""
+    D = x.shape[-1]
+    x2 = _chk(x.reshape(-1, D), "x")
+    r2 = _chk(res.reshape(-1, D), "residual")
+    _chk(gamma, "gamma", ndim=1)
+    _chk(beta, "beta", ndim=1)
+    if r2.shape != x2.shape or gamma.shape != (D,) or beta.shape != (D,):
+        raise ValueError("dropout_residual_layernorm: x %s, residual %s, gamma %s" % (tuple(x.shape), tuple(res.shape),
+                                                                                     tuple(gamma.shape)))
+    rate = _chk_rate(rate)
+    rows = x2.shape[0]
+    y = torch.empty_like(x2)
+    xhat = torch.empty_like(x2)
+    sig = torch.empty(rows, device=x.device, dtype=torch.float32)
+    keep = torch.empty(rows, D, device=x.device, dtype=torch.uint8)
+    L = _lib.lib()
+    _launch("mgnns_drop_res_ln_fwd", ("mgnns_drop_res_ln_fwd", D), L.mgnns_drop_res_ln_fwd, _p(x2), _p(r2), rows, D, _p(gamma),
+            _p(beta), float(eps), _seed64(seed), int(site), rate, _p(y), _p(xhat), _p(sig), _p(keep), _stream())
+    saved = dict(xhat=xhat, sig=sig, keep=keep, rate=rate, eps=float(eps))
+    y = y.view(x.shape)
+    if return_masks:
+        return y, saved, keep.bool()
+    return y, saved
+
+
+def dropout_residual_layernorm_backward(dy, gamma, saved, dy2=None):
+    """Backward of dropout_residual_layernorm for dy (+ dy2): (d residual, d x, d gamma, d beta)."""
+    xhat = saved["xhat"]
+    rows, D = xhat.shape
+    dy = _chk(dy.reshape(rows, D), "dy")
+    if dy2 is not None:
+        dy2 = _chk(dy2.reshape(rows, D), "dy2")
+    dres = torch.empty_like(xhat)
+    dx = torch.empty_like(xhat)
+    dg = torch.empty(D, device=xhat.device, dtype=torch.float32)
+    db = torch.empty(D, device=xhat.device, dtype=torch.float32)
+    L = _lib.lib()
+    _launch("mgnns_drop_res_ln_bwd", ("mgnns_drop_res_ln_bwd", D), L.mgnns_drop_res_ln_bwd, _p(dy), _p(dy2), _p(xhat),
+            _p(saved["sig"]), _p(saved["keep"]), rows, D, _p(gamma), saved["eps"], saved["rate"], _p(dres), _p(dx), _p(dg), _p(db),
+            _stream())
+    return dres, dx, dg, db
+
+
+def train_eltwise(op, a, b):
+    """ELT_ADD: a + b;  ELT_RELU_BWD: a * (b > 0) (b = the ReLU's output)."""
+    _chk(a, "a")
+    _chk(b, "b")
+    if a.shape != b.shape:
+        raise ValueError("train_eltwise shapes %s / %s" % (tuple(a.shape), tuple(b.shape)))
+    y = torch.empty_like(a)
+    L = _lib.lib()
+    _launch("mgnns_train_eltwise", ("mgnns_train_eltwise", op), L.mgnns_train_eltwise, int(op), _p(a), _p(b), a.numel(), _p(y),
+            _stream())
+    return y

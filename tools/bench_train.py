@@ -1,0 +1,133 @@
+#!/usr/bin/env python
+"""Training mode of one MyMultiHeadAttention layer (csrc/mha_train.hip) at B=256, H=4: L=196 unmasked and L=100 masked (ragged
+lengths).  HIP events around n calls: the layer's training forward + backward, each new entry point with its algorithmic bytes
+and achieved GB/s, and for context the same layer through plain torch autograd (fp32, on the GPU).  One JSON line per case.
+Usage: python tools/bench_train.py [--iters N]"""
+import json
+import math
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mgnns_amd import fusion, ops  # noqa: E402
+
+DEV = "cuda:0"
+D, DK = 300, 128
+
+
+def timeit(fn, n, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    a = torch.cuda.Event(enable_timing=True)
+    b = torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n * 1e3          # us per call
+
+
+def torch_layer(p, q, bank, mask, H):
+    """The reference's formulation in plain torch (K and V projected), training-mode dropout."""
+    B, L, _ = bank.shape
+    qh = F.linear(q, p["wq"], p["bq"]).view(B, H, DK)
+    kh = F.linear(bank, p["wk"], p["bk"]).view(B, L, H, DK)
+    vh = F.linear(bank, p["wv"], p["bv"]).view(B, L, H, DK)
+    s = torch.einsum("bhd,blhd->bhl", qh, kh) / math.sqrt(DK)
+    if mask is not None:
+        s = s.masked_fill(mask[:, None, :] == 0, float("-inf"))
+    pa = F.dropout(torch.softmax(s, dim=2), 0.1)
+    o = torch.einsum("bhl,blhd->bhd", pa, vh).reshape(B, H * DK)
+
+    def ln(x, g, b):
+        return g * (x - x.mean(-1, keepdim=True)) / (x.std(-1, keepdim=True) + 1e-6) + b
+
+    y = ln(F.dropout(F.linear(o, p["wfc"], p["bfc"]), 0.1) + q, p["g1"], p["be1"])
+    z = F.linear(F.relu(F.linear(y, p["w1"], p["b1"])), p["w2"], p["b2"])
+    return ln(F.dropout(z, 0.1) + y, p["g2"], p["be2"])
+
+
+def case(B, H, L, masked, n):
+    torch.manual_seed(0)
+    m = fusion.MyMultiHeadAttention(H, D, DK, dropout=0.1).to(DEV).train()
+    g = torch.Generator(device=DEV).manual_seed(1)
+    q = torch.randn(B, D, device=DEV, generator=g).requires_grad_(True)
+    bank = torch.randn(B, L, D, device=DEV, generator=g).requires_grad_(True)
+    G = torch.randn(B, D, device=DEV, generator=g)
+    mask, live = None, B * L
+    if masked:
+        lens = torch.randint(1, L + 1, (B,), device=DEV, generator=g)
+        mask = (torch.arange(L, device=DEV)[None, :] < lens[:, None]).float()
+        live = int(lens.sum())
+    res = {"case": "B%d_H%d_L%d_%s" % (B, H, L, "masked" if masked else "full"), "live_rows": live}
+
+    def layer_fwd():
+        return m(q, bank, bank, mask)[0]
+
+    def layer_fwd_bwd():
+        out = layer_fwd()
+        torch.autograd.backward(out, G)
+
+    res["layer_fwd_us"] = timeit(lambda: layer_fwd(), n)
+    res["layer_fwd_bwd_us"] = timeit(layer_fwd_bwd, n)
+
+    # the new entry points on their own, at the layer's shapes
+    a = m.slf_attn
+    wk, wv, bv = a.w_ks.weight.detach(), a.w_vs.weight.detach(), a.w_vs.bias.detach()
+    qh = torch.randn(B, H * DK, device=DEV, generator=g)
+    x = bank.detach()
+    o, attn, saved = ops.mha_attn_train(qh, x, mask, H, DK, wk, wv, bv, 7, 0.1)
+    dO = torch.randn(B, H * DK, device=DEV, generator=g)
+    f4 = 4
+    xbytes = live * D * f4                                            # one read of the live bank rows
+    hbl = H * B * L * f4
+    kern = {}
+    t = timeit(lambda: ops.mha_attn_train(qh, x, mask, H, DK, wk, wv, bv, 7, 0.1), n)
+    by = xbytes + 2 * H * DK * D * f4 + 3 * hbl + hbl // 4 + 3 * H * B * D * f4 + B * H * DK * f4
+    kern["mha_train_fwd"] = (t, by)
+    t = timeit(lambda: ops.mha_attn_train_backward(dO, qh, x, mask, wk, wv, bv, saved, want_dbank=True), n)
+    by = 2 * xbytes + B * L * D * f4 + 3 * hbl + 5 * H * B * D * f4 + 4 * H * DK * D * f4 + 2 * B * H * DK * f4
+    kern["mha_train_bwd (bank x2 + dbank)"] = (t, by)
+    y = torch.randn(B, D, device=DEV, generator=g)
+    gam, bet = a.layer_norm.gamma.detach(), a.layer_norm.beta.detach()
+    _, ln_saved = ops.dropout_residual_layernorm(y, y, gam, bet, 1e-6, 3, ops.DROP_FC, 0.1)
+    t = timeit(lambda: ops.dropout_residual_layernorm(y, y, gam, bet, 1e-6, 3, ops.DROP_FC, 0.1), n)
+    kern["drop_res_ln_fwd"] = (t, 4 * B * D * f4 + B * D)
+    t = timeit(lambda: ops.dropout_residual_layernorm_backward(y, gam, ln_saved), n)
+    kern["drop_res_ln_bwd"] = (t, 5 * B * D * f4 + B * D)
+    t = timeit(lambda: ops.wgrad(y, y), n)
+    kern["wgrad 300x300"] = (t, 2 * B * D * f4 + D * D * f4)
+    res["kernels"] = {k: {"us": round(v[0], 2), "alg_bytes": v[1], "GB/s": round(v[1] / v[0] / 1e3, 1)} for k, v in kern.items()}
+
+    # plain torch autograd, same layer, fp32 on the GPU
+    f = m.pos_ffn
+    p = {"wq": a.w_qs.weight, "bq": a.w_qs.bias, "wk": a.w_ks.weight, "bk": a.w_ks.bias, "wv": a.w_vs.weight, "bv": a.w_vs.bias,
+         "wfc": a.fc.weight, "bfc": a.fc.bias, "g1": a.layer_norm.gamma, "be1": a.layer_norm.beta,
+         "w1": f.w_1.weight.view(D, D), "b1": f.w_1.bias, "w2": f.w_2.weight.view(D, D), "b2": f.w_2.bias,
+         "g2": f.layer_norm.gamma, "be2": f.layer_norm.beta}
+
+    def torch_fwd_bwd():
+        torch.autograd.backward(torch_layer(p, q, bank, mask, H), G)
+
+    res["torch_fwd_us"] = timeit(lambda: torch_layer(p, q, bank, mask, H), n)
+    res["torch_fwd_bwd_us"] = timeit(torch_fwd_bwd, n)
+    for k in ("layer_fwd_us", "layer_fwd_bwd_us", "torch_fwd_us", "torch_fwd_bwd_us"):
+        res[k] = round(res[k], 1)
+    return res
+
+
+def main():
+    n = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 20
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_train: no GPU")
+    for B, H, L, masked in ((256, 4, 196, False), (256, 4, 100, True)):
+        print(json.dumps(case(B, H, L, masked, n)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
