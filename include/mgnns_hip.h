@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 19
+#define MGNNS_ABI_VERSION 20
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -564,10 +564,44 @@ int mgnns_drop_res_ln_fwd(const float* x, const float* res, int rows, int D, con
 int mgnns_drop_res_ln_bwd(const float* dy, const float* dy2, const float* xhat, const float* sig, const uint8_t* keep, int rows,
                           int D, const float* gamma, float eps, float rate, float* dres, float* dx, float* dgamma, float* dbeta,
                           mgnns_stream_t stream);
-/* y = a + b (MGNNS_ELT_ADD) or y = a * (b > 0) (MGNNS_ELT_RELU_BWD: ReLU backward, b = the ReLU's output), n elements. */
-#define MGNNS_ELT_ADD      0
-#define MGNNS_ELT_RELU_BWD 1
+/* y = a + b (MGNNS_ELT_ADD), y = a * (b > 0) (MGNNS_ELT_RELU_BWD: ReLU backward, b = the ReLU's output) or
+ * y = b > 0 ? a : 0.2 a (MGNNS_ELT_LRELU2_BWD: LeakyReLU(0.2) backward, b = its output or input), n elements. */
+#define MGNNS_ELT_ADD        0
+#define MGNNS_ELT_RELU_BWD   1
+#define MGNNS_ELT_LRELU2_BWD 2
 int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float* y, mgnns_stream_t stream);
+
+/* ---- training mode of the model around the fusion stacks (MODEL:431-567), fp32 -------------------------------------------
+ * Dropout sites of the model (the hash above; index = flat element index of the tensor the site drops):
+ * 3 = the label Attention's softmax(energy) [B, NLQ, H*dh], 4 = the classifier's dropout after multi_linear_1 [B, D].
+ *
+ * mgnns_imgbank_wgrad: weight gradient of an image memory bank bank[b,p,:] = W X[b,:,p] + c from dbank [B, P, N] and the feature
+ * map X [B, K, P] in its native layout: dW[N, K] = sum_{b,p} dbank[b,p,:] (x) X[b,:,p], db[N] (written).  N <= 320.  Exact-f32
+ * MFMA, the (b, p) reduction split into slabs combined in a fixed order.  workspace:
+ * mgnns_imgbank_wgrad_workspace_bytes(B, K, P, N) bytes.
+ * mgnns_label_attn_train_fwd: the label attention between its projections with dropout: Q [NLQ, H*dh], K = w_k(x), V = w_v(x)
+ * [B, H*dh] -> x [B, NLQ, H*dh] = dropout(softmax_dh(Q K / sqrt(dh))) V, and for the backward P (softmax before dropout) and
+ * keep (bytes), both [B, NLQ, H*dh].  dh <= 64.
+ * mgnns_label_attn_train_bwd: its backward from dx: dQ [NLQ, H*dh] (summed over the batch in order), dK, dV [B, H*dh].
+ * workspace: mgnns_label_attn_train_bwd_workspace_bytes(B, NLQ, H, dh) bytes.
+ * mgnns_dropout_fwd / _bwd: y = dropout(x) at `site` (keep written as bytes); dx = dy keep / (1 - rate).
+ * mgnns_dropout_mask: the keep mask of elements 0..n-1 of a site as bytes (what the training kernels draw for that seed).
+ */
+#define MGNNS_DROP_LABEL_ATTN 3
+#define MGNNS_DROP_HEAD       4
+size_t mgnns_imgbank_wgrad_workspace_bytes(int B, int K, int P, int N);
+int mgnns_imgbank_wgrad(const float* X, const float* dbank, int B, int K, int P, int N, float* dW, float* db, void* workspace,
+                        size_t workspace_bytes, mgnns_stream_t stream);
+int mgnns_label_attn_train_fwd(const float* Q, const float* K, const float* V, int B, int NLQ, int H, int dh, uint64_t seed,
+                               float rate, float* x, float* P, uint8_t* keep, mgnns_stream_t stream);
+size_t mgnns_label_attn_train_bwd_workspace_bytes(int B, int NLQ, int H, int dh);
+int mgnns_label_attn_train_bwd(const float* dx, const float* Q, const float* K, const float* V, const float* P,
+                               const uint8_t* keep, int B, int NLQ, int H, int dh, float rate, float* dQ, float* dK, float* dV,
+                               void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
+int mgnns_dropout_fwd(const float* x, int64_t n, uint64_t seed, int site, float rate, float* y, uint8_t* keep,
+                      mgnns_stream_t stream);
+int mgnns_dropout_bwd(const float* dy, const uint8_t* keep, int64_t n, float rate, float* dx, mgnns_stream_t stream);
+int mgnns_dropout_mask(uint64_t seed, int site, float rate, int64_t n, uint8_t* keep, mgnns_stream_t stream);
 
 /* ---- dense bf16 GEMM (BASELINE configs[4] (i): dense [N,N] adjacency x support on the bf16 MFMA; any large X.W) ------
  * C[M,N] = act(A[M,K] . Bt[N,K]^T + bias): A and Bt are bf16 with K-contiguous rows of Kp elements (Kp % 64 == 0, zero

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _c = ctypes
 _P = _c.c_void_p
@@ -99,6 +99,12 @@ SIGNATURES = {
     "mgnns_drop_res_ln_fwd": [_P, _P, _I, _I, _P, _P, _F, _U64, _I, _F, _P, _P, _P, _P, _P],
     "mgnns_drop_res_ln_bwd": [_P, _P, _P, _P, _P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
     "mgnns_train_eltwise": [_I, _P, _P, _L, _P, _P],
+    "mgnns_imgbank_wgrad": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_label_attn_train_fwd": [_P, _P, _P, _I, _I, _I, _I, _U64, _F, _P, _P, _P, _P],
+    "mgnns_label_attn_train_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _SZ, _P],
+    "mgnns_dropout_fwd": [_P, _L, _U64, _I, _F, _P, _P, _P],
+    "mgnns_dropout_bwd": [_P, _P, _L, _F, _P, _P],
+    "mgnns_dropout_mask": [_U64, _I, _F, _L, _P, _P],
     "mgnns_comm_unique_id": [_P, _SZ],
     "mgnns_comm_init_rank": [_I, _I, _P, _SZ, _PP],
     "mgnns_comm_init_all": [_I, _P, _PP],
@@ -129,6 +135,8 @@ SIZE_GETTERS = {
     "mgnns_mha_tail_c16_scratch_floats": [_I, _I],
     "mgnns_mha_train_bwd_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_wgrad_workspace_bytes": [_I, _I, _I],
+    "mgnns_imgbank_wgrad_workspace_bytes": [_I, _I, _I, _I],
+    "mgnns_label_attn_train_bwd_workspace_bytes": [_I, _I, _I, _I],
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 // second launch with the same seed draws the same mask.  Every reduction over samples or rows runs in a fixed order (slabs +
 // an ordered combine, no float atomics), so one seed gives bit-identical outputs and gradients.
 #include "common.hpp"
+#include "dropout_hash.hpp"
 
 int mg_launch_gemm_batched(const float* X, int ldx, long sx, int M, int K, const float* W, long sw, int w_is_kn,
                            const float* bias, long sb, int N, float* Y, int ldy, long sy, int nbatch,
@@ -26,17 +27,6 @@ constexpr int MAXH = 8;
 constexpr int MAXL = 208;
 constexpr int WAVES = 8;
 constexpr int NT = WAVES * 64;
-
-// splitmix64 finaliser of (seed, site, index) -> uniform in [0, 1) with 24 bits; kept iff u >= rate
-__device__ __forceinline__ bool mg_keep(uint64_t seed, int site, uint64_t idx, float rate) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((((uint64_t)site) << 48) + idx + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f) >= rate;
-}
-
-__host__ __device__ inline float keep_scale(float rate) { return rate < 1.0f ? 1.0f / (1.0f - rate) : 0.0f; }
 
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]); }
 
@@ -521,7 +511,7 @@ __global__ void ln_param_grad_kernel(const float* __restrict__ dy, const float* 
 
 __global__ void eltwise_kernel(int op, const float* __restrict__ a, const float* __restrict__ b, long n, float* __restrict__ y) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        y[i] = op == 0 ? a[i] + b[i] : (b[i] > 0.f ? a[i] : 0.f);
+        y[i] = op == MGNNS_ELT_ADD ? a[i] + b[i] : (b[i] > 0.f ? a[i] : (op == MGNNS_ELT_LRELU2_BWD ? 0.2f * a[i] : 0.f));
 }
 
 unsigned grid1d(size_t n) {
@@ -659,7 +649,8 @@ extern "C" int mgnns_drop_res_ln_bwd(const float* dy, const float* dy2, const fl
 
 extern "C" int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float* y, mgnns_stream_t stream) {
     MG_REQUIRE(a && b && y, "mgnns_train_eltwise: null pointer");
-    MG_REQUIRE(op == MGNNS_ELT_ADD || op == MGNNS_ELT_RELU_BWD, "mgnns_train_eltwise: unknown op %d", op);
+    MG_REQUIRE(op == MGNNS_ELT_ADD || op == MGNNS_ELT_RELU_BWD || op == MGNNS_ELT_LRELU2_BWD, "mgnns_train_eltwise: unknown op %d",
+               op);
     if (n <= 0) return 0;
     hipLaunchKernelGGL(eltwise_kernel, dim3(grid1d((size_t)n)), dim3(256), 0, (hipStream_t)stream, op, a, b, (long)n, y);
     MG_CHECK_LAUNCH("mgnns_train_eltwise");

@@ -5,7 +5,8 @@ engine can construct it, load its checkpoints with strict=True and call
 ``model(text, text_lens, text_mask, object_img, place_img, object_inp, place_inp)``
 (engine/Multi_GCN_Multihead_Att_engine.py:825) unchanged.
 
-All forward arithmetic of the hot path runs in libmgnns_hip.so.  Eval / forward only.
+All forward arithmetic of the hot path runs in libmgnns_hip.so.  Training mode (fp32) trains every parameter above the CNN
+trunks and the text encoders (Multi_GCN_Multihead_Att.forward, mgnns_amd/train.py); the trunks and text encoders are eval only.
 """
 import os
 import pickle
@@ -16,6 +17,7 @@ import torch.nn as nn
 from torch.nn import Parameter
 
 from . import _lib, ops
+from . import train as _train
 from .adjacency import gen_A, gen_adj_csr
 from .fusion import (MemoryBank, MultiHeadAttention, MyAnotherMultiHeadAttention, MyMultiHeadAttention, first_query, make_mask_plan,
                      mask_plan_applies,
@@ -59,6 +61,18 @@ class GraphConvolution(nn.Module):
             self.bias.data.uniform_(-stdv, stdv)
 
     def forward(self, input, adj, act=ops.ACT_NONE):
+        """Training mode with autograd on (and `weight` or `input` requiring a gradient): gradients reach both; `adj` must then be
+        the dense adjacency or a pair (CSR, CSR of its transpose) -- the backward propagates with adj^T (no bias: the reference
+        never builds one).  Otherwise the forward below (the layer has no dropout: both modes compute the same values)."""
+        if self.training and torch.is_grad_enabled() and (self.weight.requires_grad or input.requires_grad):
+            if self.bias is not None:
+                raise NotImplementedError("GraphConvolution(bias=True) has no training mode (the reference never builds one)")
+            if torch.is_tensor(adj):
+                a = adj.detach().float().contiguous()
+                adj = (ops.dense_to_csr(a), ops.dense_to_csr(ops.transpose_pad(a, a.shape[0])))
+            elif len(adj) != 2:
+                raise ValueError("training mode needs the dense adjacency or (csr, csr of its transpose)")
+            return _train.GCNFunction.apply(input.float().contiguous(), self.weight, adj[0], adj[1], act)
         support = ops.matmul(input.float().contiguous(), self.weight.detach())
         if torch.is_tensor(adj):
             adj = ops.dense_to_csr(adj.contiguous())
@@ -84,11 +98,12 @@ class Attention(nn.Module):
         self.do = nn.Dropout(dropout)
 
     def forward(self, query, key, value, mask=None):
-        """query [NLQ,hid] (label GloVe, any float dtype), key = value [B,image_dim] -> [B,NLQ,hid]."""
-        if self.training:
-            raise RuntimeError("Attention: eval-mode forward only on the HIP path; call .eval()")
+        """query [NLQ,hid] (label GloVe, any float dtype), key = value [B,image_dim] -> [B,NLQ,hid].  Training mode: dropout
+        (self.do) on softmax(energy), one seed per forward kept as last_dropout_seed; gradients reach every parameter and key."""
         if key.data_ptr() != value.data_ptr():
             raise ValueError("key and value must be the same tensor (as at MODEL:476,503)")
+        if self.training:
+            return _train.label_attention_train_forward(self, query, key, mask)
         Q = ops.linear(query.float().contiguous(), self.w_q.weight.detach(), self.w_q.bias.detach())
         K = ops.linear(key.contiguous(), self.w_k.weight.detach(), self.w_k.bias.detach())
         V = ops.linear(key.contiguous(), self.w_v.weight.detach(), self.w_v.bias.detach())
@@ -219,6 +234,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self.register_buffer('label_query', None, persistent=False)
         self._load_label_query(label_glove if label_glove is not None else opt.get('label_glove'))
         self._wt_cache = {}
+        self._adj_cache = {}                   # training mode: (CSR, CSR of the transpose) of gen_adj(A) per adjacency version
+        self.last_dropout_seed = None          # training mode: the classifier dropout's seed of the last forward
         self._lstm_cache = ops.LstmCache()     # derived LSTM weight forms live and die with this module
         self._streams = None
         self.use_streams = bool(opt.get('use_streams', True))
@@ -569,8 +586,9 @@ class Multi_GCN_Multihead_Att(nn.Module):
 
     def forward(self, text, text_lens, text_mask, object_feature, place_feature, object_inp, place_inp,
                 return_last_state=True):
-        if self.training:
-            raise RuntimeError("Multi_GCN_Multihead_Att: eval-mode forward only on the HIP path; call .eval()")
+        """Eval mode: the scheduled forward on four streams (forward_plan).  Training mode (_forward_train): the reference's
+        training forward in fp32 -- dropout at every site, logits with an autograd graph -- above frozen, eval-mode text
+        encoders (freeze_text_encoders) and precomputed feature maps."""
         if self.label_query is None:
             raise RuntimeError("label query missing: pass label_glove=... / opt['label_glove'], call "
                                "set_label_query(), or run from a directory holding %s" % (LABEL_GLOVE_CANDIDATES,))
@@ -579,9 +597,94 @@ class Multi_GCN_Multihead_Att(nn.Module):
                 raise RuntimeError("%s is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % (name, t.device))
         if self.label_query.device != text.device:
             self.label_query = self.label_query.to(text.device)
+        if self.training:
+            return self._forward_train(text, text_lens, text_mask, object_feature, place_feature, object_inp, place_inp)
         with torch.no_grad():
             return self._forward_streams(text, text_lens, text_mask, object_feature, place_feature,
                                          object_inp, place_inp)
+
+    # ---- training mode --------------------------------------------------------------------------------------------------
+    TEXT_ENCODERS = ('text_features', 'lstm', 'embedding')
+
+    def freeze_text_encoders(self):
+        """requires_grad_(False) and .eval() on the text encoders (text_features, lstm, embedding), which have no backward here:
+        what training mode needs after every model.train() (which puts them back in training mode)."""
+        for n in self.TEXT_ENCODERS:
+            getattr(self, n).requires_grad_(False).eval()
+        return self
+
+    def _refuse_untrainable(self):
+        if self.precision != 'fp32':
+            raise NotImplementedError("training mode runs in fp32 only (precision=%r): set_precision('fp32') before .train()"
+                                      % self.precision)
+        if self.is_regu:
+            raise NotImplementedError("training mode does not implement the is_regu head-difference gradient")
+        if not self.bidirectional:
+            raise NotImplementedError("the HIP text bank implements the bidirectional LSTM the reference configures")
+        bad = [n for n in self.TEXT_ENCODERS
+               if getattr(self, n).training or any(p_.requires_grad for p_ in getattr(self, n).parameters())]
+        if bad:
+            raise RuntimeError("Multi_GCN_Multihead_Att training mode: the text encoders (%s) have no backward on the HIP path and "
+                               "must be frozen and in eval mode (their dropout would otherwise change the forward): call "
+                               "model.freeze_text_encoders() after model.train()" % ", ".join(bad))
+
+    def _train_maps(self, x, name):
+        if not (x.dim() == 4 and x.shape[1] == 2048):
+            raise NotImplementedError("training mode takes precomputed [B,2048,h,w] feature maps for %s (the CNN trunks do not "
+                                      "train); got %s" % (name, tuple(x.shape)))
+        return x
+
+    def _adj_pair(self, A):
+        """(CSR of gen_adj(A), CSR of its transpose), built once per adjacency version."""
+        key = (A.data_ptr(), A._version, str(A.device))
+        hit = self._adj_cache.get(id(A))
+        if hit is None or hit[0] != key:
+            adj, csr = ops.gen_adj(A.detach().float().contiguous(), want_csr=True)
+            hit = (key, (csr, ops.dense_to_csr(ops.transpose_pad(adj, adj.shape[0]))))
+            self._adj_cache[id(A)] = hit
+        return hit[1]
+
+    def _forward_train(self, text, text_lens, text_mask, object_feature, place_feature, object_inp, place_inp):
+        """The reference's training forward (MODEL:431-567) as one chain of autograd Functions over HIP kernels on the current
+        stream.  The text feature and the text memory bank are constants from the eval kernels (frozen encoders); the feature
+        maps get no gradient even if they require one.  Dropout: the fusion layers' three sites, each label Attention's
+        probabilities and the classifier's; every dropping module draws one seed from torch's default generator
+        (last_dropout_seed)."""
+        self._refuse_untrainable()
+        B = text.shape[0]
+        with torch.no_grad():
+            tf = self.text_features(text)
+            text_bank = self._text_bank(text, text_lens).f32
+        mask = text_mask.float().contiguous()
+        feat, bank = {}, {}
+        for tag, trunk_in, inp, A, lin, att, l5, xl in (
+                ('obj', object_feature, object_inp, self.object_A, self.liner_img_object, self.object_attention,
+                 self.object_linear_5, self.object_x_linear),
+                ('place', place_feature, place_inp, self.place_A, self.liner_img_place, self.place_attention,
+                 self.place_linear_5, self.place_x_linear)):
+            maps = self._train_maps(trunk_in, 'object_feature' if tag == 'obj' else 'place_feature')
+            setattr(self, 'object_feature' if tag == 'obj' else 'place_feature', maps)      # MODEL:450,482 keep them
+            f3 = maps.detach().float().contiguous().view(B, maps.shape[1], -1)
+            bank[tag], pooled = _train.ImgBankFunction.apply(f3, lin.weight, lin.bias, self._wt(lin))
+            pair = self._adj_pair(A)
+            G = self.gc2(self.gc1(inp[0].float().contiguous(), pair, act=ops.ACT_LRELU2), pair)       # [C, 2048]
+            x = _train.linear(pooled, G)                                  # pooled @ G^T -> [B, C]
+            y = att(query=self.label_query, key=x, value=x)               # [B, NLQ, 300]
+            feat[tag] = _train.linear(_train.linear(y, l5).reshape(B, -1), xl)
+
+        def stack(layers, q, kv, m):
+            for layer in layers:
+                q, _ = layer(q, kv, kv, mask=m)
+            return q
+
+        iot = stack(self.img_object_text_multi_head_att, feat['obj'], text_bank, mask)
+        ipt = stack(self.img_place_text_multi_head_att, feat['place'], text_bank, mask)
+        tio = stack(self.text_img_object_multi_head_att, tf, bank['obj'], None)
+        tip = stack(self.text_img_place_multi_head_att, tf, bank['place'], None)
+        multi = _train.linear(torch.cat([tio, tip, iot, ipt], dim=1), self.multi_linear_1)
+        multi = _train.dropout_train_forward(self.dropout, multi, ops.DROP_HEAD)
+        self.last_dropout_seed = self.dropout.last_dropout_seed
+        return _train.linear(multi, self.multi_linear_2)
 
     def _side_streams(self, device):
         """The side streams of the forward's schedule by key ('s1'..'s3'), each on a hardware queue of its own

@@ -1584,7 +1584,8 @@ def stamp(name):
 # ---- training mode of the fusion layers (csrc/mha_train.hip; fp32, GPU only) ----------------------------------------------
 # dropout sites of the counter-based masks: (seed, site, element index) -> keep
 DROP_ATTN, DROP_FC, DROP_FFN = 0, 1, 2
-ELT_ADD, ELT_RELU_BWD = 0, 1
+DROP_LABEL_ATTN, DROP_HEAD = 3, 4          # the label Attention's probabilities, the classifier's dropout (model training)
+ELT_ADD, ELT_RELU_BWD, ELT_LRELU2_BWD = 0, 1, 2
 TRAIN_MAX_L, TRAIN_MAX_D, TRAIN_MAX_H = 208, 320, 8
 
 
@@ -1731,7 +1732,8 @@ def dropout_residual_layernorm_backward(dy, gamma, saved, dy2=None):
 
 
 def train_eltwise(op, a, b):
-    """ELT_ADD: a + b;  ELT_RELU_BWD: a * (b > 0) (b = the ReLU's output)."""
+    """ELT_ADD: a + b;  ELT_RELU_BWD: a * (b > 0) (b = the ReLU's output);  ELT_LRELU2_BWD: b > 0 ? a : 0.2 a (b = the
+    LeakyReLU(0.2)'s output or input)."""
     _chk(a, "a")
     _chk(b, "b")
     if a.shape != b.shape:
@@ -1741,3 +1743,105 @@ def train_eltwise(op, a, b):
     _launch("mgnns_train_eltwise", ("mgnns_train_eltwise", op), L.mgnns_train_eltwise, int(op), _p(a), _p(b), a.numel(), _p(y),
             _stream())
     return y
+
+
+# ---- training mode of the model around the fusion stacks (csrc/model_train.hip) -----------------------------------------
+def imgbank_wgrad(feat, dbank):
+    """Weight gradient of an image memory bank bank[b,p,:] = W feat[b,:,p] + c (mgnns_imgbank_wgrad): feat [B, K, P] in its
+    native layout, dbank [B, P, N] -> (dW [N, K], db [N]).  Exact-f32 MFMA, samples reduced in a fixed order."""
+    _chk(feat, "feature map", ndim=3)
+    _chk(dbank, "dbank", ndim=3)
+    B, K, P = feat.shape
+    N = dbank.shape[2]
+    if tuple(dbank.shape[:2]) != (B, P):
+        raise ValueError("dbank %s does not match the feature map %s" % (tuple(dbank.shape), tuple(feat.shape)))
+    dW = torch.empty(N, K, device=feat.device, dtype=torch.float32)
+    db = torch.empty(N, device=feat.device, dtype=torch.float32)
+    L = _lib.lib()
+    nbytes = L.mgnns_imgbank_wgrad_workspace_bytes(B, K, P, N)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
+    _launch("mgnns_imgbank_wgrad", ("mgnns_imgbank_wgrad", B, P), L.mgnns_imgbank_wgrad, _p(feat), _p(dbank), B, K, P, N, _p(dW),
+            _p(db), _p(ws), nbytes, _stream())
+    return dW, db
+
+
+def label_attn_train(Q, K, V, n_heads, seed, rate, return_masks=False):
+    """Training forward of the label attention between its projections (mgnns_label_attn_train_fwd, MODEL:101-131): Q [NLQ,hid],
+    K = V's source projections [B, hid] -> (x [B, NLQ, hid] with dropout(rate) on softmax(energy) over each head's dh axis,
+    saved) (+ keep [B, NLQ, hid] bool with return_masks)."""
+    _chk(Q, "Q", ndim=2)
+    _chk(K, "K", ndim=2)
+    _chk(V, "V", ndim=2)
+    NLQ, hid = Q.shape
+    B = K.shape[0]
+    if K.shape[1] != hid or V.shape != K.shape or hid % n_heads:
+        raise ValueError("label attention shapes Q%s K%s V%s" % (tuple(Q.shape), tuple(K.shape), tuple(V.shape)))
+    dh = hid // n_heads
+    if dh > 64:
+        raise ValueError("training label attention supports head widths up to 64, got %d" % dh)
+    rate = _chk_rate(rate)
+    x = torch.empty(B, NLQ, hid, device=K.device, dtype=torch.float32)
+    P = torch.empty_like(x)
+    keep = torch.empty(B, NLQ, hid, device=K.device, dtype=torch.uint8)
+    L = _lib.lib()
+    _launch("mgnns_label_attn_train_fwd", ("mgnns_label_attn_train_fwd",), L.mgnns_label_attn_train_fwd, _p(Q), _p(K), _p(V), B, NLQ,
+            n_heads, dh, _seed64(seed), rate, _p(x), _p(P), _p(keep), _stream())
+    saved = dict(P=P, keep=keep, rate=rate, n_heads=n_heads)
+    if return_masks:
+        return x, saved, keep.bool()
+    return x, saved
+
+
+def label_attn_train_backward(dx, Q, K, V, saved):
+    """Backward of label_attn_train: dx [B, NLQ, hid] -> (dQ [NLQ, hid] summed over the batch in order, dK, dV [B, hid])."""
+    NLQ, hid = Q.shape
+    B = K.shape[0]
+    dx = _chk(dx.reshape(B, NLQ, hid), "dx")
+    H = saved["n_heads"]
+    dQ = torch.empty(NLQ, hid, device=K.device, dtype=torch.float32)
+    dK = torch.empty(B, hid, device=K.device, dtype=torch.float32)
+    dV = torch.empty(B, hid, device=K.device, dtype=torch.float32)
+    L = _lib.lib()
+    nbytes = L.mgnns_label_attn_train_bwd_workspace_bytes(B, NLQ, H, hid // H)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=K.device)
+    _launch("mgnns_label_attn_train_bwd", ("mgnns_label_attn_train_bwd",), L.mgnns_label_attn_train_bwd, _p(dx), _p(Q), _p(K), _p(V),
+            _p(saved["P"]), _p(saved["keep"]), B, NLQ, H, hid // H, saved["rate"], _p(dQ), _p(dK), _p(dV), _p(ws), nbytes, _stream())
+    return dQ, dK, dV
+
+
+def dropout(x, seed, site, rate, return_masks=False):
+    """Training-mode dropout at `site` (mgnns_dropout_fwd) -> (y, keep bytes) (+ keep bool with return_masks)."""
+    _chk(x, "x")
+    rate = _chk_rate(rate)
+    y = torch.empty_like(x)
+    keep = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
+    L = _lib.lib()
+    _launch("mgnns_dropout_fwd", ("mgnns_dropout_fwd",), L.mgnns_dropout_fwd, _p(x), x.numel(), _seed64(seed), int(site), rate, _p(y),
+            _p(keep), _stream())
+    if return_masks:
+        return y, keep, keep.bool()
+    return y, keep
+
+
+def dropout_backward(dy, keep, rate):
+    """dx = dy keep / (1 - rate) (mgnns_dropout_bwd)."""
+    _chk(dy, "dy")
+    _chk(keep, "keep", torch.uint8)
+    if dy.shape != keep.shape:
+        raise ValueError("dropout_backward shapes %s / %s" % (tuple(dy.shape), tuple(keep.shape)))
+    dx = torch.empty_like(dy)
+    L = _lib.lib()
+    _launch("mgnns_dropout_bwd", ("mgnns_dropout_bwd",), L.mgnns_dropout_bwd, _p(dy), _p(keep), dy.numel(), _chk_rate(rate), _p(dx),
+            _stream())
+    return dx
+
+
+def dropout_mask(seed, site, rate, shape, device):
+    """The keep mask (bool, `shape`) the training kernels draw for `seed` at `site` over a tensor of that shape (mgnns_dropout_mask):
+    how tests and tools rebuild a training forward's dropout from the seeds the modules keep (`last_dropout_seed`).  Sites index
+    their tensors flat: DROP_ATTN [H*B, 1, L], DROP_FC / DROP_FFN [B, D], DROP_LABEL_ATTN [B, NLQ, hid], DROP_HEAD [B, D]."""
+    keep = torch.empty(tuple(shape), device=device, dtype=torch.uint8)
+    L = _lib.lib()
+    _launch("mgnns_dropout_mask", ("mgnns_dropout_mask",), L.mgnns_dropout_mask, _seed64(seed), int(site), _chk_rate(rate),
+            keep.numel(), _p(keep), _stream())
+    return keep.bool()

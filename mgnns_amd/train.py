@@ -5,6 +5,12 @@ semantics (submodules.py:15-139): dropout on the attention probabilities (`attn_
 `attention.dropout`), after `fc` and after `w_2` (the layers' own `dropout`), and the custom LayerNorm (unbiased std, eps added
 to the std).  Everything is fp32.  The masks are drawn from a counter-based hash of a seed the module draws from torch's default
 generator per training forward (kept as `last_dropout_seed`), so torch.manual_seed reproduces a run bit for bit.
+
+The rest of the model trains through the Functions below the fusion layers' (csrc/model_train.hip): the image memory banks
+(their weight gradient is the backward's hot path), the label GCN (propagated back with the transposed adjacency), the label
+attention with dropout on its probabilities, the channel tails and the classifier with its dropout.  The CNN trunks and the
+text encoders have no backward here: Multi_GCN_Multihead_Att refuses training mode unless the text encoders are frozen and
+in eval mode, and it takes precomputed feature maps.
 """
 import torch
 
@@ -108,3 +114,142 @@ def ffn_train_forward(ffn, x):
     out = FFNTrainFunction.apply(x2, seed, ffn.dropout.p, ffn.layer_norm.eps, w1, ffn.w_1.bias, w2, ffn.w_2.bias,
                                  ffn.layer_norm.gamma, ffn.layer_norm.beta)
     return out.view(shp)
+
+
+# ---- the model around the fusion stacks (MODEL:431-567) ----------------------------------------------------------------------
+class LinearFunction(torch.autograd.Function):
+    """y = x W^T + b over rows x [M, K] (b may be None); backward dx = dy W, (dW, db) = wgrad(dy, x)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = b is not None
+        return ops.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = ops.matmul(dy, w) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = ops.wgrad(dy, x, bias=ctx.has_bias)
+        return dx, dw, db
+
+
+def linear(x, lin_or_w, b=None):
+    """LinearFunction over the last axis of x: an nn.Linear, or a weight [N, K] and bias."""
+    if isinstance(lin_or_w, torch.nn.Linear):
+        lin_or_w, b = lin_or_w.weight, lin_or_w.bias
+    shp = x.shape
+    y = LinearFunction.apply(x.reshape(-1, shp[-1]).contiguous(), lin_or_w, b)
+    return y.view(*shp[:-1], y.shape[-1])
+
+
+class ImgBankFunction(torch.autograd.Function):
+    """(bank [B, P, N], pooled [B, K]) = the fp32 memory bank and max-pool of a feature map f [B, K, P] (ops.imgbank_pool; wt =
+    the bank kernel's transposed weight).  Only the weight and bias get gradients (ops.imgbank_wgrad, skipped when neither
+    requires one); the map gets none -- the trunks do not train -- and pooled is a constant."""
+
+    @staticmethod
+    def forward(ctx, f, weight, bias, wt):
+        bank, pooled = ops.imgbank_pool(f, wt, bias.detach(), weight.shape[0])
+        ctx.save_for_backward(f)
+        ctx.mark_non_differentiable(pooled)
+        return bank, pooled
+
+    @staticmethod
+    def backward(ctx, dbank, _dpooled):
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            return None, None, None, None
+        f, = ctx.saved_tensors
+        dw, db = ops.imgbank_wgrad(f, dbank.contiguous())
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
+
+
+class GCNFunction(torch.autograd.Function):
+    """y = act(adj (x W)) with adj as CSR (csr) and its transpose (csr_t); backward dh = act'(dy), ds = adj^T dh,
+    dW = x^T ds, dx = ds W^T.  act: ops.ACT_NONE or ops.ACT_LRELU2 (the label GCN's LeakyReLU(0.2), MODEL:462)."""
+
+    @staticmethod
+    def forward(ctx, x, w, csr, csr_t, act):
+        y = ops.spmm_csr(csr, ops.matmul(x, w), act=act)
+        ctx.csr_t, ctx.act = csr_t, act
+        ctx.save_for_backward(x, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        dh = dy.contiguous()
+        if ctx.act == ops.ACT_LRELU2:
+            dh = ops.train_eltwise(ops.ELT_LRELU2_BWD, dh, y)
+        elif ctx.act != ops.ACT_NONE:
+            raise NotImplementedError("GCNFunction: no backward for activation %d" % ctx.act)
+        ds = ops.spmm_csr(ctx.csr_t, dh)
+        dw = ops.wgrad(x, ds, bias=False)[0] if ctx.needs_input_grad[1] else None
+        dx = ops.linear(ds, w) if ctx.needs_input_grad[0] else None
+        return dx, dw, None, None, None
+
+
+class LabelAttentionFunction(torch.autograd.Function):
+    """Attention.forward (MODEL:88-133) in training mode: out [B, NLQ, hid] = fc(dropout(softmax_dh(w_q(lq) w_k(x) / sqrt(dh)))
+    w_v(x)); lq [NLQ, hid] is a constant, x [B, C] gets a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, lq, seed, rate, n_heads, wq, bq, wk, bk, wv, bv, wfc, bfc):
+        Q = ops.linear(lq, wq, bq)
+        K = ops.linear(x, wk, bk)
+        V = ops.linear(x, wv, bv)
+        y, saved = ops.label_attn_train(Q, K, V, n_heads, seed, rate)
+        B, NLQ, hid = y.shape
+        y2 = y.view(B * NLQ, hid)
+        ctx.la = saved
+        ctx.save_for_backward(x, lq, wk, wv, wfc, Q, K, V, y2)
+        return ops.linear(y2, wfc, bfc).view(B, NLQ, -1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, lq, wk, wv, wfc, Q, K, V, y2 = ctx.saved_tensors
+        d2 = dout.reshape(y2.shape[0], -1).contiguous()
+        dwfc, dbfc = ops.wgrad(d2, y2)
+        dQ, dK, dV = ops.label_attn_train_backward(ops.matmul(d2, wfc), Q, K, V, ctx.la)
+        dwq, dbq = ops.wgrad(dQ, lq)
+        dwk, dbk = ops.wgrad(dK, x)
+        dwv, dbv = ops.wgrad(dV, x)
+        dx = ops.train_eltwise(ops.ELT_ADD, ops.matmul(dK, wk), ops.matmul(dV, wv)) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, None, dwq, dbq, dwk, dbk, dwv, dbv, dwfc, dbfc
+
+
+class DropoutFunction(torch.autograd.Function):
+    """Training-mode dropout of x at `site` (ops.dropout); the backward applies the same mask."""
+
+    @staticmethod
+    def forward(ctx, x, seed, site, rate):
+        y, keep = ops.dropout(x, seed, site, rate)
+        ctx.keep, ctx.rate = keep, rate
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.dropout_backward(dy.contiguous(), ctx.keep, ctx.rate), None, None, None
+
+
+def label_attention_train_forward(att, query, key, mask=None):
+    """model.Attention.forward in training mode: query [NLQ, hid] (the label GloVe: no gradient), key = value [B, C]."""
+    if mask is not None:
+        raise NotImplementedError("training mode of the label Attention takes no mask (no reference call site passes one)")
+    if not key.is_cuda:
+        raise RuntimeError("key is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % key.device)
+    seed = draw_seed()
+    att.last_dropout_seed = seed
+    return LabelAttentionFunction.apply(key.contiguous(), query.detach().float().contiguous(), seed, att.do.p, att.n_heads,
+                                        att.w_q.weight, att.w_q.bias, att.w_k.weight, att.w_k.bias, att.w_v.weight, att.w_v.bias,
+                                        att.fc.weight, att.fc.bias)
+
+
+def dropout_train_forward(mod, x, site):
+    """An nn.Dropout `mod` in training mode at `site`; one seed per call, kept as mod.last_dropout_seed."""
+    seed = draw_seed()
+    mod.last_dropout_seed = seed
+    return DropoutFunction.apply(x.contiguous(), seed, site, mod.p)

@@ -2,7 +2,10 @@
 """Training mode of one MyMultiHeadAttention layer (csrc/mha_train.hip) at B=256, H=4: L=196 unmasked and L=100 masked (ragged
 lengths).  HIP events around n calls: the layer's training forward + backward, each new entry point with its algorithmic bytes
 and achieved GB/s, and for context the same layer through plain torch autograd (fp32, on the GPU).  One JSON line per case.
-Usage: python tools/bench_train.py [--iters N]"""
+The last line is the whole model (csrc/model_train.hip) at mvsa_multiple_b256 in fp32: the training forward + backward step,
+the image-bank weight-gradient kernel alone with its % of the 155 TF fp32 matrix peak, and plain torch autograd over the same
+formulation.
+Usage: python tools/bench_train.py [--iters N] [--model-only]"""
 import json
 import math
 import os
@@ -121,12 +124,106 @@ def case(B, H, L, masked, n):
     return res
 
 
+FP32_PEAK = 155e12        # measured exact-f32 MFMA peak of the MI355X
+
+
+def torch_model(model, tf, tbank, tmask, maps, inps, lq):
+    """The reference's training forward (MODEL:88-133, 431-567) in plain fp32 torch over the model's own parameters: the same
+    formulation the HIP chain computes (text feature and text bank as constants, every dropout site)."""
+    from oracle import restatement as R
+    B = tf.shape[0]
+    feat, bank = {}, {}
+    for tag, chan in (("obj", "object"), ("place", "place")):
+        lin, att = getattr(model, "liner_img_" + chan), getattr(model, chan + "_attention")
+        f = maps[tag]
+        bank[tag] = F.linear(f.reshape(B, f.shape[1], -1).transpose(1, 2), lin.weight, lin.bias)
+        adj = R.gen_adj(getattr(model, chan + "_A").detach())
+        G = adj @ (F.leaky_relu(adj @ (inps[tag][0] @ model.gc1.weight), 0.2) @ model.gc2.weight)
+        x = f.reshape(B, f.shape[1], -1).amax(dim=2) @ G.t()
+        nh = att.n_heads
+        dh = 300 // nh
+        Q, K, V = att.w_q(lq).view(1, -1, nh, dh), att.w_k(x).view(B, 1, nh, dh), att.w_v(x).view(B, 1, nh, dh)
+        y = att.fc((F.dropout(torch.softmax(Q * K / math.sqrt(dh), dim=-1), att.do.p) * V).reshape(B, -1, 300))
+        feat[tag] = getattr(model, chan + "_x_linear")(getattr(model, chan + "_linear_5")(y).reshape(B, -1))
+
+    def ln(x, g, b):
+        return g * (x - x.mean(-1, keepdim=True)) / (x.std(-1, keepdim=True) + 1e-6) + b
+
+    def layer(m, q, kv, mask):
+        a, f = m.slf_attn, m.pos_ffn
+        H, dk, L = a.n_head, a.d_k, kv.shape[1]
+        qh = a.w_qs(q).view(B, H, dk)
+        kh, vh = a.w_ks(kv).view(B, L, H, dk), a.w_vs(kv).view(B, L, H, dk)
+        s_ = torch.einsum("bhd,blhd->bhl", qh, kh) / math.sqrt(dk)
+        if mask is not None:
+            s_ = s_.masked_fill(mask[:, None, :] == 0, float("-inf"))
+        o = torch.einsum("bhl,blhd->bhd", F.dropout(torch.softmax(s_, dim=2), a.attn_dropout.p), vh).reshape(B, -1)
+        y = ln(F.dropout(a.fc(o), a.dropout.p) + q, a.layer_norm.gamma, a.layer_norm.beta)
+        z = F.linear(F.relu(F.linear(y, f.w_1.weight.squeeze(-1), f.w_1.bias)), f.w_2.weight.squeeze(-1), f.w_2.bias)
+        return ln(F.dropout(z, f.dropout.p) + y, f.layer_norm.gamma, f.layer_norm.beta)
+
+    def stack(layers, q, kv, mask):
+        for m in layers:
+            q = layer(m, q, kv, mask)
+        return q
+
+    multi = torch.cat([stack(model.text_img_object_multi_head_att, tf, bank["obj"], None),
+                       stack(model.text_img_place_multi_head_att, tf, bank["place"], None),
+                       stack(model.img_object_text_multi_head_att, feat["obj"], tbank, tmask),
+                       stack(model.img_place_text_multi_head_att, feat["place"], tbank, tmask)], dim=1)
+    return model.multi_linear_2(F.dropout(model.multi_linear_1(multi), model.dropout.p))
+
+
+def model_case(n):
+    from mgnns_amd import harness, synth
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=cfg.B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV).train().freeze_text_encoders()
+    args = harness.call_args(inp, DEV)
+    B = args[0].shape[0]
+    G = torch.randn(B, cfg.NL, device=DEV)
+    res = {"case": "model_%s_fp32" % cfg.name, "B": B}
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        torch.autograd.backward(model(*args), G)
+
+    res["model_fwd_us"] = timeit(lambda: model(*args), n)
+    res["model_fwd_bwd_us"] = timeit(step, n)
+    f3 = args[3].float().contiguous().view(B, args[3].shape[1], -1)
+    K, P, N = f3.shape[1], f3.shape[2], model.liner_img_object.out_features
+    dbank = torch.randn(B, P, N, device=DEV)
+    t = timeit(lambda: ops.imgbank_wgrad(f3, dbank), n)
+    flop = 2.0 * B * P * K * N
+    res["bank_wgrad"] = {"us": round(t, 1), "GFLOP": round(flop / 1e9, 1), "TF/s": round(flop / t / 1e6, 1),
+                         "pct_fp32_peak": round(100.0 * flop / t / 1e6 / (FP32_PEAK / 1e12), 1)}
+    with torch.no_grad():
+        tf = model.text_features(args[0])
+        tbank = model._text_bank(args[0], args[1]).f32
+    maps = {"obj": args[3].float(), "place": args[4].float()}
+    inps = {"obj": args[5].float(), "place": args[6].float()}
+    lq = model.label_query.float()
+
+    def torch_step():
+        model.zero_grad(set_to_none=True)
+        torch.autograd.backward(torch_model(model, tf, tbank, args[2].float(), maps, inps, lq), G)
+
+    res["torch_fwd_bwd_us"] = timeit(torch_step, n)
+    for k in ("model_fwd_us", "model_fwd_bwd_us", "torch_fwd_bwd_us"):
+        res[k] = round(res[k], 1)
+    return res
+
+
 def main():
     n = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 20
     if not torch.cuda.is_available():
         raise SystemExit("bench_train: no GPU")
-    for B, H, L, masked in ((256, 4, 196, False), (256, 4, 100, True)):
-        print(json.dumps(case(B, H, L, masked, n)), flush=True)
+    if "--model-only" not in sys.argv:
+        for B, H, L, masked in ((256, 4, 196, False), (256, 4, 100, True)):
+            print(json.dumps(case(B, H, L, masked, n)), flush=True)
+    print(json.dumps(model_case(n)), flush=True)
 
 
 if __name__ == "__main__":
