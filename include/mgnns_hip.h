@@ -537,6 +537,8 @@ int mgnns_layernorm_fwd(const float* x, int rows, int D, const float* gamma, con
  * [B, L] (0 = masked) or NULL.  Outputs (all [H][B][...]): U [H,B,D] = W_k,h^T qh_h; P [H,B,L] softmax before dropout;
  * attn [H*B, L] after dropout (the reference's returned attn); keep [H,B,L] bytes or NULL; Z [H,B,D] = X^T p'; SP [H,B] =
  * sum_l p'; o [B, H*dk] = W_v,h z_h + b_v,h SP.  D <= 320, D % 4 == 0, H <= 8, dk % 4 == 0, L <= 208, 0 <= rate <= 1.
+ * A sample without a live position (a padded row) is an empty contribution: P = attn = Z = SP = 0 and o = 0, and the backward
+ * gives it exact zeros (the reference's softmax gives NaN there).
  * mgnns_mha_train_bwd: its backward from dO [B, H*dk] and the forward's saved tensors (keep required): dqh [B, H*dk],
  * dWk / dWv [H*dk, D], dbv [H*dk] (written, not accumulated), dbank [B, L, D] or NULL (masked rows: 0).  b_k has no gradient
  * (it drops out of the softmax).  workspace: mgnns_mha_train_bwd_workspace_bytes(B, D, H, dk) bytes, 16-byte aligned.
@@ -550,7 +552,8 @@ int mgnns_mha_train_bwd(const float* dO, const float* qh, const float* bank, con
                         const float* attn, const uint8_t* keep, const float* Z, const float* SP, float* dqh, float* dWk,
                         float* dWv, float* dbv, float* dbank, void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
 /* Weight gradient of a linear layer: dW[N,K] = dY[M,N]^T X[M,K], db[N] = column sums of dY (db NULL: none).  Row slabs + an
- * ordered combine, no atomics.  workspace: mgnns_wgrad_workspace_bytes(M, N, K) bytes. */
+ * ordered combine, no atomics.  workspace: mgnns_wgrad_workspace_bytes(M, N, K) bytes.  M = 0: dW and db are zeroed, dY and X
+ * may be NULL. */
 size_t mgnns_wgrad_workspace_bytes(int M, int N, int K);
 int mgnns_wgrad_fwd(const float* dY, int M, int N, const float* X, int K, float* dW, float* db, void* workspace,
                     size_t workspace_bytes, mgnns_stream_t stream);
@@ -578,12 +581,13 @@ int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float
  * mgnns_imgbank_wgrad: weight gradient of an image memory bank bank[b,p,:] = W X[b,:,p] + c from dbank [B, P, N] and the feature
  * map X [B, K, P] in its native layout: dW[N, K] = sum_{b,p} dbank[b,p,:] (x) X[b,:,p], db[N] (written).  N <= 320.  Exact-f32
  * MFMA, the (b, p) reduction split into slabs combined in a fixed order.  workspace:
- * mgnns_imgbank_wgrad_workspace_bytes(B, K, P, N) bytes.
+ * mgnns_imgbank_wgrad_workspace_bytes(B, K, P, N) bytes.  B = 0: dW and db are zeroed, X and dbank may be NULL.
  * mgnns_label_attn_train_fwd: the label attention between its projections with dropout: Q [NLQ, H*dh], K = w_k(x), V = w_v(x)
  * [B, H*dh] -> x [B, NLQ, H*dh] = dropout(softmax_dh(Q K / sqrt(dh))) V, and for the backward P (softmax before dropout) and
  * keep (bytes), both [B, NLQ, H*dh].  dh <= 64.
  * mgnns_label_attn_train_bwd: its backward from dx: dQ [NLQ, H*dh] (summed over the batch in order), dK, dV [B, H*dh].
- * workspace: mgnns_label_attn_train_bwd_workspace_bytes(B, NLQ, H, dh) bytes.
+ * workspace: mgnns_label_attn_train_bwd_workspace_bytes(B, NLQ, H, dh) bytes.  B = 0: dQ is zeroed, and the per-sample
+ * tensors (K, V, x, P, keep, dx, dK, dV) may be NULL.
  * mgnns_dropout_fwd / _bwd: y = dropout(x) at `site` (keep written as bytes); dx = dy keep / (1 - rate).
  * mgnns_dropout_mask: the keep mask of elements 0..n-1 of a site as bytes (what the training kernels draw for that seed).
  */

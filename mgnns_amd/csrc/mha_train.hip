@@ -119,7 +119,9 @@ __global__ __launch_bounds__(NT) void train_attn_fwd_kernel(const float* __restr
             f[w] = (mz[0][w][h] == -INFINITY) ? 0.f : __expf(mz[0][w][h] - M);
             Zs += mz[1][w][h] * f[w];
         }
-        const float iz = 1.0f / Zs;                          // every row masked: 0 * inf = NaN, as the reference's softmax
+        // every row masked (a padded sample): P = A = Z = SP = 0, so o = 0 and the backward gives exact zeros.  The reference's
+        // softmax would give NaN there, and 0 * NaN in the backward would reach every weight gradient of the step.
+        const float iz = Zs > 0.f ? 1.0f / Zs : 0.f;
         for (int w = 0; w < WAVES; ++w) fac[w][h] = f[w] * iz * ks;
         stat[0][h] = M;
         stat[1][h] = iz;
@@ -604,7 +606,7 @@ extern "C" size_t mgnns_wgrad_workspace_bytes(int M, int N, int K) { return size
 
 extern "C" int mgnns_wgrad_fwd(const float* dY, int M, int N, const float* X, int K, float* dW, float* db, void* workspace,
                                size_t workspace_bytes, mgnns_stream_t stream) {
-    MG_REQUIRE(dY && X && dW && workspace, "mgnns_wgrad_fwd: null pointer");
+    MG_REQUIRE(dW && workspace && (M == 0 || (dY && X)), "mgnns_wgrad_fwd: null pointer");      // M = 0: dY, X may be empty
     MG_REQUIRE(M >= 0 && N > 0 && K > 0, "mgnns_wgrad_fwd: bad dims M=%d N=%d K=%d", M, N, K);
     MG_REQUIRE(workspace_bytes >= mgnns_wgrad_workspace_bytes(M, N, K), "mgnns_wgrad_fwd: workspace too small");
     hipStream_t s = (hipStream_t)stream;

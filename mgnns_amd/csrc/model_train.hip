@@ -272,7 +272,7 @@ extern "C" size_t mgnns_imgbank_wgrad_workspace_bytes(int B, int K, int P, int N
 
 extern "C" int mgnns_imgbank_wgrad(const float* X, const float* dbank, int B, int K, int P, int N, float* dW, float* db,
                                    void* workspace, size_t workspace_bytes, mgnns_stream_t stream) {
-    MG_REQUIRE(X && dbank && dW && db && workspace, "mgnns_imgbank_wgrad: null pointer");
+    MG_REQUIRE(dW && db && workspace && (B == 0 || (X && dbank)), "mgnns_imgbank_wgrad: null pointer");   // B = 0: empty maps
     MG_REQUIRE(B >= 0 && K > 0 && P > 0 && N > 0 && N <= BW_O, "mgnns_imgbank_wgrad: need B >= 0, K, P > 0, 0 < N <= %d "
                "(B=%d K=%d P=%d N=%d)", BW_O, B, K, P, N);
     MG_REQUIRE((long)B * K * P < (1L << 40), "mgnns_imgbank_wgrad: feature map too large");
@@ -305,7 +305,7 @@ extern "C" int mgnns_imgbank_wgrad(const float* X, const float* dbank, int B, in
 
 extern "C" int mgnns_label_attn_train_fwd(const float* Q, const float* K, const float* V, int B, int NLQ, int H, int dh,
                                           uint64_t seed, float rate, float* x, float* P, uint8_t* keep, mgnns_stream_t stream) {
-    MG_REQUIRE(Q && K && V && x && P && keep, "mgnns_label_attn_train_fwd: null pointer");
+    MG_REQUIRE(Q && (B == 0 || (K && V && x && P && keep)), "mgnns_label_attn_train_fwd: null pointer");   // B = 0: empty
     const char* bad = label_attn_shape_error(B, NLQ, H, dh);
     MG_REQUIRE(!bad, "mgnns_label_attn_train_fwd: %s (B=%d NLQ=%d H=%d dh=%d)", bad ? bad : "", B, NLQ, H, dh);
     MG_REQUIRE(rate >= 0.f && rate <= 1.f, "mgnns_label_attn_train_fwd: dropout rate %g outside [0, 1]", (double)rate);
@@ -324,7 +324,8 @@ extern "C" size_t mgnns_label_attn_train_bwd_workspace_bytes(int B, int NLQ, int
 extern "C" int mgnns_label_attn_train_bwd(const float* dx, const float* Q, const float* K, const float* V, const float* P,
                                           const uint8_t* keep, int B, int NLQ, int H, int dh, float rate, float* dQ, float* dK,
                                           float* dV, void* workspace, size_t workspace_bytes, mgnns_stream_t stream) {
-    MG_REQUIRE(dx && Q && K && V && P && keep && dQ && dK && dV && workspace, "mgnns_label_attn_train_bwd: null pointer");
+    MG_REQUIRE(Q && dQ && workspace && (B == 0 || (dx && K && V && P && keep && dK && dV)),
+               "mgnns_label_attn_train_bwd: null pointer");                                      // B = 0: per-sample tensors empty
     const char* bad = label_attn_shape_error(B, NLQ, H, dh);
     MG_REQUIRE(!bad, "mgnns_label_attn_train_bwd: %s (B=%d NLQ=%d H=%d dh=%d)", bad ? bad : "", B, NLQ, H, dh);
     MG_REQUIRE(rate >= 0.f && rate <= 1.f, "mgnns_label_attn_train_bwd: dropout rate %g outside [0, 1]", (double)rate);

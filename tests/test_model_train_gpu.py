@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from mgnns_amd import harness, ops, synth
 from mgnns_amd.model import Attention, GraphConvolution
 from oracle import restatement as R
+from tests import dropout_ref as DR
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -108,6 +109,31 @@ def collect_masks(model, B, T, P):
     return out
 
 
+def collect_host_masks(model, B, T, P):
+    """collect_masks from the host restatement of the hash alone (tests/dropout_ref.py), at each site's documented layout;
+    also -> the seed of every module that drops."""
+    t = torch.from_numpy
+    out, seeds = {}, []
+    for st in STACKS:
+        L = T if st.startswith("img_") else P
+        for i, layer in enumerate(getattr(model, st)):
+            sa, ff = layer.slf_attn, layer.pos_ffn
+            seeds += [sa.last_dropout_seed, ff.last_dropout_seed]
+            out["%s.%d" % (st, i)] = (
+                (t(DR.attn_keep(sa.last_dropout_seed, sa.attn_dropout.p, model.n_head, B, L)),
+                 t(DR.rows_keep(sa.last_dropout_seed, DR.DROP_FC, sa.dropout.p, B, D)),
+                 t(DR.rows_keep(ff.last_dropout_seed, DR.DROP_FFN, ff.dropout.p, B, D))),
+                (sa.attn_dropout.p, sa.dropout.p, ff.dropout.p))
+    for chan in ("object", "place"):
+        att = getattr(model, chan + "_attention")
+        seeds.append(att.last_dropout_seed)
+        out[chan + "_attention"] = (t(DR.label_keep(att.last_dropout_seed, att.do.p, B, model.label_query.shape[0], D)), att.do.p)
+    seeds.append(model.last_dropout_seed)
+    out["head"] = (t(DR.rows_keep(model.last_dropout_seed, DR.DROP_HEAD, model.dropout.p, B, model.bi_hidden_size)),
+                   model.dropout.p)
+    return out, seeds
+
+
 def model_ref(p, model, consts, inp, masks):
     """fp64 training forward (MODEL:431-567) over the parameter dict p; consts: text feature, text bank, mask (constants)."""
     tf, tbank, tmask = consts
@@ -164,8 +190,8 @@ def train_step(model, args):
     return logits.detach()
 
 
-@pytest.mark.parametrize("rates", [0, "reference"])
-@pytest.mark.parametrize("cfg_name", ["mvsa_single_b8", "tumemo_b64"])
+@pytest.mark.parametrize("cfg_name,rates", [(c, r) for c in ("mvsa_single_b8", "tumemo_b64") for r in (0, "reference")]
+                         + [("mvsa_multiple_b256", "reference")])          # (the configuration tools/bench_train.py times)
 def test_whole_model_gradients_match_fp64(cfg_name, rates):
     cfg, model, inp = make(cfg_name, rates)
     args = harness.call_args(inp, DEV)
@@ -183,6 +209,84 @@ def test_whole_model_gradients_match_fp64(cfg_name, rates):
     for k, v in model.named_parameters():
         if v.grad is not None:
             close(v.grad, p[k].grad, k)
+
+
+def test_whole_model_matches_fp64_under_host_restated_masks():
+    """Every module's mask rebuilt from its last_dropout_seed by the host restatement alone: a kernel drawing at a wrong index
+    would still agree with ops.dropout_mask (same hash, same mistake) but not with this."""
+    cfg, model, inp = make("tumemo_b64")
+    args = harness.call_args(inp, DEV)
+    logits = train_step(model, args)
+    B, T = args[0].shape
+    masks, seeds = collect_host_masks(model, B, T, args[3].shape[2] * args[3].shape[3])
+    assert len(seeds) == len(set(seeds)) == 4 * 2 * model.stack_num + 3, "two dropping modules drew the same seed"
+    p = ref_params(model)
+    ref = model_ref(p, model, constants(model, args), inp, masks)
+    ref.sum().backward()
+    close(logits, ref.detach(), "logits")
+    for k, v in model.named_parameters():
+        if v.grad is not None:
+            close(v.grad, p[k].grad, k)
+
+
+def padded_batch(rates, B=16, live=11):
+    """tumemo_b64 with trailing empty samples, padded as the host pipeline pads a partial batch (batching.BatchAssembler: ids
+    0, length 0, mask 0) -- the padding of test_model_gpu.py::test_padded_partial_batch_with_trailing_empty_samples."""
+    cfg, model, inp = make("tumemo_b64", rates, B=B, seed=31)
+    inp["text"][live:] = 0
+    inp["text_lens"][live:] = 0
+    inp["text_mask"][live:] = 0
+    sub = {k: (v[:live] if k != "label_query" else v) for k, v in inp.items()}
+    return model, harness.call_args(inp, DEV), harness.call_args(sub, DEV)
+
+
+def live_grads(model, args, live):
+    model.zero_grad(set_to_none=True)
+    logits = model(*args)
+    logits[:live].sum().backward()
+    return logits.detach(), {k: v.grad.clone() for k, v in model.named_parameters() if v.grad is not None}
+
+
+def test_trailing_empty_samples_do_not_poison_the_gradients():
+    live = 11
+    model, args, sub = padded_batch(0)
+    logits, g = live_grads(model, args, live)
+    ref_logits, ref = live_grads(model, sub, live)
+    assert g.keys() == ref.keys() and g
+    bad = [k for k, v in g.items() if not torch.isfinite(v).all()]
+    assert not bad, "non-finite gradients with padded samples: %s" % bad[:8]
+    close(logits[:live], ref_logits, "live logits")
+    for k in ref:
+        close(g[k], ref[k], k)
+
+
+def test_trailing_empty_samples_at_reference_rates_then_adam_stay_finite():
+    live = 11
+    model, args, _ = padded_batch("reference")
+    opt = torch.optim.Adam(model.get_config_optim(1e-3, 0.1), lr=1e-3)
+    logits, g = live_grads(model, args, live)
+    assert torch.isfinite(logits[:live]).all()
+    bad = [k for k, v in g.items() if not torch.isfinite(v).all()]
+    assert not bad, "non-finite gradients with padded samples: %s" % bad[:8]
+    opt.step()
+    bad = [k for k, v in model.named_parameters() if not torch.isfinite(v).all()]
+    assert not bad, "non-finite weights after an Adam step: %s" % bad[:8]
+
+
+@pytest.mark.parametrize("cfg_name,B", [("mvsa_single_b8", None), ("tumemo_b64", None), ("tumemo_b64", 1),
+                                        ("mvsa_multiple_b256", None)])
+def test_training_forward_at_rate_0_equals_the_eval_forward(cfg_name, B):
+    """Two independent implementations of one function: the training chain at rate 0 and the fp32 eval forward (default
+    attention form)."""
+    cfg, model, inp = make(cfg_name, 0, B=B)
+    args = harness.call_args(inp, DEV)
+    train_logits = model(*args).detach()
+    model.eval()
+    assert model.precision == "fp32"
+    with torch.no_grad():
+        eval_logits = model(*args)
+    assert torch.isfinite(train_logits).all()
+    close(train_logits, eval_logits, "training logits at rate 0 vs eval")
 
 
 def test_dropout_masks_and_seeds_reproduce_bit_for_bit():
