@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 20
+#define MGNNS_ABI_VERSION 21
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -118,17 +118,13 @@ int mgnns_bilstm_fwd(const int64_t* tok, const int64_t* lens, int B, int T,
                      mgnns_stream_t stream);
 /* Same contract, bf16-mode recurrence: the per-step W_hh . h on v_mfma_f32_4x4x4_16b_bf16 (W_hh and h rounded to bf16 for
  * the product; fp32 accumulation, gates and cell state; fast exp / rcp): ~2e-3 absolute on the bank, 2.5x shorter chain.  The
- * input projections stay on the exact-f32 GEMM.
- * plan_mask / plan (both or neither; round 5): the batch's text mask [B, T] float and mgnns_sq_mha32_plan_ints(B) int32 -- the
- * packing plan of that mask (exactly what mgnns_sq_mha32_plan(plan_mask, B, T, plan) writes) is built by one extra workgroup of
- * this call's first launch, for the two image->text stacks that consume the text bank (Multi_GCN_Multihead_att.py:509-527).
- * Needs B <= 1024, T <= 128, emb_dim % 4 == 0. */
+ * input projections stay on the exact-f32 GEMM. */
 int mgnns_bilstm_bf16_fwd(const int64_t* tok, const int64_t* lens, int B, int T,
                      const float* emb_table, int V, int emb_dim, int hidden, int num_layers,
                      const float* const* w_ih_cat, const float* const* b_ih_cat,
                      const float* const* w_hh, const float* const* b_hh,
                      void* workspace, size_t workspace_bytes, float* out, void* out_bf16, int ld_bf16, const void* prepacked,
-                     const float* plan_mask, int32_t* plan, mgnns_stream_t stream);
+                     mgnns_stream_t stream);
 /* Weights of the bf16 recurrence / projections in their kernel layouts (depends on the weights only: build once per weight
  * version, pass as `prepacked`; NULL = packed on the fly inside every call). */
 size_t mgnns_bilstm_bf16_prepack_bytes(int hidden, int num_layers);
@@ -151,7 +147,7 @@ int mgnns_bilstm_bf16_table_fwd(const int64_t* tok, const int64_t* lens, int B, 
                      const float* const* w_ih_cat, const float* const* b_ih_cat,
                      const float* const* w_hh, const float* const* b_hh,
                      void* workspace, size_t workspace_bytes, float* out, void* out_bf16, int ld_bf16, const void* prepacked,
-                     const float* gx_table, const float* plan_mask, int32_t* plan, mgnns_stream_t stream);
+                     const float* gx_table, mgnns_stream_t stream);
 
 /* ---- a3: adjacency normalisation ----------------------------------------------------------
  * gen_adj (utils/util.py:421-426): d = rowsum(A)^-1/2; adj[i,j] = (A[j,i]*d[i])*d[j].
@@ -667,21 +663,6 @@ int mgnns_maxpool3x3s2_nhwc_fwd(const void* x, int B, int H, int W, int C, void*
 int mgnns_conv_bf16_nhwc_fwd(const void* x, int B, int H, int W, int Cin, const void* wt, const float* bias, int Cout,
                              int KH, int KW, int stride, int pad, const void* residual, int relu, int out_nchw_f32,
                              void* y, mgnns_stream_t stream);
-
-/* ---- a8 (fused layer, bf16 mode): attention core + the rest of the layer in ONE launch ------------------------------
- * mgnns_sq_mha_core_bf16_fwd followed by mgnns_mha_tail_bf16_fwd(terms = 1) for every 16-sample tile, the tail run by the
- * tile's LAST attention-core workgroup to finish (system-scope write-through stores of o, one relaxed agent-scope atomic per
- * workgroup on tile_counters[tile], no fences, nobody spins).  Results are bit-identical to the two separate launches.
- * o_scratch [B, H*dk] fp32 (the cores' output, not needed afterwards); q_in [B, d_model] the layer input (residual);
- * packed[8] as in mgnns_mha_tail_bf16_fwd; tile_counters: ceil(B/16) int32, ZERO before the first launch (the kernel
- * leaves them zero), one array per concurrently running launch.
- */
-int mgnns_sq_mha_layer_bf16_fwd(const float* qh, const void* bank_bf16, const float* mask, int B, int L, int ld, int H, int dk,
-                                const void* Wp, const float* bk, const float* bv, float* o_scratch, const float* q_in,
-                                int d_model, const void* const* packed, const float* fc_b, const float* ln1_gamma,
-                                const float* ln1_beta, const float* b1, const float* b2, const float* ln2_gamma,
-                                const float* ln2_beta, float eps, float* out, const float* bq_next, int HK_next,
-                                float* qh_next, int* tile_counters, mgnns_stream_t stream);
 
 /* ---- measurement aid: a one-thread kernel that writes the GPU's constant-rate real-time counter (s_memrealtime,
  * 100 MHz) into slots[idx] when the stream reaches it.  Captured into the forward's hipGraph it gives the REAL

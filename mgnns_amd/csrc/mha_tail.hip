@@ -288,7 +288,7 @@ __global__ __launch_bounds__(NTHR) void mha_tail_bf16_kernel(const float* __rest
                                                              TailW w, float eps, float* __restrict__ out, int HKn,
                                                              float* __restrict__ qh_next) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
-    mg_tail::tail_bf16_body<TERMS, false>(smem_b, o, HK, q, B, w, eps, out, HKn, qh_next, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
+    mg_tail::tail_bf16_body<TERMS>(smem_b, o, HK, q, B, w, eps, out, HKn, qh_next, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
 }
 
 // the same with the K of `fc` split over the cluster (round 4; as mha_tail_c16_kernel): ranks of a tile are ADJACENT workgroups,
@@ -299,8 +299,8 @@ __global__ __launch_bounds__(NTHR) void mha_tail_bf16_ks_kernel(const float* __r
                                                                 TailW w, float eps, float* __restrict__ out, int cl,
                                                                 float* __restrict__ xpart, int* __restrict__ xcnt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
-    mg_tail::tail_bf16_body<TERMS, false>(smem_b, o, HK, q, B, w, eps, out, 0, nullptr, (int)blockIdx.x / cl, (int)blockIdx.x % cl, cl,
-                                          xpart, xcnt);
+    mg_tail::tail_bf16_body<TERMS>(smem_b, o, HK, q, B, w, eps, out, 0, nullptr, (int)blockIdx.x / cl, (int)blockIdx.x % cl, cl,
+                                   xpart, xcnt);
 }
 
 // the same tail behind the folded attention (sq_mha_folded_bf16.hip): `c` = bf16 [B, HC] weighted bank rows per head, `fc` = the
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(NTHR) void mha_tail_c16_kernel(const unsigned short
                                                             float* __restrict__ u_next, int cl, float* __restrict__ xpart,
                                                             int* __restrict__ xcnt) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
-    mg_tail::tail_bf16_body<1, false, true>(smem_b, reinterpret_cast<const float*>(c), HC, q, B, w, eps, out, HCn, u_next,
+    mg_tail::tail_bf16_body<1, true>(smem_b, reinterpret_cast<const float*>(c), HC, q, B, w, eps, out, HCn, u_next,
                                             (int)blockIdx.x / cl, (int)blockIdx.x % cl, cl, xpart, xcnt);
 }
 
@@ -431,7 +431,7 @@ extern "C" int mgnns_mha_tail_bf16_fwd(const float* o, int HK, const float* q, i
     MG_DYN_LDS(mha_tail_bf16_kernel<1>, 160 * 1024);
     MG_DYN_LDS(mha_tail_bf16_kernel<3>, 160 * 1024);
     // with a next-layer projection: a cluster of workgroups per 16-sample tile, each recomputing the front part and taking a
-    // share of the projection (MGNNS_TAIL_CLUSTER overrides: 1 = none).  Four while the chip has CUs to spare; TWO from 256
+    // share of the projection.  Four while the chip has CUs to spare; TWO from 256
     // samples on, where the forward is bound by CU time and 64 workgroups x 21 us cost more than the shorter chain returns
     // (B=256: 0.811-0.820 ms per forward with 2, 0.830 with 4; B=128: equal; B=64: 0.453-0.458 with 4, 0.464-0.467 with 2)
     // terms == 3 (round 5): the same K split on split-bf16 operands; it has no projection launch of its own -- the caller leaves the
@@ -464,7 +464,6 @@ extern "C" int mgnns_mha_tail_bf16_fwd(const float* o, int HK, const float* q, i
         return 0;
     }
     int cl = packed[6] ? (B >= 256 ? 2 : 4) : 1;
-    if (const int e = mg_env_int("MGNNS_TAIL_CLUSTER", 0, 1)) cl = packed[6] ? e : 1;
     if (cluster) cl = packed[6] ? cluster : 1;
     if (cl < 1) cl = 1;
     if (cl > 8) cl = 8;
@@ -513,9 +512,6 @@ extern "C" int mgnns_mha_tail_c16_fwd(const void* c_bf16, int HC, const float* q
     // (or, without a next map and cluster == 0, one workgroup per tile).
     // (measured at B = 256, two forwards in flight: 442 k samples/s with four ranks, 435 k with two; one at a time 0.624 / 0.643 ms)
     int cl = cluster ? cluster : (cluster_scratch ? 4 : (packed[6] ? (B >= 256 ? 2 : 4) : 1));
-    if (!cluster) {
-        if (const int e = mg_env_int("MGNNS_TAIL_CLUSTER", 0, 1)) cl = e;
-    }
     if (cl < 1) cl = 1;
     if (cl > 8) cl = 8;
     if (!packed[6] && !cluster_scratch) cl = 1;            // nothing to share

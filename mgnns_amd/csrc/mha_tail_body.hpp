@@ -1,6 +1,5 @@
 // The bf16 / split-bf16 fused layer tail (fc + residual + LN + FFN + residual + LN + next layer's w_qs, submodules.py:88-94 and
-// 132-139) as a DEVICE FUNCTION over one 16-sample tile, shared by the stand-alone kernel (mha_tail.hip) and the fused
-// layer kernel (sq_mha_bf16.hip: the last attention-core workgroup of a tile to finish runs the tile's tail).
+// 132-139) as a DEVICE FUNCTION over one 16-sample tile, shared by the tail kernels of mha_tail.hip.
 #pragma once
 #include "common.hpp"
 #include "tile_bf16.hpp"
@@ -106,12 +105,10 @@ struct TailW {            // packed hi/lo pairs + fp32 vectors of one layer
 };
 
 // tile: index of the 16-sample tile; crank / csize: this workgroup's rank in / the size of the cluster that shares the tile
-// (rank 0 stores `out`, the next layer's projection is split over the ranks).  O_COHERENT: `o` was written by OTHER
-// workgroups of the same launch with system-scope write-through stores: read it with loads that bypass the non-coherent
-// caches (raw buffer loads, aux sc0 | sc1).
+// (rank 0 stores `out`, the next layer's projection is split over the ranks).
 // O_BF16: `o` is already a bf16 matrix [B, HK] (the folded attention's weighted bank rows, sq_mha_folded_bf16.hip): it is copied
 // into the A image as it is, any HK that fits LDS (TERMS == 1 only: there is no lo image).
-template <int TERMS, bool O_COHERENT, bool O_BF16 = false>
+template <int TERMS, bool O_BF16 = false>
 __device__ __forceinline__ void tail_bf16_body(unsigned char* smem_b, const float* __restrict__ o, int HK, const float* __restrict__ q,
                                                int B, const TailW& w, float eps, float* __restrict__ out, int HKn,
                                                float* __restrict__ qh_next, int tile, int crank, int csize,
@@ -180,10 +177,6 @@ __device__ __forceinline__ void tail_bf16_body(unsigned char* smem_b, const floa
         }
     } else {
         constexpr int MAXIT = (ROWS * (2048 / 8 + 2) + NTHR - 1) / NTHR;      // HK <= 2048
-        const int rows_here = B - r0 < ROWS ? B - r0 : ROWS;
-        const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(o + (size_t)r0 * HK), 0, rows_here * HK * (int)sizeof(float), 0x00027000);
-        (void)o_rsrc;
         f32x4 v[MAXIT][2];
 #pragma unroll
         for (int it = 0; it < MAXIT; ++it) {
@@ -192,15 +185,9 @@ __device__ __forceinline__ void tail_bf16_body(unsigned char* smem_b, const floa
             v[it][0] = v[it][1] = f32x4{0.f, 0.f, 0.f, 0.f};
             const int cg = c + 4 * ks_lo;                     // this rank's K slice (all of K without a split)
             if (i < ROWS * so && r0 + r < B && c < 4 * KSo && cg * 8 < HK) {
-                if (O_COHERENT) {
-                    const int off = (int)(((size_t)r * HK + cg * 8) * sizeof(float));
-                    v[it][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(o_rsrc, off, 0, 17));
-                    v[it][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(o_rsrc, off + 16, 0, 17));
-                } else {
-                    const f32x4* src = reinterpret_cast<const f32x4*>(o + (size_t)(r0 + r) * HK + cg * 8);
-                    v[it][0] = src[0];
-                    v[it][1] = src[1];
-                }
+                const f32x4* src = reinterpret_cast<const f32x4*>(o + (size_t)(r0 + r) * HK + cg * 8);
+                v[it][0] = src[0];
+                v[it][1] = src[1];
             }
         }
 #pragma unroll

@@ -144,10 +144,10 @@ __global__ __launch_bounds__(256) void classifier_head_kernel(const float* __res
 // the four features, so each stack's chain ends with ITS part -- one wave per sample writes parts[p][b][:] -- and whichever
 // of the nparts launches finishes last adds the parts in index order (deterministic) and writes the logits.  Saves the
 // segment boundary in front of the head: dependent work behind events of three other streams started 15-28 us after the last
-// of them (profiles/r03_timeline.txt, tools/dev/boundary_gap.py).  Hand-over without fences, like the fused layer kernel: the
-// parts leave through system-scope write-through stores (sc0 | sc1), every thread waits for its own acknowledgements
-// (vmcnt(0)), ONE relaxed agent-scope atomic per workgroup counts arrivals, the last arriver reads with loads that bypass the
-// non-coherent caches and re-arms the counter.
+// of them (profiles/r03_timeline.txt, tools/dev/boundary_gap.py).  Hand-over without fences: the parts leave through
+// system-scope write-through stores (sc0 | sc1), every thread waits for its own acknowledgements (vmcnt(0)), ONE relaxed
+// agent-scope atomic per workgroup counts arrivals, the last arriver reads with loads that bypass the non-coherent caches and
+// re-arms the counter.
 template <int NI>
 __global__ __launch_bounds__(256) void classifier_part_kernel(const float* __restrict__ f, int part, int nparts, int B, int D,
                                                               const float* __restrict__ W, const float* __restrict__ bias, int NL,

@@ -512,10 +512,6 @@ __global__ __launch_bounds__(NTHR) void sq_mha32_core_kernel(const float* __rest
     const int n_sel = n_mt <= 1 ? 1 : n_mt <= 2 ? 2 : n_mt <= 4 ? 4 : MT;
     // rows >= L of the class read the zero padding at the end of bank row 0 (columns 312..319)
     stage_rows(smem, n_sel * RT, xb + (CH - 1), [&](int row) { return row < L ? xb + (size_t)row * CH : (const uint4*)nullptr; });
-#ifdef MG_MHA32_ONLY                   // measurement builds: one tile-count class (register / code-size studies)
-    mha_body<MG_MHA32_ONLY>(smem, B, L, H, Wp, bv, temp, o, attn, lvalid);
-    return;
-#endif
     switch (n_sel) {
         case 1: mha_body<1>(smem, B, L, H, Wp, bv, temp, o, attn, lvalid); break;
         case 2: mha_body<2>(smem, B, L, H, Wp, bv, temp, o, attn, lvalid); break;
@@ -856,7 +852,6 @@ extern "C" int mgnns_sq_mha32_core_bf16_fwd(const float* qh, const void* bank_bf
     MG_DYN_LDS(sq_mha32_core_kernel, SMEM_BYTES);
     int gy = 1;                         // one workgroup per sample owns all head pairs when the batch fills the chip
     while (gy < pairs && B * gy < n_cu) gy *= 2;
-    if (const int e = mg_env_int("MGNNS_MHA_SPLIT", 0, 4)) gy = e;        // measurement knob: workgroups per sample
     if (gy > pairs) gy = pairs;
     hipLaunchKernelGGL(sq_mha32_core_kernel, dim3(B, gy), dim3(NTHR), SMEM_BYTES, (hipStream_t)stream, qh,
                        reinterpret_cast<const unsigned short*>(bank_bf16), mask, B, L, H,

@@ -58,10 +58,8 @@ static_assert(OFF_U % 16 == 0 && OFF_SC % 16 == 0 && OFF_P % 16 == 0, "LDS align
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-// The transposing read (TR): lane i of a 16-lane group passes the address of row (i >> 2), features 4 (i & 3) .. + 3 of the
-// group's 4-row x 16-feature block and receives feature i of rows 0 .. 3.  TR = false reads the same values with 2-byte loads
-// (MGNNS_FOLD_TR=0: the cross-check of the transposing form in the tests).
-template <bool TR>
+// The B operand of the weighted sum comes through the transposing read (ds_read_tr16_b64): lane i of a 16-lane group passes the
+// address of row (i >> 2), features 4 (i & 3) .. + 3 of the group's 4-row x 16-feature block and receives feature i of rows 0 .. 3.
 __global__ __launch_bounds__(NTHR) void folded_attn_bf16_kernel(const float* __restrict__ U, const unsigned short* __restrict__ bank,
                                                                 const float* __restrict__ mask, int B, int L, int D, int H,
                                                                 float inv_temp, unsigned short* __restrict__ C, int ldc,
@@ -213,28 +211,13 @@ __global__ __launch_bounds__(NTHR) void folded_attn_bf16_kernel(const float* __r
         auto fetch = [&](int ks) {
             a = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(s_p + n * PROW + ((ks * 4 + g) << 3)));
             const int r_lo = 32 * ks + 4 * g, r_hi = r_lo + 16;
-            int rl, rh;
-            if (TR) {
-                rl = min(r_lo + (n >> 2), last_row);
-                rh = min(r_hi + (n >> 2), last_row);
-            } else {
-                rl = r_lo;
-                rh = r_hi;
-            }
+            const int rl = min(r_lo + (n >> 2), last_row), rh = min(r_hi + (n >> 2), last_row);
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                if (TR) {
-                    const unsigned char* pl = smem + (size_t)rl * ROWB + (size_t)(ft[t] + 4 * (n & 3)) * 2;
-                    const unsigned char* ph = smem + (size_t)rh * ROWB + (size_t)(ft[t] + 4 * (n & 3)) * 2;
-                    lo[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(uintptr_t)pl);
-                    hi[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(uintptr_t)ph);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        lo[t][k] = *reinterpret_cast<const short*>(smem + (size_t)min(rl + k, last_row) * ROWB + (size_t)(ft[t] + n) * 2);
-                        hi[t][k] = *reinterpret_cast<const short*>(smem + (size_t)min(rh + k, last_row) * ROWB + (size_t)(ft[t] + n) * 2);
-                    }
-                }
+                const unsigned char* pl = smem + (size_t)rl * ROWB + (size_t)(ft[t] + 4 * (n & 3)) * 2;
+                const unsigned char* ph = smem + (size_t)rh * ROWB + (size_t)(ft[t] + 4 * (n & 3)) * 2;
+                lo[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(uintptr_t)pl);
+                hi[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(uintptr_t)ph);
             }
         };
         fetch(0);
@@ -288,17 +271,9 @@ extern "C" int mgnns_sq_mha_folded_bf16_fwd(const float* U, const void* bank_bf1
     MG_REQUIRE(ldc >= H * D && ldc % 8 == 0, "mgnns_sq_mha_folded_bf16_fwd: ldc=%d (>= H*D = %d, multiple of 8)", ldc, H * D);
     if (B == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool tr = mg_env_int("MGNNS_FOLD_TR", 1, 6) != 0;
-    MG_DYN_LDS(folded_attn_bf16_kernel<true>, SMEM_BYTES);
-    MG_DYN_LDS(folded_attn_bf16_kernel<false>, SMEM_BYTES);
-    if (tr)
-        hipLaunchKernelGGL(folded_attn_bf16_kernel<true>, dim3(B), dim3(NTHR), SMEM_BYTES, s, U,
-                           static_cast<const unsigned short*>(bank_bf16), mask, B, L, D, H, inv_temp,
-                           static_cast<unsigned short*>(C_bf16), ldc, attn);
-    else
-        hipLaunchKernelGGL(folded_attn_bf16_kernel<false>, dim3(B), dim3(NTHR), SMEM_BYTES, s, U,
-                           static_cast<const unsigned short*>(bank_bf16), mask, B, L, D, H, inv_temp,
-                           static_cast<unsigned short*>(C_bf16), ldc, attn);
+    MG_DYN_LDS(folded_attn_bf16_kernel, SMEM_BYTES);
+    hipLaunchKernelGGL(folded_attn_bf16_kernel, dim3(B), dim3(NTHR), SMEM_BYTES, s, U, static_cast<const unsigned short*>(bank_bf16),
+                       mask, B, L, D, H, inv_temp, static_cast<unsigned short*>(C_bf16), ldc, attn);
     MG_CHECK_LAUNCH("mgnns_sq_mha_folded_bf16_fwd");
     return 0;
 }

@@ -1,7 +1,6 @@
 // Packing plan of a text mask for the packed masked attention launches (sq_mha32_bf16.hip: sq_mha32_packed_kernel): one
-// workgroup's worth of device code, shared by the stand-alone plan launch (mgnns_sq_mha32_plan) and by the BiLSTM's prep launch
-// (lstm.hip: an extra workgroup of lstm_prep_kernel builds the plan of the batch's mask while the others pack the batch, so
-// neither masked stack of the forward pays a launch for it -- Multi_GCN_Multihead_att.py:509-527 runs both on the same mask).
+// workgroup's worth of device code, run by the plan launches (mgnns_sq_mha32_plan, mgnns_sq_mha_split_plan).  The forward builds
+// one plan per batch and both masked stacks take it (Multi_GCN_Multihead_att.py:509-527 runs both on the same mask).
 #pragma once
 #include "common.hpp"
 
@@ -39,8 +38,7 @@ __device__ __forceinline__ void build(const float* __restrict__ mask, int B, int
     // live rows = last unmasked position + 1.  A WAVE per sample row, four rows per trip: the row as coalesced dword loads (lane,
     // lane + 64, ...: eight loads in flight per lane for L <= 128), the last live position of a lane's elements, a 64-lane max.
     // (Round 4 swept the mask with an LDS atomicMax per live position; one thread per row with 16-byte loads was no better -- 25
-    // strided loads per thread that the compiler does not keep in flight together: ~10 us either way, and with the plan riding on the
-    // BiLSTM's prep launch that time sits on the chain the forward follows.)
+    // strided loads per thread that the compiler does not keep in flight together: ~10 us either way.)
     {
         const int lane = tid & 63, wv = tid >> 6, NW = NT / 64;
         for (int b0 = wv * 4; b0 < B; b0 += NW * 4) {

@@ -18,24 +18,6 @@ from . import ops
 from . import train as _train
 
 
-import os as _os
-
-TAIL_TERMS = int(_os.environ.get('MGNNS_TAIL_TERMS', '1'))   # bf16-mode tail: 3 = split-bf16 (hi/lo), 1 = plain bf16
-# bf16 mode, 1-term tail: attention core + tail as ONE launch (the tile's last core workgroup runs its tail).  Correct and
-# bit-identical (tests), but OFF by default: 100 us per L=196 layer stand-alone against 91 us for the two launches (the in-kernel
-# tail has no 4-workgroup cluster for the next projection) and 0.99 against 0.91 ms per forward -- DESIGN.md section 6
-FUSED_LAYER = _os.environ.get('MGNNS_FUSED_LAYER', '0') == '1'
-# bf16 mode + set_attention('folded'): the composed-map kernels (sq_mha_folded_bf16.hip + mgnns_mha_tail_c16_fwd); 0 = the three
-# exact-fp32 launches of sq_mha_folded.hip as in fp32 / bf16x3 mode
-FOLDED_BF16 = _os.environ.get('MGNNS_FOLDED_BF16', '1') == '1'
-# bf16x3 mode + faithful attention: the split-bf16 core (sq_mha_split_bf16.hip); 0 = the exact-f32 MFMA core of fp32 mode
-SPLIT_CORE = _os.environ.get('MGNNS_SPLIT_CORE', '1') == '1'
-# ... its masked launches (the text bank) in the GROUPED form: the samples of a group share a workgroup's staging and weight stream
-SPLIT_GROUPED = _os.environ.get('MGNNS_SPLIT_GROUPED', '1') == '1'
-# split-bf16 (terms = 3) layer tails with fc's K split over a cluster of workgroups like the bf16 mode's
-TAIL3_KSPLIT = _os.environ.get('MGNNS_TAIL3_KSPLIT', '1') == '1'
-
-
 def _require_eval(mod):
     if mod.training:
         raise RuntimeError("%s: mgnns_amd implements the eval-mode forward only (dropout/backward are "
@@ -81,9 +63,9 @@ def mask_plan_applies(mask, precision='bf16', attention='faithful'):
     kind of plan: 'packed' (bf16 mode: sq_mha32_packed_kernel) | 'grouped' (bf16x3 + faithful: the split-bf16 core's grouped form)."""
     if mask is None or attention != 'faithful' or mask.shape[0] > ops.PLAN_MAX_B:
         return False
-    if precision == 'bf16' and ops.MHA_CORE == 32 and ops.MHA_PACKED and mask.shape[-1] <= ops.PLAN_MAX_L and not FUSED_LAYER:
+    if precision == 'bf16' and mask.shape[-1] <= ops.PLAN_MAX_L:
         return 'packed'
-    if precision == 'bf16x3' and SPLIT_CORE and SPLIT_GROUPED and mask.shape[-1] <= ops.SPLIT_PLAN_MAX_L:
+    if precision == 'bf16x3' and mask.shape[-1] <= ops.SPLIT_PLAN_MAX_L:
         return 'grouped'
     return False
 
@@ -91,8 +73,7 @@ def mask_plan_applies(mask, precision='bf16', attention='faithful'):
 def make_mask_plan(mask, precision='bf16', attention='faithful'):
     """The packing plan of a [B, L] attention mask for the masked attention launches of this mode (ops.sq_mha_plan / ops.sq_mha_split_plan:
     the live rows of short samples share a workgroup), or None where it does not apply.  Depends on the mask's VALUES only; whoever
-    passes it to run_stack(plan=...) orders the launch that built it in front of the stack (an event if it ran on another stream).
-    The model's bf16 forward gets the same plan out of the BiLSTM's prep launch instead (ops.bilstm(plan_mask=...))."""
+    passes it to run_stack(plan=...) orders the launch that built it in front of the stack (an event if it ran on another stream)."""
     kind = mask_plan_applies(mask, precision, attention)
     if not kind:
         return None
@@ -157,26 +138,31 @@ class MultiHeadAttention(nn.Module):
         q2 = q.reshape(B, -1).contiguous()
         m2 = None if mask is None else mask.reshape(B, -1).float().contiguous()
         qh = ops.linear(q2, self.w_qs.weight.detach(), self.w_qs.bias.detach())
-        if self.attention == 'folded':
-            o, attn = self._folded(qh, bank, m2, True)
-        elif self.precision == 'bf16':
-            o, attn = ops.sq_mha_core_bf16(qh, bank.bf16, m2, self.n_head, self.d_k, self._packed_kv(ops.MHA_CORE_PLAIN),
-                                           self.w_ks.bias.detach(), self.w_vs.bias.detach())
-        elif self._split_core():
-            o, attn = ops.sq_mha_core_split(qh, bank.split, m2, self.n_head, self.d_k, self._packed_kv("split"),
-                                            self.w_ks.bias.detach(), self.w_vs.bias.detach())
-        else:
-            if bank.f32 is None:
-                raise ValueError("fp32 attention needs the fp32 memory bank")
-            o, attn = ops.sq_mha_core(qh, bank.f32, m2, self.n_head, self.d_k,
-                                      self.w_ks.weight.detach(), self.w_ks.bias.detach(),
-                                      self.w_vs.weight.detach(), self.w_vs.bias.detach())
+        o, attn = self._core(qh, bank, m2, None, True)
         y = ops.linear(o, self.fc.weight.detach(), self.fc.bias.detach(), residual=q2)
         y = self.layer_norm(y)
         if self.is_regu:                    # submodules.py:84-93: the head-difference term as a third result
             return y.view(B, 1, -1), attn, ops.head_diff(o, self.n_head)
         return y.view(B, 1, -1), attn
 
+    def _core(self, qh, bank, m2, plan, want_attn):
+        """The attention core of this layer's mode on the projected query qh [B, H*dk] -> (o [B, H*dk], attn or None).  plan: the
+        mask's packing plan (make_mask_plan) or None; with a packed plan bf16 mode runs the 32x32x16 build, without one the 16x16x32
+        build.  bf16x3 + faithful runs the split-bf16 core where it takes the shape, every other case the exact-f32 core."""
+        bk, bv = self.w_ks.bias.detach(), self.w_vs.bias.detach()
+        if self.attention == 'folded':
+            return self._folded(qh, bank, m2, want_attn)
+        if self.precision == 'bf16':
+            return ops.sq_mha_core_bf16(qh, bank.bf16, m2, self.n_head, self.d_k,
+                                        self._packed_kv(ops.MHA_CORE if plan is not None else ops.MHA_CORE_PLAIN), bk, bv,
+                                        want_attn=want_attn, plan=plan)
+        if self._split_core():
+            return ops.sq_mha_core_split(qh, bank.split, m2, self.n_head, self.d_k, self._packed_kv("split"), bk, bv,
+                                         want_attn=want_attn, plan=plan)
+        if bank.f32 is None:
+            raise ValueError("fp32 attention needs the fp32 memory bank")
+        return ops.sq_mha_core(qh, bank.f32, m2, self.n_head, self.d_k, self.w_ks.weight.detach(), bk, self.w_vs.weight.detach(),
+                               bv, want_attn=want_attn)
 
     def _folded(self, qh, bank, m2, want_attn):
         """K/V projections folded into the query side (csrc/sq_mha_folded.hip): algebraically the reference's
@@ -187,13 +173,13 @@ class MultiHeadAttention(nn.Module):
 
     def _split_core(self):
         """'bf16x3' + 'faithful': the K/V projections on split-bf16 operands (csrc/sq_mha_split_bf16.hip) -- the reference's
-        formulation inside the 1e-4 gate without the exact-f32 MFMA's 16x lower rate (MGNNS_SPLIT_CORE=0: the exact-f32 core)."""
-        return (self.precision == 'bf16x3' and self.attention == 'faithful' and SPLIT_CORE and self.d_k == 128
+        formulation inside the 1e-4 gate without the exact-f32 MFMA's 16x lower rate (shapes it does not take: the exact-f32 core)."""
+        return (self.precision == 'bf16x3' and self.attention == 'faithful' and self.d_k == 128
                 and self.n_head <= 16 and self.w_ks.in_features <= ops.BANK_LD)
 
     def _packed_kv(self, form=None):
-        """w_ks / w_vs in the MFMA-fragment-major bf16 layout of the attention core's build `form` (ops.MHA_CORE; the fused
-        layer kernel takes 16), rebuilt when either weight changes."""
+        """w_ks / w_vs in the MFMA-fragment-major bf16 layout of the attention core's build `form` (ops.MHA_CORE, ops.MHA_CORE_PLAIN
+        or "split"), rebuilt when either weight changes."""
         form = ops.MHA_CORE if form is None else form
         wk, wv = self.w_ks.weight, self.w_vs.weight
         key = (wk.data_ptr(), wk._version, wv.data_ptr(), wv._version, str(wk.device))
@@ -312,7 +298,7 @@ def _wq_pack_bf16(layer):
 
 def _use_folded_bf16(a):
     """bf16 mode + folded attention: the composed-map form (sq_mha_folded_bf16.hip) instead of the three exact-fp32 launches."""
-    return a.attention == 'folded' and a.precision == 'bf16' and not a.is_regu and FOLDED_BF16
+    return a.attention == 'folded' and a.precision == 'bf16' and not a.is_regu
 
 
 def composed_query_map(layer):
@@ -363,17 +349,6 @@ def _tail_pack_folded(layer):
         ops.retire(getattr(layer, "_tail_cache_folded", None))      # a live capture may hold the old pack's addresses
         layer._tail_cache_folded = hit
     return hit[1]
-
-
-def _tile_counters(layer, B, device):
-    """int32 zeros [ceil(B/16)] owned by the layer: arrival counters of the fused layer kernel (it leaves them zero)."""
-    n = (B + 15) // 16
-    c = getattr(layer, "_tile_counters", None)
-    if c is None or c.shape[0] < n or c.device != device:
-        c = torch.zeros(max(n, 64), dtype=torch.int32, device=device)
-        ops.retire(getattr(layer, "_tile_counters", None))
-        layer._tile_counters = c
-    return c
 
 
 def _wq_pack(layer):
@@ -456,37 +431,17 @@ def run_stack(layers, q, bank, mask=None, qh=None, plan=None):
         plan = make_mask_plan(m2, a0.precision, a0.attention)
     for i, layer in enumerate(layers):
         a = layer.slf_attn
-        if a.attention == 'folded':
-            o, _ = a._folded(qh, bank, m2, False)
-        elif a.precision == 'bf16' and FUSED_LAYER and TAIL_TERMS == 1 and a.n_head * a.d_v % 32 == 0:
-            # the whole layer in one launch: the tile's last attention-core workgroup runs the tile's tail
-            nxt = _wq_pack_bf16(layers[i + 1]) if i + 1 < len(layers) else None
-            q, qh = ops.sq_mha_layer_bf16(qh, bank.bf16, m2, a.n_head, a.d_k, a._packed_kv(16), a.w_ks.bias.detach(),
-                                          a.w_vs.bias.detach(), q, _tail_pack_bf16(layer), a.layer_norm.eps,
-                                          _tile_counters(layer, B, q.device), nxt)
-            continue
-        elif a.precision == 'bf16':
-            # packed masked banks: the 32x32x16 form; one workgroup per sample: whichever form is the faster (ops.MHA_CORE_PLAIN)
-            o, _ = ops.sq_mha_core_bf16(qh, bank.bf16, m2, a.n_head, a.d_k,
-                                        a._packed_kv(32 if plan is not None else ops.MHA_CORE_PLAIN), a.w_ks.bias.detach(),
-                                        a.w_vs.bias.detach(), want_attn=False, plan=plan)
-        elif a._split_core():
-            o, _ = ops.sq_mha_core_split(qh, bank.split, m2, a.n_head, a.d_k, a._packed_kv("split"), a.w_ks.bias.detach(),
-                                         a.w_vs.bias.detach(), want_attn=False, plan=plan)
-        else:
-            o, _ = ops.sq_mha_core(qh, bank.f32, m2, a.n_head, a.d_k, a.w_ks.weight.detach(), a.w_ks.bias.detach(),
-                                   a.w_vs.weight.detach(), a.w_vs.bias.detach(), want_attn=False)
+        o, _ = a._core(qh, bank, m2, plan, False)
         if a.precision in ('bf16', 'bf16x3') and a.n_head * a.d_v % 32 == 0:
-            # bf16 MFMA tail; split-bf16 (hi + lo operands, fp32-class) with MGNNS_TAIL_TERMS=3 and always in 'bf16x3' mode
+            # bf16 MFMA tail, fc's K split over a cluster of workgroups: plain bf16 in 'bf16' mode, split-bf16 (hi + lo operands,
+            # fp32-class) in 'bf16x3' mode, where the next layer's w_qs is an exact-fp32 GEMM behind it
             nxt = _wq_pack_bf16(layers[i + 1]) if i + 1 < len(layers) else None
-            terms = 3 if a.precision == 'bf16x3' else TAIL_TERMS
-            # split-bf16 tail: fc's K split over a cluster too (round 5); the next layer's w_qs then is an exact-fp32 GEMM behind it
+            terms = 3 if a.precision == 'bf16x3' else 1
             nlin = None
-            if terms == 3 and nxt is not None and TAIL3_KSPLIT:
+            if terms == 3 and nxt is not None:
                 an = layers[i + 1].slf_attn
                 nlin = (an.w_qs.weight.detach(), an.w_qs.bias.detach())
-            q, qh = ops.mha_tail_bf16(o, q, _tail_pack_bf16(layer), a.layer_norm.eps, nxt, terms=terms,
-                                      ksplit=(None if terms == 1 else TAIL3_KSPLIT), next_linear=nlin)
+            q, qh = ops.mha_tail_bf16(o, q, _tail_pack_bf16(layer), a.layer_norm.eps, nxt, terms=terms, next_linear=nlin)
         else:
             nxt = _wq_pack(layers[i + 1]) if i + 1 < len(layers) else None
             q, qh = ops.mha_tail(o, q, _tail_pack(layer), a.layer_norm.eps, nxt)

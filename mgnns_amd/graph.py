@@ -38,7 +38,7 @@ def single_graph_probe(schedule, timeout=900, precision="fp32", attention="faith
     capture of a topology is tried in a CHILD process on a small synthetic model (the topology, not the size, is what the
     runtime trips over).  Cached per process."""
     # the TOPOLOGY also depends on the mode: with a packing plan of the text mask (bf16 / bf16x3 + faithful) the image->text stacks
-    # wait for the text-GCN segment as well (model.PLAN_SITE) -- the child captures the mode the caller is in
+    # wait for the text-GCN segment as well (where the plan is built) -- the child captures the mode the caller is in
     key = schedule if (precision, attention) == ("fp32", "faithful") else (schedule, precision, attention)
     if key not in _PROBED:
         # The child is this interpreter with this process's flags (-s / -E / -I: the same site-packages and environment rules

@@ -24,18 +24,6 @@ from .fusion import (MemoryBank, MultiHeadAttention, MyAnotherMultiHeadAttention
                      first_query_pack, first_query_pack_bf16, run_stack)
 from .text_gcn import Model as Text_GCN_Model
 
-# Where the packing plan of the text mask (both masked stacks' attention launches) is built, once per batch:
-#   'text_gcn' (default, round 5)  one small launch at the END of the text-GCN segment -- a stream with 200 us of slack before the
-#              image->text stacks start; they wait for that segment in addition to their own producers;
-#   'prep'     an extra workgroup of the BiLSTM's prep launch (ops.bilstm(plan_mask=...)): no launch at all, but the prep launch --
-#              the head of the chain the forward follows -- is as long as its slowest workgroup, and the plan workgroup (10-15 us of
-#              serial LDS chains) is that: place_bank_first 0.691-0.702 ms two in flight against 0.626-0.628 (NOTES_r05 4);
-#   'tails'    round 4: one launch per channel at the head of its label-attention tail segment.
-PLAN_SITE = os.environ.get("MGNNS_PLAN_SITE", "prep" if os.environ.get("MGNNS_PLAN_IN_PREP") == "1" else "text_gcn")
-if PLAN_SITE not in ("text_gcn", "prep", "tails"):
-    raise ValueError("MGNNS_PLAN_SITE must be text_gcn | prep | tails")
-PLAN_IN_PREP = PLAN_SITE == "prep"
-
 LABEL_GLOVE_CANDIDATES = ('data/glove/tumblr_label_glove.pkl', 'data/tumblr_label_glove.pkl')
 
 
@@ -260,8 +248,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
     def set_precision(self, precision):
         """'fp32': every contraction on the exact-f32 MFMA (the parity path, <=1e-4 on logits).
         'bf16' (BASELINE configs[2]): bf16 operands with fp32 accumulation in the image-bank projection, the fusion
-        attention's K/V projections, the fused layer tail (plain bf16 weights; MGNNS_TAIL_TERMS=3 selects split hi+lo
-        weights) and the BiLSTM's input and recurrent products (MGNNS_LSTM_REC=f32 keeps the exact fp32 recurrence);
+        attention's K/V projections, the fused layer tail (plain bf16 weights) and the BiLSTM's input and recurrent products
+        (MGNNS_LSTM_REC=f32 keeps the exact fp32 recurrence);
         text GCN, label GCN / attention, scores, softmax, LayerNorms, gates, cell state and residuals stay fp32.
         Measured |logit - fp32 CPU oracle| at B=256: 1.6e-2 (not inside the 1e-4 gate, which is the fp32 mode's).
         A feature map whose position count P is not in (104, 200] or not a multiple of 4 uses the fp32 bank kernel
@@ -339,20 +327,14 @@ class Multi_GCN_Multihead_Att(nn.Module):
                                 for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")))
         return ws
 
-    def _text_bank(self, text, text_lens, plan_mask=None):
-        """MemoryBank of the text (fp32 + bf16 copy in bf16 mode, both written by the LSTM kernel).  plan_mask: the text mask
-        whose packing plan the bf16 prep launch builds on the side (bank.mask_plan; None where it cannot)."""
+    def _text_bank(self, text, text_lens):
+        """MemoryBank of the text (fp32 + bf16 copy in bf16 mode, both written by the LSTM kernel)."""
         lens = text_lens.to(device=text.device, dtype=torch.int64, non_blocking=True).contiguous()
         if self.precision == 'bf16':                        # ('bf16x3': the exact fp32 recurrence below)
             rec = os.environ.get("MGNNS_LSTM_REC", "bf16")
-            if plan_mask is not None and not ops.bilstm_can_plan(text.shape[0], text.shape[1], self.embedding.weight.shape[1], rec):
-                plan_mask = None
             r = ops.bilstm(text.long().contiguous(), lens, self.embedding.weight.detach(), self._lstm_weights(),
-                           self.hidden_size, self.lstm.num_layers, want_bf16=True, recurrence=rec, cache=self._lstm_cache,
-                           plan_mask=plan_mask)
-            bank = MemoryBank(f32=r[0], bf16=r[1])
-            bank.mask_plan = r[2] if plan_mask is not None else None     # the text mask's packing plan, built by the prep launch
-            return bank
+                           self.hidden_size, self.lstm.num_layers, want_bf16=True, recurrence=rec, cache=self._lstm_cache)
+            return MemoryBank(f32=r[0], bf16=r[1])
         return MemoryBank(f32=ops.bilstm(text.long().contiguous(), lens, self.embedding.weight.detach(),
                                          self._lstm_weights(), self.hidden_size, self.lstm.num_layers,
                                          cache=self._lstm_cache))
@@ -822,7 +804,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
             for nm, layers in (('tio', self.text_img_object_multi_head_att), ('tip', self.text_img_place_multi_head_att)):
                 if len(layers):
                     ctx['qh_' + nm] = first_query(layers, tf)
-            if plan_kind and PLAN_SITE == "text_gcn":
+            if plan_kind:
                 # the mask's packing plan for both image->text stacks (MODEL:509-527), here: this stream is idle from now until
                 # the place bank is done, the stacks that take the plan start ~200 us later (and wait for this segment)
                 ctx['mha_plan'] = make_mask_plan(text_mask.float().contiguous(), self.precision, self.attention)
@@ -833,21 +815,13 @@ class Multi_GCN_Multihead_Att(nn.Module):
             # input conversion first: a bool / int mask (the reference documents a bool tensor) is cast HERE, in the
             # segment both masked stacks wait for
             ctx['text_mask'] = text_mask.float().contiguous()
-            # the packing plan of the mask for both image->text stacks (MODEL:509-527) rides on the BiLSTM's prep launch: one more
-            # workgroup there instead of a launch per channel (round 4) on the stacks' critical paths
-            ctx['text_bank'] = self._text_bank(text, text_lens, ctx['text_mask'] if (PLAN_IN_PREP and plan_kind == 'packed') else None)
+            ctx['text_bank'] = self._text_bank(text, text_lens)
             # bf16x3 + faithful: BOTH masked stacks read the bank's split-bf16 (hi + lo) images and run on different streams --
             # the images are made HERE, in the segment both wait for (made lazily inside the first stack, the other stack's
             # core had no event ordering it behind the conversion launch: a stale read under graph replay)
             if any(m.slf_attn._split_core() for st in (self.img_object_text_multi_head_att, self.img_place_text_multi_head_att)
                    for m in st):
                 ctx['text_bank_split'] = ctx['text_bank'].split      # (MemoryBank caches it: the stacks find the images made)
-            prep_plan = getattr(ctx['text_bank'], 'mask_plan', None)
-            if prep_plan is not None:
-                ctx['mha_plan'] = prep_plan
-            elif PLAN_IN_PREP and plan_kind:
-                # (no prep launch to ride on -- the fp32 LSTM of bf16x3 mode, a shape the fused prep does not take: a launch here)
-                ctx['mha_plan'] = make_mask_plan(ctx['text_mask'], self.precision, self.attention)
             ops.stamp("text bank (LSTM) end")
 
         def lgcn(tag, A, inp, attention):
@@ -890,12 +864,6 @@ class Multi_GCN_Multihead_Att(nn.Module):
 
         def tail(tag, attention, linear_5, x_linear, next_stack, next_name):
             def run():
-                # the packing plan of the text mask for the image->text stack this tail feeds (which samples share a workgroup of
-                # its masked attention launches, MODEL:509-527): one small launch per channel, HERE -- on the stack's own stream,
-                # which has slack; on the BiLSTM's stream (the longest chain) it cost the pipelined forward 3 %, and one plan for
-                # both stacks means a cross-stream dependency the runtime's one-graph capture of the schedule does not survive
-                if plan_kind and PLAN_SITE == "tails":
-                    ctx['mha_plan_' + next_name] = make_mask_plan(text_mask, self.precision, self.attention)
                 ctx['att_' + tag], ctx['qh_' + next_name] = self._channel_tail(
                     ctx['pooled_' + tag], ctx['G_' + tag], ctx.get('Gp_' + tag), ctx['Q_' + tag], attention, linear_5, x_linear,
                     next_stack)
@@ -922,9 +890,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
             def run():
                 ops.stamp("%s stack start" % name)
                 ctx[name] = run_stack(layers, ctx[q_key], ctx[bank_key], ctx['text_mask'] if masked else None,
-                                      qh=ctx.get('qh_' + name),
-                                      plan=(ctx.get('mha_plan_' + name) if ctx.get('mha_plan_' + name) is not None
-                                            else ctx.get('mha_plan')) if masked else None)
+                                      qh=ctx.get('qh_' + name), plan=ctx.get('mha_plan') if masked else None)
                 if split_head:
                     wc, bc, hstate = ctx['_head']
                     ops.classifier_head_part(ctx[name], part_of[name], 4, wc, bc, hstate)
@@ -966,7 +932,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         for entry, skey in sched:
             name, *extra = entry.split("+")          # "seg+other": also wait for `other` (ordering only, no data)
             deps = tuple(self.SEGMENT_DEPS[name]) + tuple(extra)
-            if name in ("iot", "ipt") and plan_kind and PLAN_SITE == "text_gcn" and "text_gcn" not in deps:
+            if name in ("iot", "ipt") and plan_kind and "text_gcn" not in deps:
                 deps += ("text_gcn",)                # the mask's packing plan is built at the end of that segment
             for d in deps:
                 if d not in where:

@@ -610,13 +610,7 @@ def _lstm_table(emb_table, cat0, hidden, cache):
     return table
 
 
-def bilstm_can_plan(B, T, emb_dim, recurrence="bf16"):
-    """Can bilstm(..., plan_mask=...) build the packing plan of the text mask inside its prep launch?"""
-    return recurrence == "bf16" and B <= 1024 and T <= PLAN_MAX_L and emb_dim % 4 == 0 and emb_dim <= 320
-
-
-def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, recurrence="f32", cache=None, fold=None,
-           plan_mask=None):
+def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, recurrence="f32", cache=None, fold=None):
     """tok [B,T] int64, lens [B] int64 (device), weights = list over (layer, direction) of
     (w_ih, w_hh, b_ih, b_hh) -> [B,T,2*hidden] with zeros behind each sample's length
     (+ the same bank as zero-padded bf16 [B,T,320] when want_bf16).  recurrence="bf16": W_hh . h of every step on the
@@ -624,10 +618,7 @@ def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, r
     cache: an LstmCache owned by the module that owns `weights` (None: derived weight forms are rebuilt per call).
     fold (bf16 recurrence; default LSTM_FOLD_EMBEDDING when a cache is given): read the layer-0 input projection out of the
     table folded from the embedding and W_ih once per weight version -- the same rows bit for bit, no GEMM in front of the first
-    recurrence.
-    plan_mask (bf16 recurrence, bilstm_can_plan): the batch's text mask [B, T] float -- the packing plan of that mask for the packed
-    masked attention launches (== sq_mha_plan(plan_mask)) is built by an extra workgroup of the prep launch and returned as a
-    third / second value."""
+    recurrence."""
     import ctypes
     _chk(tok, "text", torch.int64, 2)
     _chk(lens, "text_lens", torch.int64, 1)
@@ -657,12 +648,6 @@ def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, r
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=tok.device)
     out = torch.empty(B, T, 2 * hidden, device=tok.device, dtype=torch.float32)
     out_bf = torch.empty(B, T, BANK_LD, device=tok.device, dtype=torch.bfloat16) if want_bf16 else None
-    plan = None
-    if plan_mask is not None:
-        _chk(plan_mask, "plan_mask", ndim=2)
-        if tuple(plan_mask.shape) != (B, T) or not bilstm_can_plan(B, T, emb_table.shape[1], recurrence):
-            raise ValueError("plan_mask must be the [%d, %d] text mask and needs bilstm_can_plan(...)" % (B, T))
-        plan = torch.empty(L.mgnns_sq_mha32_plan_ints(B), dtype=torch.int32, device=tok.device)
     if recurrence not in ("f32", "bf16"):
         raise ValueError("recurrence must be 'f32' or 'bf16', got %r" % (recurrence,))
     if recurrence == "f32":
@@ -688,14 +673,11 @@ def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, r
             table = _lstm_table(emb_table, cat[0], hidden, cache)
             _launch("mgnns_bilstm_bf16_table_fwd", ("mgnns_bilstm_bf16_table_fwd",), L.mgnns_bilstm_bf16_table_fwd, _p(tok), _p(lens), B, T,
                     _p(emb_table), emb_table.shape[0], emb_table.shape[1], hidden, num_layers, c_wih, c_bih, c_whh, c_bhh,
-                    _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _p(table), _p(plan_mask), _p(plan), _stream())
+                    _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _p(table), _stream())
         else:
             _launch("mgnns_bilstm_bf16_fwd", ("mgnns_bilstm_bf16_fwd",), L.mgnns_bilstm_bf16_fwd, _p(tok), _p(lens), B, T, _p(emb_table),
                     emb_table.shape[0], emb_table.shape[1], hidden, num_layers, c_wih, c_bih, c_whh, c_bhh,
-                    _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _p(plan_mask), _p(plan), _stream())
-    if plan is not None:
-        plan._mg_plan_kind = 'packed'
-        return (out, out_bf, plan) if want_bf16 else (out, plan)
+                    _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _stream())
     return (out, out_bf) if want_bf16 else out
 
 
@@ -973,11 +955,11 @@ def sq_mha_core(qh, bank, mask, n_head, d_kv, wk, bk, wv, bv, want_attn=True):
 
 
 # The bf16 attention core has two builds: 32 = v_mfma_f32_32x32x16_bf16 (csrc/sq_mha32_bf16.hip; packed masked banks), 16 = the
-# 16x16x32 form of rounds 1-3 (csrc/sq_mha_bf16.hip; also what the fused layer kernel runs).  The packed weights differ: a pack
-# carries its form as an attribute and sq_mha_core_bf16 dispatches on it.
-MHA_CORE = int(os.environ.get("MGNNS_MHA_CORE", "32"))
-MHA_CORE_PLAIN = int(os.environ.get("MGNNS_MHA_CORE_PLAIN", "16"))      # one workgroup per sample (no plan): the faster build
-MHA_PACKED = os.environ.get("MGNNS_MHA_PACKED", "1") == "1"      # masked banks: pack the live rows of short samples (a plan)
+# 16x16x32 form of rounds 1-3 (csrc/sq_mha_bf16.hip).  The packed weights differ: a pack carries its form as an attribute and
+# sq_mha_core_bf16 dispatches on it.
+MHA_CORE = 32               # the build that takes a packing plan
+MHA_CORE_PLAIN = 16         # one workgroup per sample (no plan): the faster build
+MHA_PACKED = True           # masked banks: the live rows of short samples packed into shared workgroups (a plan)
 
 
 def pack_kv_weights_bf16(wk, wv, n_head, d_kv, form=None):
@@ -1051,7 +1033,7 @@ def sq_mha_core_bf16(qh, bank_bf16, mask, n_head, d_kv, wp, bk, bv, want_attn=Tr
                 raise ValueError("a packing plan needs a mask, L <= %d and exactly %d ints (a plan built for this batch size)"
                                  % (PLAN_MAX_L, L.mgnns_sq_mha32_plan_ints(B)))
             if getattr(plan, "_mg_plan_kind", 'packed') != 'packed':       # (the grouped split-bf16 core's plan has the same size)
-                raise ValueError("sq_mha_core_bf16 takes the plan sq_mha_plan(mask) / bilstm(plan_mask=...) returned (got kind %r)"
+                raise ValueError("sq_mha_core_bf16 takes the plan sq_mha_plan(mask) returned (got kind %r)"
                                  % plan._mg_plan_kind)
         _launch("mgnns_sq_mha_core_bf16_fwd", ("mgnns_sq_mha_core_bf16_fwd", L_, mask is not None),
                 L.mgnns_sq_mha32_core_bf16_fwd, _p(qh), _p(bank_bf16), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk),
@@ -1140,46 +1122,6 @@ def sq_mha_core_split(qh, bank_split, mask, n_head, d_kv, wp, bk, bv, want_attn=
             _p(qh), _p(bank_split[0]), _p(bank_split[1]), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk), _p(bv), _p(o),
             _p(attn), _p(plan), _stream())
     return o, attn
-
-
-def sq_mha_layer_bf16(qh, bank_bf16, mask, n_head, d_kv, wp, bk, bv, q, packed, eps, counters, next_packed=None):
-    """One fusion layer in one launch (mgnns_sq_mha_layer_bf16_fwd): attention core + fused tail (plain bf16 operands).
-    q: the layer input [B,300]; packed / next_packed as for mha_tail_bf16; counters: int32 zeros [ceil(B/16)] owned by the
-    layer (left zero by the kernel).  -> (out [B,300], qh_next or None)"""
-    import ctypes
-    _chk(qh, "qh", ndim=2)
-    _chk(bank_bf16, "memory bank (bf16)", torch.bfloat16, 3)
-    _chk(wp, "packed K/V weights", torch.uint8, 1)
-    if getattr(wp, "_mg_form", 16) != 16:
-        raise ValueError("the fused layer kernel takes the 16x16x32 form of the packed K/V weights (pack_kv_weights_bf16(form=16))")
-    _chk(q, "q", ndim=2)
-    _chk(counters, "tile counters", torch.int32, 1)
-    B, L_, ld = bank_bf16.shape
-    if qh.shape != (B, n_head * d_kv) or q.shape != (B, 300):
-        raise ValueError("qh %s / q %s do not match batch %d" % (tuple(qh.shape), tuple(q.shape), B))
-    if counters.shape[0] < (B + 15) // 16:
-        raise ValueError("need %d tile counters" % ((B + 15) // 16))
-    if mask is not None:
-        _chk(mask, "mask", ndim=2)
-        if mask.shape != (B, L_):
-            raise ValueError("mask shape %s, expected %s" % (tuple(mask.shape), (B, L_)))
-    o = torch.empty(B, n_head * d_kv, device=qh.device, dtype=torch.float32)
-    out = torch.empty(B, 300, device=qh.device, dtype=torch.float32)
-    ptrs = [packed["fc"][0].data_ptr(), packed["fc"][1].data_ptr(), packed["w1"][0].data_ptr(), packed["w1"][1].data_ptr(),
-            packed["w2"][0].data_ptr(), packed["w2"][1].data_ptr(), None, None]
-    bq = qhn = None
-    hkn = 0
-    if next_packed is not None:
-        (wh, wl), bq, hkn = next_packed
-        ptrs[6], ptrs[7] = wh.data_ptr(), wl.data_ptr()
-        qhn = torch.empty(B, hkn, device=qh.device, dtype=torch.float32)
-    arr = (ctypes.c_void_p * 8)(*ptrs)
-    L = _lib.lib()
-    _launch("mgnns_sq_mha_layer_bf16_fwd", ("mgnns_sq_mha_layer_bf16_fwd", L_, mask is not None), L.mgnns_sq_mha_layer_bf16_fwd,
-            _p(qh), _p(bank_bf16), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk), _p(bv), _p(o), _p(q), 300, arr,
-            _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]), _p(packed["b1"]), _p(packed["b2"]), _p(packed["g2"]),
-            _p(packed["be2"]), float(eps), _p(out), _p(bq), hkn, _p(qhn), _p(counters), _stream())
-    return out, qhn
 
 
 def sq_mha_folded(qh, bank, mask, n_head, d_kv, wk, wv, bv, want_attn=True):
@@ -1282,10 +1224,7 @@ def pack_weight_bf16_split(w):
     return hi, lo
 
 
-TAIL_BF16_KSPLIT = os.environ.get("MGNNS_TAIL_BF16_KSPLIT", "1") == "1"
-
-
-def mha_tail_bf16(o, q, packed, eps, next_packed=None, terms=3, cluster=0, ksplit=None, next_linear=None):
+def mha_tail_bf16(o, q, packed, eps, next_packed=None, terms=3, cluster=0, ksplit=True, next_linear=None):
     """bf16-MFMA fused tail.  packed: dict with fc, w1, w2 = (hi, lo) buffers and fc_b, g1, be1, b1, b2, g2, be2;
     next_packed = ((hi, lo), bq, HK_next) or None.  ksplit (default on): a tile's cluster of workgroups splits the K
     of fc and exchanges partial sums through scratch owned by `packed` (one per capture epoch and launch stream), the next
@@ -1303,7 +1242,7 @@ def mha_tail_bf16(o, q, packed, eps, next_packed=None, terms=3, cluster=0, kspli
             packed["w1"][1].data_ptr(), packed["w2"][0].data_ptr(), packed["w2"][1].data_ptr(), None, None]
     bq = qh = None
     hkn = 0
-    use_ks = (TAIL_BF16_KSPLIT if ksplit is None else ksplit) and B > 0 and cluster != 1
+    use_ks = ksplit and B > 0 and cluster != 1
     if int(terms) == 3 and use_ks and next_packed is not None and next_linear is None:
         use_ks = False                    # (the split-bf16 K split has no packed projection: without next_linear, the one-launch form)
     split_proj = int(terms) == 3 and use_ks and next_linear is not None
@@ -1335,10 +1274,7 @@ def mha_tail_bf16(o, q, packed, eps, next_packed=None, terms=3, cluster=0, kspli
     return out, qh
 
 
-TAIL_C16_KSPLIT = os.environ.get("MGNNS_TAIL_C16_KSPLIT", "1") == "1"
-
-
-def mha_tail_c16(c, q, packed, eps, next_packed=None, cluster=0, ksplit=None):
+def mha_tail_c16(c, q, packed, eps, next_packed=None, cluster=0, ksplit=True):
     """The bf16 fused tail behind sq_mha_folded_bf16 (mgnns_mha_tail_c16_fwd): c bf16 [B, H*300 rounded up to 32];
     packed["fc"] = the composed map fc . blockdiag(W_v); next_packed = ((hi, lo), bias, H*300) of the next layer's composed query
     map or None.  cluster: workgroups per 16-sample tile (0 = the library's default); ksplit (default on): the ranks split the K of
@@ -1360,7 +1296,7 @@ def mha_tail_c16(c, q, packed, eps, next_packed=None, cluster=0, ksplit=None):
     arr = (ctypes.c_void_p * 8)(*ptrs)
     L = _lib.lib()
     scratch = counters = None
-    if (TAIL_C16_KSPLIT if ksplit is None else ksplit) and B > 0 and cluster != 1:
+    if ksplit and B > 0 and cluster != 1:
         tiles = (B + 15) // 16
         slot = packed.setdefault("_cluster_ws", {})
         key = _scratch_key()                                     # per (capture epoch, launch stream), like the channel tail's

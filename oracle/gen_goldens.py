@@ -148,7 +148,7 @@ def gold_mha(ns):
         q, bank, mask = (None if a is None else torch.from_numpy(a) for a in GI.mha_case(H, tag, L, masked))
         with torch.no_grad():
             o, attn = layer(q=q, k=bank, v=bank, mask=mask)
-        mo, ma = R.sq_mha_layer(p, name, q, bank, mask, H, 128)
+        mo, ma = R.mha_layer(p, name, q, bank, mask, H, 128)
         assert maxdiff(mo, o) < 2e-5 and maxdiff(ma, attn) < 1e-5, (maxdiff(mo, o), maxdiff(ma, attn))
         out[name + "_out"] = o
         out[name + "_attn"] = attn
@@ -159,7 +159,7 @@ def gold_mha(ns):
             with torch.no_grad():
                 o2, attn2, hd = regu(q=q, k=bank, v=bank, mask=mask)
             assert maxdiff(o2, o) == 0.0 and maxdiff(attn2, attn) == 0.0
-            assert maxdiff(R.sq_mha_layer(p, name, q, bank, mask, H, 128, return_head_diff=True)[2], hd) < 1e-6
+            assert maxdiff(R.mha_layer(p, name, q, bank, mask, H, 128, return_head_diff=True)[2], hd) < 1e-6
             out[name + "_head_diff"] = hd
     save("mha.npz", **out)
 

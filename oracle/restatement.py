@@ -113,7 +113,7 @@ def layer_norm(x, gamma, beta, eps=1e-6):
     return gamma * (x - mean) / (std + eps) + beta
 
 
-def sq_mha_layer(p, prefix, q, bank, mask, n_head, d_kv, return_head_diff=False):
+def mha_layer(p, prefix, q, bank, mask, n_head, d_kv, return_head_diff=False):
     """MyMultiHeadAttention.forward (moudles.py:207-230) with len_q == 1.
 
     q [B,300], bank [B,L,300] (key = value), mask [B,L] float (1 token / 0 pad) or None.
@@ -158,7 +158,7 @@ def head_diff(o):
 def mha_stack(p, stack, q, bank, mask, n_head, d_kv, stack_num):
     """MODEL:509-546: `stack_num` layers, output of layer i is the query of layer i+1."""
     for i in range(stack_num):
-        q, _ = sq_mha_layer(p, "%s.%d" % (stack, i), q, bank, mask, n_head, d_kv)
+        q, _ = mha_layer(p, "%s.%d" % (stack, i), q, bank, mask, n_head, d_kv)
     return q
 
 

@@ -1377,47 +1377,6 @@ def test_mha_tail_bf16_k_split_over_the_cluster(Hn):
     assert all(int(v[2].abs().sum()) == 0 for v in ws.values())               # the arrival counters are back at zero
 
 
-@pytest.mark.parametrize("Hn,L,masked", [(8, 196, False), (8, 100, True), (4, 196, False), (1, 50, True)])
-def test_fused_layer_bf16_equals_core_plus_tail(Hn, L, masked):
-    """mgnns_sq_mha_layer_bf16_fwd (attention core + the tile's tail run by its last-finishing core workgroup, hand-over of
-    `o` through system-scope stores and one relaxed atomic per workgroup) == the two separate launches, BIT FOR BIT, for
-    batches that fill the chip (one workgroup per sample), smaller ones (head pairs split over workgroups), batches that are
-    not a multiple of the 16-sample tile, repeated launches on the same counters, with and without a next-layer projection."""
-    name = "h%d_img" % Hn
-    pc = H.params_for(H.mha_shapes(Hn), prefix=name + ".")
-    p = dparams(pc)
-    a, f = name + ".slf_attn.", name + ".pos_ffn."
-    w1 = p[f + "w_1.weight"].squeeze(-1).contiguous()
-    w2 = p[f + "w_2.weight"].squeeze(-1).contiguous()
-    pk = {"fc_b": p[a + "fc.bias"], "g1": p[a + "layer_norm.gamma"], "be1": p[a + "layer_norm.beta"], "b1": p[f + "w_1.bias"],
-          "b2": p[f + "w_2.bias"], "g2": p[f + "layer_norm.gamma"], "be2": p[f + "layer_norm.beta"],
-          "fc": ops.pack_weight_bf16_split(p[a + "fc.weight"]), "w1": ops.pack_weight_bf16_split(w1), "w2": ops.pack_weight_bf16_split(w2)}
-    nx = (ops.pack_weight_bf16_split(p[a + "w_qs.weight"]), p[a + "w_qs.bias"], Hn * 128)
-    wp = ops.pack_kv_weights_bf16(p[a + "w_ks.weight"], p[a + "w_vs.weight"], Hn, 128, form=16)      # (the fused layer runs the 16x16x32 core)
-    counters = torch.zeros(64, dtype=torch.int32, device=DEV)
-    rs = np.random.RandomState(Hn + L)
-    for B in (256, 37, 16, 1, 300):
-        bank = ops.cast_pad_bf16(dev(rs.standard_normal((B, L, 300)).astype(np.float32)))
-        qh = dev(rs.standard_normal((B, Hn * 128)).astype(np.float32))
-        q = dev(rs.standard_normal((B, 300)).astype(np.float32))
-        mask = None
-        if masked:
-            m = np.ones((B, L), np.float32)
-            for b in range(B):
-                m[b, rs.randint(1, L + 1):] = 0.0
-            mask = dev(m)
-        o, _ = ops.sq_mha_core_bf16(qh, bank, mask, Hn, 128, wp, p[a + "w_ks.bias"], p[a + "w_vs.bias"], want_attn=False)
-        for nxt in (nx, None):
-            ref_out, ref_qh = ops.mha_tail_bf16(o, q, pk, 1e-6, nxt, terms=1, ksplit=False)      # (the fused layer runs the unsplit chain)
-            for rep in range(3):
-                out, qhn = ops.sq_mha_layer_bf16(qh, bank, mask, Hn, 128, wp, p[a + "w_ks.bias"], p[a + "w_vs.bias"], q, pk, 1e-6,
-                                                 counters, nxt)
-                torch.cuda.synchronize()
-                assert torch.equal(out, ref_out), (B, rep, float((out - ref_out).abs().max()))
-                assert (qhn is None) == (nxt is None) and (nxt is None or torch.equal(qhn, ref_qh)), (B, rep)
-                assert int(counters.abs().sum()) == 0                 # every tile was handed over exactly once
-
-
 def test_metrics_tail_softmax_argmax_confusion():
     """The evaluation tail on the device (ENGINE:828-838): softmax == torch.softmax, pred == argmax(softmax) incl. ties
     (first maximum), confusion matrix accumulated over batches, scores == sklearn's on the concatenated predictions."""
@@ -1561,48 +1520,6 @@ def test_bilstm_bf16_layer0_projection_folded_into_the_embedding_table():
             a1, _ = ops.bilstm(t, l, emb, weights, Hh, 2, want_bf16=True, recurrence="bf16", cache=cache, fold=True)
             b1, _ = ops.bilstm(t, l, emb, weights, Hh, 2, want_bf16=True, recurrence="bf16", cache=ops.LstmCache(), fold=False)
             assert cache.table[2] is not first and torch.equal(a1, b1) and not torch.equal(a1, a0)
-
-
-def test_bilstm_prep_launch_builds_the_mask_packing_plan():
-    """ops.bilstm(plan_mask=mask): the packing plan of the text mask built by an extra workgroup of the BiLSTM's prep launch is the
-    stand-alone plan kernel's (ops.sq_mha_plan) int for int -- ragged lengths, a mask with holes and one that differs from the lengths
-    (the plan is defined by the MASK), folded-table and per-forward projection forms -- and the bank is untouched by it."""
-    import numpy as np
-    rs = np.random.RandomState(31)
-    V, E, Hh = 700, 300, 150
-    emb = torch.from_numpy((0.4 * rs.standard_normal((V, E))).astype(np.float32)).to(DEV)
-    weights = []
-    for layer in range(2):
-        for d in range(2):
-            ind = E if layer == 0 else 2 * Hh
-            weights.append(tuple(torch.from_numpy(rs.uniform(-0.08, 0.08, size=s).astype(np.float32)).to(DEV)
-                                 for s in ((4 * Hh, ind), (4 * Hh, Hh), (4 * Hh,), (4 * Hh,))))
-    for B, T in ((256, 100), (37, 128), (1, 9), (1000, 24)):
-        lens = np.clip(np.round(np.exp(rs.normal(2.4, 0.75, B))), 1, T).astype(int)
-        lens[0] = T
-        tok = np.zeros((B, T), np.int64)
-        mask = np.zeros((B, T), np.float32)
-        for b in range(B):
-            tok[b, :lens[b]] = rs.randint(1, V, size=lens[b])
-            mask[b, :lens[b]] = 1
-        if B > 2:
-            mask[1, ::2] = 0                                   # holes
-            mask[2, :] = 0
-            mask[2, min(T - 1, 5)] = 1                         # a mask that is not the length vector's
-        t, l, m = torch.from_numpy(tok).to(DEV), torch.from_numpy(lens.astype(np.int64)).to(DEV), torch.from_numpy(mask).to(DEV)
-        assert ops.bilstm_can_plan(B, T, E)
-        want = ops.sq_mha_plan(m)
-        for fold in (True, False):
-            cache = ops.LstmCache()
-            ref, ref_bf = ops.bilstm(t, l, emb, weights, Hh, 2, want_bf16=True, recurrence="bf16", cache=cache, fold=fold)
-            out, out_bf, plan = ops.bilstm(t, l, emb, weights, Hh, 2, want_bf16=True, recurrence="bf16", cache=cache, fold=fold,
-                                           plan_mask=m)
-            # (group slots behind the last group are never written by either launch)
-            ng = int(want[0])
-            assert torch.equal(plan[:4 + 4 * ng], want[:4 + 4 * ng]) and torch.equal(plan[4 + 4 * B:], want[4 + 4 * B:]), (B, T, fold)
-            assert torch.equal(out, ref) and torch.equal(out_bf, ref_bf)
-    with pytest.raises(ValueError):
-        ops.bilstm(t, l, emb, weights, Hh, 2, want_bf16=True, recurrence="f32", plan_mask=m)
 
 
 def test_bilstm_trailing_empty_samples_never_index_the_table_with_unwritten_tokens():

@@ -65,7 +65,7 @@ def test_single_query_mha_layer(Hn, tag, L, masked):
     name = "h%d_%s" % (Hn, tag)
     p = H.params_for(H.mha_shapes(Hn), prefix=name + ".")
     q, bank, mask = (None if a is None else torch.from_numpy(a) for a in GI.mha_case(Hn, tag, L, masked))
-    out, attn = R.sq_mha_layer(p, name, q, bank, mask, Hn, 128)
+    out, attn = R.mha_layer(p, name, q, bank, mask, Hn, 128)
     assert H.maxabs(out, g[name + "_out"]) < 2e-5
     assert H.maxabs(attn, g[name + "_attn"]) < 1e-5
     assert attn.shape == (Hn * GI.MHA_B, 1, L)
@@ -73,7 +73,7 @@ def test_single_query_mha_layer(Hn, tag, L, masked):
         m = torch.from_numpy(np.tile(GI.mha_case(Hn, tag, L, masked)[2], (Hn, 1)))
         assert float((attn[:, 0, :] * (1 - m)).abs().max()) == 0.0
     if Hn > 1:   # is_regu=True: the head-difference term of the same layer (reference output)
-        hd = R.sq_mha_layer(p, name, q, bank, mask, Hn, 128, return_head_diff=True)[2]
+        hd = R.mha_layer(p, name, q, bank, mask, Hn, 128, return_head_diff=True)[2]
         assert H.maxabs(hd, g[name + "_head_diff"]) < 1e-6
 
 

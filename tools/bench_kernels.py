@@ -47,7 +47,7 @@ def timeit(fn, n=20, warm=5):
 
 
 def mha(kind, B=256, L=196, H=8, masked=False):
-    L = int(os.environ.get("MGNNS_BENCH_L", L)) if not masked else L          # (L = 192 with the 12-tile ablation build: the 13th tile's cost)
+    L = int(os.environ.get("MGNNS_BENCH_L", L)) if not masked else L
     g = torch.Generator(device=DEV).manual_seed(0)
     bank = torch.randn(B, L, 300, device=DEV, generator=g)
     qh = torch.randn(B, H * 128, device=DEV, generator=g)
@@ -77,7 +77,7 @@ def mha(kind, B=256, L=196, H=8, masked=False):
         sp = ops.split_pad_bf16(bank)
         wp = ops.pack_kv_weights_split(wk, wv, H, 128)
         print("  split_pad_bf16 (fp32 bank -> hi + lo images): %.1f us" % (timeit(lambda: ops.split_pad_bf16(bank)) * 1e3))
-        plan = ops.sq_mha_split_plan(mask) if (masked and L <= ops.SPLIT_PLAN_MAX_L and os.environ.get("MGNNS_SPLIT_GROUPED", "1") == "1") else None
+        plan = ops.sq_mha_split_plan(mask) if (masked and L <= ops.SPLIT_PLAN_MAX_L) else None
         if plan is not None:
             print("  group plan: %d groups for %d samples, %d live rows; sq_mha_split_plan %.1f us"
                   % (int(plan[0]), B, int(mask.sum()), timeit(lambda: ops.sq_mha_split_plan(mask)) * 1e3))
