@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 21
+#define MGNNS_ABI_VERSION 22
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -598,6 +598,56 @@ size_t mgnns_label_attn_train_bwd_workspace_bytes(int B, int NLQ, int H, int dh)
 int mgnns_label_attn_train_bwd(const float* dx, const float* Q, const float* K, const float* V, const float* P,
                                const uint8_t* keep, int B, int NLQ, int H, int dh, float rate, float* dQ, float* dK, float* dV,
                                void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
+
+/* ---- training mode of the text encoders (fp32): the packed 2-layer BiLSTM and the text GCN ----------------------------------
+ * Two more dropout sites: 5 = the BiLSTM's inter-layer dropout on layer 0's output, index (b*T + t)*2H + j over [B, T, 2H];
+ * 6 = the text GCN's dropout before its ReLU, index b*D + d over [B, D].
+ * mgnns_bilstm_train_fwd: the eval forward (mgnns_bilstm_fwd, fp32 recurrence; bit for bit its bank at rate 0) with dropout(rate) at
+ * site 5 between the layers, keeping for the backward: meta (int32: offs [B+1] | order [B+8] | pack_tok [B*T] | pack_pos [B*T]),
+ * gates [num_layers][2][rows_cap][4H] (after the activations) and cells [num_layers][2][rows_cap][H] at row offs[b] + t,
+ * mid / mid_drop [B, T, 2H] (layer 0's output before / after the dropout; unused with one layer).  rows_cap >= sum of the
+ * clamped lengths.  workspace: mgnns_bilstm_train_workspace_bytes(B, T, hidden) bytes.
+ * mgnns_bilstm_train_bwd_rec: one layer's backward recurrence from dout [B, T, 2H] -> dz [rows, 2 * 4H] (pre-activation gate
+ * gradients, forward direction then reverse, row offs[b] + t); gates / cells: that layer's slices.
+ * mgnns_bilstm_train_hprev: hprev [rows, 2H] = each packed step's recurrent input (forward: h at t-1, reverse: h at t+1, 0 at
+ * a chain's first step) from a layer output hout [B, T, 2H].
+ * mgnns_bilstm_train_unpack_drop: dout[pack_pos[r], :] = dx[r, :] through the site-5 mask (dout zeroed by the caller).
+ * mgnns_gather_rows: dst[r, :] = src[idx[r], :] (r < M).
+ * mgnns_keyed_row_sum: out[k, :] = sum of values[perm[r], :] over the sorted run of key k, in sorted order (a stable sort
+ * makes the result deterministic); keys below skip_below and at or past K add nothing; rows of out without a key are left
+ * as the caller set them.
+ * mgnns_textgcn_train_fwd: mgnns_textgcn_fwd with dropout(rate) at site 6 before the ReLU; presum [B, D] (before the dropout) and
+ * win [B, min(T, max_length), D] int16 (the source position of the winning in-edge, written at the first position of each
+ * node) for the backward.  Tie rule: the smallest source position whose fp32 product equals the fp32 max.
+ * mgnns_textgcn_train_bwd: from dy [B, D] the per-document partials: R [B, Tm, D] rows keyed by keyR [B, Tm] (the token id of
+ * the source, -1 = none) for node_hidden; Eg [B, Tm, 2 ngram + 1] keyed by keyE (edge id, -1 = none) for seq_edge_w.
+ */
+#define MGNNS_DROP_LSTM       5
+#define MGNNS_DROP_TEXT_GCN   6
+size_t mgnns_bilstm_train_workspace_bytes(int B, int T, int hidden);
+int mgnns_bilstm_train_fwd(const int64_t* tok, const int64_t* lens, int B, int T, const float* emb_table, int V, int emb_dim,
+                           int hidden, int num_layers, const float* const* w_ih_cat, const float* const* b_ih_cat,
+                           const float* const* w_hh, const float* const* b_hh, uint64_t seed, float rate, int32_t* meta,
+                           int rows_cap, float* gates, float* cells, float* mid, float* mid_drop, float* out, void* workspace,
+                           size_t workspace_bytes, mgnns_stream_t stream);
+int mgnns_bilstm_train_bwd_rec(const float* dout, const int64_t* lens, int B, int T, const int32_t* meta, int rows_cap,
+                               const float* gates, const float* cells, const float* w_hh_f, const float* w_hh_r, float* dz,
+                               mgnns_stream_t stream);
+int mgnns_bilstm_train_hprev(const float* hout, const int64_t* lens, int B, int T, const int32_t* meta, int rows_cap, float* hprev,
+                             mgnns_stream_t stream);
+int mgnns_bilstm_train_unpack_drop(const float* dx, const int32_t* pack_pos, int64_t M, int B, int T, uint64_t seed, float rate,
+                                   float* dout, mgnns_stream_t stream);
+int mgnns_gather_rows(const float* src, int n_src, int K, const int32_t* idx, int64_t M, float* dst, mgnns_stream_t stream);
+int mgnns_keyed_row_sum(const int64_t* sorted_keys, const int64_t* perm, int64_t M, const float* values, int D, int64_t n_values,
+                        int64_t skip_below, float* out, int64_t K, mgnns_stream_t stream);
+int mgnns_textgcn_train_fwd(const int64_t* tok, int B, int T, const float* node_hidden, int V, int D, const float* edge_w,
+                            int n_edge_w, const int32_t* pmi_row_ptr, const int32_t* pmi_col, const int32_t* pmi_eid, int ngram,
+                            int max_length, uint64_t seed, float rate, float* out, float* presum, int16_t* win,
+                            mgnns_stream_t stream);
+int mgnns_textgcn_train_bwd(const int64_t* tok, int B, int T, const float* node_hidden, int V, int D, const float* edge_w,
+                            int n_edge_w, const int32_t* pmi_row_ptr, const int32_t* pmi_col, const int32_t* pmi_eid, int ngram,
+                            int max_length, uint64_t seed, float rate, const float* dy, const float* presum, const int16_t* win,
+                            float* R, int32_t* keyR, float* Eg, int32_t* keyE, mgnns_stream_t stream);
 int mgnns_dropout_fwd(const float* x, int64_t n, uint64_t seed, int site, float rate, float* y, uint8_t* keep,
                       mgnns_stream_t stream);
 int mgnns_dropout_bwd(const float* dy, const uint8_t* keep, int64_t n, float rate, float* dx, mgnns_stream_t stream);

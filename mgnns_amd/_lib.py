@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _c = ctypes
 _P = _c.c_void_p
@@ -103,6 +103,15 @@ SIGNATURES = {
     "mgnns_dropout_fwd": [_P, _L, _U64, _I, _F, _P, _P, _P],
     "mgnns_dropout_bwd": [_P, _P, _L, _F, _P, _P],
     "mgnns_dropout_mask": [_U64, _I, _F, _L, _P, _P],
+    "mgnns_bilstm_train_fwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _PP, _PP, _PP, _PP, _U64, _F, _P, _I, _P, _P, _P, _P, _P, _P,
+                               _SZ, _P],
+    "mgnns_bilstm_train_bwd_rec": [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
+    "mgnns_bilstm_train_hprev": [_P, _P, _I, _I, _P, _I, _P, _P],
+    "mgnns_bilstm_train_unpack_drop": [_P, _P, _L, _I, _I, _U64, _F, _P, _P],
+    "mgnns_gather_rows": [_P, _I, _I, _P, _L, _P, _P],
+    "mgnns_keyed_row_sum": [_P, _P, _L, _P, _I, _L, _L, _P, _L, _P],
+    "mgnns_textgcn_train_fwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _U64, _F, _P, _P, _P, _P],
+    "mgnns_textgcn_train_bwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _U64, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "mgnns_comm_unique_id": [_P, _SZ],
     "mgnns_comm_init_rank": [_I, _I, _P, _SZ, _PP],
     "mgnns_comm_init_all": [_I, _P, _PP],
@@ -135,6 +144,7 @@ SIZE_GETTERS = {
     "mgnns_wgrad_workspace_bytes": [_I, _I, _I],
     "mgnns_imgbank_wgrad_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_label_attn_train_bwd_workspace_bytes": [_I, _I, _I, _I],
+    "mgnns_bilstm_train_workspace_bytes": [_I, _I, _I],
 }
 
 _lib = None

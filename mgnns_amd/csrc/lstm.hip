@@ -172,12 +172,17 @@ constexpr int NWAVE = 12;
 constexpr int RPL = 10;              // gate rows per lane (ceil(600 / 64))
 constexpr int PSTR = 640;            // row stride of the partial-sum array
 
+// SAVE (the training forward, text_train.hip): also store every step's post-activation gates and cell state at the packed row
+// offs[b] + t -- gates [2][rows_cap][4H], cells [2][rows_cap][H] -- with the arithmetic untouched, so the h rows are the eval
+// kernel's bit for bit.
+template <bool SAVE>
 __global__ __launch_bounds__(REC_THREADS) void lstm_rec_kernel(const float* __restrict__ Gx, const int32_t* __restrict__ offs,
                                                                const int64_t* __restrict__ lens, int T,
                                                                const float* __restrict__ Whh_f, const float* __restrict__ Whh_b,
                                                                const float* __restrict__ bhh_f, const float* __restrict__ bhh_b,
                                                                const int32_t* __restrict__ order, float* __restrict__ out,
-                                                               unsigned short* __restrict__ out_bf16, int ld_bf16) {
+                                                               unsigned short* __restrict__ out_bf16, int ld_bf16,
+                                                               float* __restrict__ gates, float* __restrict__ cells, int rows_cap) {
     __shared__ __attribute__((aligned(16))) float s_h[2][NWAVE][16];     // h, chunked per owning wave (15 + 1 pad)
     __shared__ float s_part[NWAVE][PSTR];
     __shared__ float s_act[G4];
@@ -244,7 +249,12 @@ __global__ __launch_bounds__(REC_THREADS) void lstm_rec_kernel(const float* __re
             for (int ww = 1; ww < NWAVE; ++ww) sum += sp[rd_idx + ww * PSTR];
             const float pre = (gx + bias) + sum;
             if (s + 1 < len) gx = gx_base[(size_t)(dir ? len - 2 - s : s + 1) * (2 * G4)];   // next step, in flight
-            s_act[tid] = is_tanh ? tanhf_(pre) : sigmoidf_(pre);
+            const float a = is_tanh ? tanhf_(pre) : sigmoidf_(pre);
+            s_act[tid] = a;
+            if (SAVE) {
+                const int row = off + (dir ? len - 1 - s : s);
+                if (row < rows_cap) gates[((size_t)dir * rows_cap + row) * G4 + tid] = a;
+            }
         }
         mg_lds_barrier();
         // ---- 3. cell update by the 150 unit threads -------------------------------------------------------------------
@@ -254,6 +264,10 @@ __global__ __launch_bounds__(REC_THREADS) void lstm_rec_kernel(const float* __re
             const float hh = og * tanhf_(c);
             s_h[cur ^ 1][tid / KW][tid % KW] = hh;
             s_out[s % OCH][tid] = hh;
+            if (SAVE) {
+                const int row = off + (dir ? len - 1 - s : s);
+                if (row < rows_cap) cells[((size_t)dir * rows_cap + row) * HID + tid] = c;
+            }
         }
         mg_lds_barrier();
         cur ^= 1;
@@ -803,9 +817,9 @@ static int bilstm_impl(bool bf16_rec, const void* prepacked, const int64_t* tok,
                                tab ? (const int32_t*)pack_tok : (const int32_t*)nullptr);
         }
         else
-            hipLaunchKernelGGL(lstm_rec_kernel, dim3(2 * B), dim3(REC_THREADS), 0, s, (const float*)Gx, (const int32_t*)offs, lens,
+            hipLaunchKernelGGL(lstm_rec_kernel<false>, dim3(2 * B), dim3(REC_THREADS), 0, s, (const float*)Gx, (const int32_t*)offs, lens,
                                T, w_hh[2 * layer], w_hh[2 * layer + 1], b_hh[2 * layer], b_hh[2 * layer + 1],
-                               (const int32_t*)order, dst, obf, ld_bf16);
+                               (const int32_t*)order, dst, obf, ld_bf16, (float*)nullptr, (float*)nullptr, 0);
     }
     MG_CHECK_LAUNCH("mgnns_bilstm_fwd");
     return 0;
@@ -860,4 +874,25 @@ extern "C" int mgnns_bilstm_bf16_table_fwd(const int64_t* tok, const int64_t* le
     MG_REQUIRE(gx_table, "mgnns_bilstm_bf16_table_fwd: null table (mgnns_bilstm_bf16_fold_embedding makes it)");
     return bilstm_impl(true, prepacked, tok, lens, B, T, emb_table, V, emb_dim, hidden, num_layers, w_ih_cat, b_ih_cat, w_hh, b_hh, workspace,
                        workspace_bytes, out, out_bf16, ld_bf16, stream, gx_table);
+}
+
+// The fp32 recurrence of one layer with the stores of the training forward (text_train.hip): gates / cells are this layer's
+// [2][rows_cap][4H] / [2][rows_cap][H].
+int mg_launch_lstm_rec_save(const float* Gx, const int32_t* offs, const int64_t* lens, int B, int T, const float* Whh_f,
+                            const float* Whh_b, const float* bhh_f, const float* bhh_b, const int32_t* order, float* out,
+                            float* gates, float* cells, int rows_cap, hipStream_t s) {
+    hipLaunchKernelGGL(lstm_rec_kernel<true>, dim3(2 * B), dim3(REC_THREADS), 0, s, Gx, offs, lens, T, Whh_f, Whh_b, bhh_f, bhh_b, order,
+                       out, (unsigned short*)nullptr, 0, gates, cells, rows_cap);
+    MG_CHECK_LAUNCH("mg_launch_lstm_rec_save");
+    return 0;
+}
+
+// The packing of the forward (offs [B+1], order [B+8], pack_tok / pack_pos [B*T]) for the training kernels (text_train.hip),
+// which keep it for their backward.
+int mg_lstm_pack(const int64_t* tok, const int64_t* lens, int B, int T, int V, int32_t* offs, int32_t* order, int32_t* pack_tok,
+                 int32_t* pack_pos, hipStream_t s) {
+    hipLaunchKernelGGL(lstm_pack_kernel, dim3(1), dim3(1024), 0, s, lens, B, T, offs, order);
+    hipLaunchKernelGGL(lstm_fill_kernel, dim3(B), dim3(128), 0, s, tok, lens, T, V, (const int32_t*)offs, pack_tok, pack_pos);
+    MG_CHECK_LAUNCH("mg_lstm_pack");
+    return 0;
 }

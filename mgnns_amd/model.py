@@ -224,6 +224,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self._wt_cache = {}
         self._adj_cache = {}                   # training mode: (CSR, CSR of the transpose) of gen_adj(A) per adjacency version
         self.last_dropout_seed = None          # training mode: the classifier dropout's seed of the last forward
+        self.text_encoders_trainable = False   # unfreeze_text_encoders(): training mode trains the text encoders too
         self._lstm_cache = ops.LstmCache()     # derived LSTM weight forms live and die with this module
         self._streams = None
         self.use_streams = bool(opt.get('use_streams', True))
@@ -347,8 +348,12 @@ class Multi_GCN_Multihead_Att(nn.Module):
             raise NotImplementedError("the HIP text bank implements the bidirectional LSTM the reference configures")
         batch_size, max_text_len = list(text.size())
         lens = text_lens.to(device=text.device, dtype=torch.int64, non_blocking=True).contiguous()
-        memory_bank = ops.bilstm(text.long().contiguous(), lens, self.embedding.weight.detach(),
-                                 self._lstm_weights(), self.hidden_size, self.lstm.num_layers, cache=self._lstm_cache)
+        if self.training and self.text_encoders_trainable:
+            memory_bank = _train.bilstm_train_forward(self.lstm, self.embedding, text, text_lens,
+                                                      self.lstm.dropout if self.lstm.training else 0.0)
+        else:
+            memory_bank = ops.bilstm(text.long().contiguous(), lens, self.embedding.weight.detach(),
+                                     self._lstm_weights(), self.hidden_size, self.lstm.num_layers, cache=self._lstm_cache)
         assert memory_bank.size() == torch.Size([batch_size, max_text_len, self.bi_hidden_size])
         if not return_last_state:
             return memory_bank
@@ -570,7 +575,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
                 return_last_state=True):
         """Eval mode: the scheduled forward on four streams (forward_plan).  Training mode (_forward_train): the reference's
         training forward in fp32 -- dropout at every site, logits with an autograd graph -- above frozen, eval-mode text
-        encoders (freeze_text_encoders) and precomputed feature maps."""
+        encoders (freeze_text_encoders) or trainable ones (unfreeze_text_encoders), and precomputed feature maps."""
         if self.label_query is None:
             raise RuntimeError("label query missing: pass label_glove=... / opt['label_glove'], call "
                                "set_label_query(), or run from a directory holding %s" % (LABEL_GLOVE_CANDIDATES,))
@@ -593,6 +598,16 @@ class Multi_GCN_Multihead_Att(nn.Module):
         what training mode needs after every model.train() (which puts them back in training mode)."""
         for n in self.TEXT_ENCODERS:
             getattr(self, n).requires_grad_(False).eval()
+        self.text_encoders_trainable = False
+        return self
+
+    def unfreeze_text_encoders(self):
+        """Opt in to training the text encoders (text_features, lstm, embedding): requires_grad_(True) on them; training mode then
+        runs their HIP training forward and backward (dropout as each submodule's own .training says).  freeze_text_encoders()
+        undoes it."""
+        for n in self.TEXT_ENCODERS:
+            getattr(self, n).requires_grad_(True)
+        self.text_encoders_trainable = True
         return self
 
     def _refuse_untrainable(self):
@@ -603,12 +618,23 @@ class Multi_GCN_Multihead_Att(nn.Module):
             raise NotImplementedError("training mode does not implement the is_regu head-difference gradient")
         if not self.bidirectional:
             raise NotImplementedError("the HIP text bank implements the bidirectional LSTM the reference configures")
+        if self.text_encoders_trainable:
+            return
         bad = [n for n in self.TEXT_ENCODERS
                if getattr(self, n).training or any(p_.requires_grad for p_ in getattr(self, n).parameters())]
         if bad:
             raise RuntimeError("Multi_GCN_Multihead_Att training mode: the text encoders (%s) have no backward on the HIP path and "
                                "must be frozen and in eval mode (their dropout would otherwise change the forward): call "
                                "model.freeze_text_encoders() after model.train()" % ", ".join(bad))
+
+    def _text_train(self, text, text_lens):
+        """(text feature [B, D], text memory bank [B, T, 2H]) with autograd (unfreeze_text_encoders): the text GCN's dropout applies
+        iff text_features.training, the BiLSTM's inter-layer dropout iff lstm.training."""
+        tg = self.text_features
+        tf = _train.text_gcn_train_forward(tg, text, tg.dropout.p if tg.training else 0.0)
+        bank = _train.bilstm_train_forward(self.lstm, self.embedding, text, text_lens,
+                                           self.lstm.dropout if self.lstm.training else 0.0)
+        return tf, bank
 
     def _train_maps(self, x, name):
         if not (x.dim() == 4 and x.shape[1] == 2048):
@@ -634,9 +660,12 @@ class Multi_GCN_Multihead_Att(nn.Module):
         (last_dropout_seed)."""
         self._refuse_untrainable()
         B = text.shape[0]
-        with torch.no_grad():
-            tf = self.text_features(text)
-            text_bank = self._text_bank(text, text_lens).f32
+        if self.text_encoders_trainable:
+            tf, text_bank = self._text_train(text, text_lens)
+        else:
+            with torch.no_grad():
+                tf = self.text_features(text)
+                text_bank = self._text_bank(text, text_lens).f32
         mask = text_mask.float().contiguous()
         feat, bank = {}, {}
         for tag, trunk_in, inp, A, lin, att, l5, xl in (

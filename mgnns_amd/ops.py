@@ -1781,3 +1781,180 @@ def dropout_mask(seed, site, rate, shape, device):
     _launch("mgnns_dropout_mask", ("mgnns_dropout_mask",), L.mgnns_dropout_mask, _seed64(seed), int(site), _chk_rate(rate),
             keep.numel(), _p(keep), _stream())
     return keep.bool()
+
+
+# ---- training mode of the text encoders (csrc/text_train.hip; fp32, GPU only) ---------------------------------------------
+DROP_LSTM, DROP_TEXT_GCN = 5, 6            # the BiLSTM's inter-layer dropout [B, T, 2H], the text GCN's dropout [B, D]
+
+
+def bilstm_train(tok, lens, emb_table, weights, hidden, num_layers, seed, rate):
+    """Training forward of the text bank (mgnns_bilstm_train_fwd): bilstm(recurrence="f32") with dropout(rate) at DROP_LSTM on layer
+    0's output before layer 1 (bit for bit the eval bank at rate 0) -> (bank [B, T, 2*hidden], saved for bilstm_train_backward)."""
+    import ctypes
+    _chk(tok, "text", torch.int64, 2)
+    _chk(lens, "text_lens", torch.int64, 1)
+    _chk(emb_table, "embedding.weight", ndim=2)
+    B, T = tok.shape
+    if lens.shape[0] != B:
+        raise ValueError("text_lens has %d entries for batch %d" % (lens.shape[0], B))
+    if len(weights) != 2 * num_layers:
+        raise ValueError("need %d (layer, direction) weight tuples" % (2 * num_layers))
+    for t in (w for tup in weights for w in tup):
+        _chk(t, "lstm weight")
+    rate = _chk_rate(rate)
+    dev = tok.device
+    rows = max(int(lens.clamp(0, T).sum().item()), 1)      # packed rows (one sync: the saved tensors are sized by it)
+    cat = _lstm_cat(weights, num_layers, None)
+    arr = lambda ptrs: (ctypes.c_void_p * len(ptrs))(*ptrs)
+    G = 4 * hidden
+    meta = torch.empty(B + 1 + B + 8 + 2 * B * T, dtype=torch.int32, device=dev)
+    gates = torch.empty(num_layers, 2, rows, G, device=dev, dtype=torch.float32)
+    cells = torch.empty(num_layers, 2, rows, hidden, device=dev, dtype=torch.float32)
+    mid = torch.empty(B, T, 2 * hidden, device=dev, dtype=torch.float32) if num_layers > 1 else None
+    mid_d = torch.empty_like(mid) if num_layers > 1 else None
+    out = torch.empty(B, T, 2 * hidden, device=dev, dtype=torch.float32)
+    L = _lib.lib()
+    nbytes = L.mgnns_bilstm_train_workspace_bytes(B, T, hidden)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _launch("mgnns_bilstm_train_fwd", ("mgnns_bilstm_train_fwd",), L.mgnns_bilstm_train_fwd, _p(tok), _p(lens), B, T, _p(emb_table),
+            emb_table.shape[0], emb_table.shape[1], hidden, num_layers, arr([c[0].data_ptr() for c in cat]),
+            arr([c[1].data_ptr() for c in cat]), arr([w[1].data_ptr() for w in weights]), arr([w[3].data_ptr() for w in weights]),
+            _seed64(seed), rate, _p(meta), rows, _p(gates), _p(cells), _p(mid), _p(mid_d), _p(out), _p(ws), ws.numel(), _stream())
+    saved = dict(tok=tok, lens=lens, B=B, T=T, rows=rows, n_rows=int(lens.clamp(0, T).sum().item()), hidden=hidden,
+                 num_layers=num_layers, seed=seed, rate=rate, meta=meta, gates=gates, cells=cells, mid=mid, mid_d=mid_d, out=out,
+                 cat=cat)
+    return out, saved
+
+
+def _bilstm_meta(s):
+    B, T = s["B"], s["T"]
+    m = s["meta"]
+    return m[B + 1 + B + 8: B + 1 + B + 8 + B * T], m[B + 1 + B + 8 + B * T:]      # pack_tok, pack_pos
+
+
+def gather_rows(src, idx, M):
+    """dst [M, K] = src[idx[:M]] (mgnns_gather_rows; idx int32)."""
+    _chk(src, "src", ndim=2)
+    _chk(idx, "idx", torch.int32)
+    dst = torch.empty(M, src.shape[1], device=src.device, dtype=torch.float32)
+    L = _lib.lib()
+    _launch("mgnns_gather_rows", ("mgnns_gather_rows",), L.mgnns_gather_rows, _p(src), src.shape[0], src.shape[1], _p(idx), M, _p(dst),
+            _stream())
+    return dst
+
+
+def keyed_row_sum(keys, values, n_out, skip_below=0):
+    """out [n_out, D] (zeros where no key lands) = for every key k, the sum of the rows values[r] with keys[r] == k, added in the
+    order of a stable sort of the keys (mgnns_keyed_row_sum): the same inputs give bit-identical sums.  keys < skip_below add nothing
+    (the embedding's padding row, -1 for empty slots)."""
+    values = _chk(values.reshape(values.shape[0], -1), "values")
+    keys = keys.reshape(-1).long()
+    if keys.shape[0] != values.shape[0]:
+        raise ValueError("keyed_row_sum: %d keys for %d rows" % (keys.shape[0], values.shape[0]))
+    D = values.shape[1]
+    out = torch.zeros(n_out, D, device=values.device, dtype=torch.float32)
+    if keys.numel() == 0:
+        return out
+    sk, perm = torch.sort(keys, stable=True)
+    L = _lib.lib()
+    _launch("mgnns_keyed_row_sum", ("mgnns_keyed_row_sum",), L.mgnns_keyed_row_sum, _p(sk.contiguous()), _p(perm.contiguous()), keys.numel(),
+            _p(values), D, values.shape[0], int(skip_below), _p(out), n_out, _stream())
+    return out
+
+
+def bilstm_train_backward(dout, saved, weights, emb_table, need_emb=True):
+    """Backward of bilstm_train from dbank [B, T, 2H] -> (d embedding.weight [V, E] or None (row 0 stays 0), [per (layer, direction):
+    (dW_ih, dW_hh, db_ih, db_hh)]).  Recurrences on the GPU (mgnns_bilstm_train_bwd_rec); weight gradients through wgrad (fixed-order
+    reductions), input gradients as one GEMM per layer; layer 1's input gradient goes back through the DROP_LSTM mask."""
+    s = saved
+    B, T, H, nl, M = s["B"], s["T"], s["hidden"], s["num_layers"], s["n_rows"]
+    G = 4 * H
+    pack_tok, pack_pos = _bilstm_meta(s)
+    L = _lib.lib()
+    grads = [None] * (2 * nl)
+    demb = torch.zeros_like(emb_table) if need_emb else None
+    if M == 0:
+        for li in range(2 * nl):
+            grads[li] = tuple(torch.zeros_like(w) for w in weights[li])
+        return demb, grads
+    dcur = _chk(dout.contiguous(), "dbank")
+    for layer in range(nl - 1, -1, -1):
+        dz = torch.empty(M, 2 * G, device=dout.device, dtype=torch.float32)
+        _launch("mgnns_bilstm_train_bwd_rec", ("mgnns_bilstm_train_bwd_rec",), L.mgnns_bilstm_train_bwd_rec, _p(dcur), _p(s["lens"]), B, T,
+                _p(s["meta"]), s["rows"], _p(s["gates"][layer]), _p(s["cells"][layer]), _p(weights[2 * layer][1]),
+                _p(weights[2 * layer + 1][1]), _p(dz), _stream())
+        hout = s["out"] if layer == nl - 1 else s["mid"]
+        hprev = torch.empty(M, 2 * H, device=dout.device, dtype=torch.float32)
+        _launch("mgnns_bilstm_train_hprev", ("mgnns_bilstm_train_hprev",), L.mgnns_bilstm_train_hprev, _p(hout), _p(s["lens"]), B, T,
+                _p(s["meta"]), M, _p(hprev), _stream())
+        x = gather_rows(emb_table, pack_tok, M) if layer == 0 else gather_rows(s["mid_d"].view(B * T, 2 * H), pack_pos, M)
+        dwih, dbih = wgrad(dz, x)
+        dwhh = wgrad(dz, hprev, bias=False)[0]
+        for d in (0, 1):
+            db = dbih[d * G:(d + 1) * G]
+            grads[2 * layer + d] = (dwih[d * G:(d + 1) * G].contiguous(), dwhh[d * G:(d + 1) * G, d * H:(d + 1) * H].contiguous(),
+                                    db.contiguous(), db.clone())
+        if layer > 0:
+            dx = matmul(dz, s["cat"][layer][0])
+            dprev = torch.zeros(B, T, 2 * H, device=dout.device, dtype=torch.float32)
+            _launch("mgnns_bilstm_train_unpack_drop", ("mgnns_bilstm_train_unpack_drop",), L.mgnns_bilstm_train_unpack_drop, _p(dx),
+                    _p(pack_pos), M, B, T, _seed64(s["seed"]), s["rate"], _p(dprev), _stream())
+            dcur = dprev
+        elif need_emb:
+            dx = matmul(dz, s["cat"][0][0])
+            demb = keyed_row_sum(pack_tok[:M], dx, emb_table.shape[0], skip_below=1)
+    return demb, grads
+
+
+def textgcn_train(tok, node_hidden, edge_w, pmi_dev, ngram, max_length, seed, rate):
+    """Training forward of the text GCN (mgnns_textgcn_train_fwd): relu(dropout(sum over nodes of the max-aggregated states)) with
+    dropout(rate) at DROP_TEXT_GCN -> (out [B, D], saved for textgcn_train_backward)."""
+    _chk(tok, "doc_ids", torch.int64, 2)
+    _chk(node_hidden, "node_hidden.weight", ndim=2)
+    ew = _chk(edge_w.reshape(-1), "seq_edge_w.weight")
+    rp, col, eid = pmi_dev
+    B, T = tok.shape
+    V, D = node_hidden.shape
+    if rp.shape[0] != V + 1:
+        raise ValueError("PMI map has %d rows, vocabulary has %d" % (rp.shape[0] - 1, V))
+    rate = _chk_rate(rate)
+    Tm = min(T, int(max_length))
+    out = torch.empty(B, D, device=tok.device, dtype=torch.float32)
+    presum = torch.empty(B, D, device=tok.device, dtype=torch.float32)
+    win = torch.empty(B, Tm, D, device=tok.device, dtype=torch.int16)
+    if B:
+        L = _lib.lib()
+        _launch("mgnns_textgcn_train_fwd", ("mgnns_textgcn_train_fwd",), L.mgnns_textgcn_train_fwd, _p(tok), B, T, _p(node_hidden), V, D,
+                _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), int(ngram), int(max_length), _seed64(seed), rate, _p(out), _p(presum),
+                _p(win), _stream())
+    return out, dict(presum=presum, win=win, seed=seed, rate=rate, ngram=int(ngram), max_length=int(max_length))
+
+
+def textgcn_train_backward(dy, tok, node_hidden, edge_w, pmi_dev, saved, need_nodes=True, need_edges=True):
+    """Backward of textgcn_train from dy [B, D] -> (d node_hidden [V, D] or None, d edge weights [n_edge_w] or None): each (node,
+    feature) sends its gradient through its winning in-edge (the tie rule of textgcn_train); per-document partials summed per key by
+    keyed_row_sum."""
+    rp, col, eid = pmi_dev
+    ew = edge_w.reshape(-1)
+    B, T = tok.shape
+    V, D = node_hidden.shape
+    g = saved["ngram"]
+    Tm, W = min(T, saved["max_length"]), 2 * saved["ngram"] + 1
+    dn = torch.zeros(V, D, device=tok.device, dtype=torch.float32) if need_nodes else None
+    de = torch.zeros(ew.shape[0], device=tok.device, dtype=torch.float32) if need_edges else None
+    if B == 0:
+        return dn, de
+    dy = _chk(dy.contiguous(), "dy")
+    R = torch.empty(B, Tm, D, device=tok.device, dtype=torch.float32)
+    keyR = torch.empty(B, Tm, device=tok.device, dtype=torch.int32)
+    Eg = torch.empty(B, Tm, W, device=tok.device, dtype=torch.float32)
+    keyE = torch.empty(B, Tm, W, device=tok.device, dtype=torch.int32)
+    L = _lib.lib()
+    _launch("mgnns_textgcn_train_bwd", ("mgnns_textgcn_train_bwd",), L.mgnns_textgcn_train_bwd, _p(tok), B, T, _p(node_hidden), V, D,
+            _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), g, saved["max_length"], _seed64(saved["seed"]), saved["rate"], _p(dy),
+            _p(saved["presum"]), _p(saved["win"]), _p(R), _p(keyR), _p(Eg), _p(keyE), _stream())
+    if need_nodes:
+        dn = keyed_row_sum(keyR, R.view(B * Tm, D), V)
+    if need_edges:
+        de = keyed_row_sum(keyE, Eg.view(-1, 1), ew.shape[0]).view(-1)
+    return dn, de

@@ -4,7 +4,8 @@
 (node_hidden, seq_edge_w, Linear).  forward() hands the whole batch of token ids to one HIP
 kernel that builds each document's n-gram graph, looks the PMI edge ids up in a CSR map,
 gathers node/edge embeddings and does the max-aggregation + sum read-out + ReLU
-(the reference does this with a Python loop per document and three DGL kernels).
+(the reference does this with a Python loop per document and three DGL kernels).  In training mode the forward
+runs train.TextGCNTrainFunction: dropout before the ReLU, and a HIP backward through each (node, feature)'s winning in-edge.
 """
 import os
 
@@ -50,6 +51,7 @@ class Model(nn.Module):
         self.dropout = nn.Dropout(p=drop_out)
         self.activation = nn.ReLU()
         self.Linear = nn.Linear(hidden_size_node, class_num, bias=True)   # constructed, never applied (TGCN:273)
+        self.last_dropout_seed = None      # training mode: the dropout's seed of the last forward
 
     def word2id(self, word):
         return self.d.get(word, self.d.get('UNK'))
@@ -76,7 +78,9 @@ class Model(nn.Module):
     def forward(self, doc_ids, is_20ng=None):
         """doc_ids [B,T] int64 (0 = PAD) -> relu(sum_nodes(max-aggregated node states)) [B, hidden]."""
         if self.training:
-            raise RuntimeError("Text_GCN.Model: eval-mode forward only on the HIP path; call .eval()")
+            # training mode (Text_GCN.py:255-275): dropout, then ReLU, with gradients to node_hidden and seq_edge_w
+            from .train import text_gcn_train_forward
+            return text_gcn_train_forward(self, doc_ids, self.dropout.p)
         if doc_ids.dim() != 2:
             raise ValueError("doc_ids must be [B,T]")
         doc_ids = doc_ids.long().contiguous()

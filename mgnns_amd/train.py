@@ -253,3 +253,85 @@ def dropout_train_forward(mod, x, site):
     seed = draw_seed()
     mod.last_dropout_seed = seed
     return DropoutFunction.apply(x.contiguous(), seed, site, mod.p)
+
+
+# ---- the text encoders (csrc/text_train.hip) ------------------------------------------------------------------------------
+class BiLSTMTrainFunction(torch.autograd.Function):
+    """bank [B, T, 2H] = the packed 2-layer BiLSTM over the embedded text (ops.bilstm_train) with the inter-layer dropout; gradients
+    to the embedding table (row 0, the padding row, gets none) and the 16 LSTM weights / biases.  Every tensor the backward reads
+    goes through save_for_backward (the bank is an output: kept in ctx it would form a reference cycle and outlive the step)."""
+
+    TENSORS = ("tok", "lens", "meta", "gates", "cells", "mid", "mid_d", "out")
+
+    @staticmethod
+    def forward(ctx, tok, lens, seed, rate, hidden, num_layers, emb, *flat):
+        weights = [tuple(flat[4 * i:4 * i + 4]) for i in range(len(flat) // 4)]
+        bank, saved = ops.bilstm_train(tok, lens, emb, weights, hidden, num_layers, seed, rate)
+        ctx.info = {k: v for k, v in saved.items() if k not in BiLSTMTrainFunction.TENSORS and k != "cat"}
+        ctx.n_flat = len(flat)
+        ctx.save_for_backward(emb, *flat, *[saved[k] for k in BiLSTMTrainFunction.TENSORS], *[t for c in saved["cat"] for t in c])
+        return bank
+
+    @staticmethod
+    def backward(ctx, dbank):
+        st = ctx.saved_tensors
+        nf, nt = ctx.n_flat, len(BiLSTMTrainFunction.TENSORS)
+        emb, flat = st[0], st[1:1 + nf]
+        saved = dict(ctx.info, **dict(zip(BiLSTMTrainFunction.TENSORS, st[1 + nf:1 + nf + nt])))
+        cat = st[1 + nf + nt:]
+        saved["cat"] = [(cat[2 * i], cat[2 * i + 1]) for i in range(len(cat) // 2)]
+        weights = [tuple(flat[4 * i:4 * i + 4]) for i in range(nf // 4)]
+        demb, grads = ops.bilstm_train_backward(dbank, saved, weights, emb, need_emb=ctx.needs_input_grad[6])
+        out = [g for tup in grads for g in tup]
+        out = [g if ctx.needs_input_grad[7 + i] else None for i, g in enumerate(out)]
+        return (None, None, None, None, None, None, demb if ctx.needs_input_grad[6] else None, *out)
+
+
+class TextGCNTrainFunction(torch.autograd.Function):
+    """out [B, D] = relu(dropout(sum over nodes of max over in-edges of w_e h_u)) (ops.textgcn_train); gradients to node_hidden and the
+    edge weights through each (node, feature)'s winning in-edge.  Saved tensors go through save_for_backward."""
+
+    @staticmethod
+    def forward(ctx, tok, pmi_dev, ngram, max_length, seed, rate, node_hidden, edge_w):
+        out, saved = ops.textgcn_train(tok, node_hidden, edge_w, pmi_dev, ngram, max_length, seed, rate)
+        ctx.info = {k: v for k, v in saved.items() if k not in ("presum", "win")}
+        ctx.save_for_backward(tok, node_hidden, edge_w, saved["presum"], saved["win"], *pmi_dev)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        tok, node_hidden, edge_w, presum, win, rp, col, eid = ctx.saved_tensors
+        saved = dict(ctx.info, presum=presum, win=win)
+        dn, de = ops.textgcn_train_backward(dy, tok, node_hidden, edge_w, (rp, col, eid), saved,
+                                            need_nodes=ctx.needs_input_grad[6], need_edges=ctx.needs_input_grad[7])
+        return None, None, None, None, None, None, dn, (de.view_as(edge_w) if de is not None else None)
+
+
+def text_gcn_train_forward(tg, doc_ids, rate):
+    """Text_GCN.Model's forward with autograd: dropout(rate) before the ReLU (rate = tg.dropout.p in training mode, 0 otherwise); one
+    seed per call, kept as tg.last_dropout_seed."""
+    if not doc_ids.is_cuda:
+        raise RuntimeError("doc_ids is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % doc_ids.device)
+    if doc_ids.dim() != 2:
+        raise ValueError("doc_ids must be [B,T]")
+    seed = draw_seed()
+    tg.last_dropout_seed = seed
+    tok = doc_ids.long().contiguous()
+    return TextGCNTrainFunction.apply(tok, tg.edges_matrix.device_arrays(tok.device), tg.ngram, tg.max_length, seed, rate,
+                                      tg.node_hidden.weight, tg.seq_edge_w.weight)
+
+
+def bilstm_train_forward(lstm, embedding, text, text_lens, rate):
+    """The text memory bank with autograd (MODEL:366-398): embedding + packed nn.LSTM `lstm` with dropout(rate) between its layers;
+    one seed per call, kept as lstm.last_dropout_seed."""
+    if not text.is_cuda:
+        raise RuntimeError("text is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % text.device)
+    seed = draw_seed()
+    lstm.last_dropout_seed = seed
+    lens = text_lens.to(device=text.device, dtype=torch.int64).contiguous()
+    flat = []
+    for layer in range(lstm.num_layers):
+        for suffix in ("", "_reverse"):
+            flat += [getattr(lstm, "%s_l%d%s" % (n, layer, suffix)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    return BiLSTMTrainFunction.apply(text.long().contiguous(), lens, seed, rate, lstm.hidden_size, lstm.num_layers, embedding.weight,
+                                     *flat)

@@ -5,7 +5,10 @@ and achieved GB/s, and for context the same layer through plain torch autograd (
 The last line is the whole model (csrc/model_train.hip) at mvsa_multiple_b256 in fp32: the training forward + backward step,
 the image-bank weight-gradient kernel alone with its % of the 155 TF fp32 matrix peak, and plain torch autograd over the same
 formulation.
-Usage: python tools/bench_train.py [--iters N] [--model-only]"""
+--text: the text encoders' training (csrc/text_train.hip) at mvsa_multiple_b256 in fp32 -- the whole-model step with frozen and
+with trainable encoders, each new kernel alone (with algorithmic bytes or FLOPs), and plain torch autograd over the same text
+formulation (nn.LSTM on packed sequences, a scatter-max text GCN).
+Usage: python tools/bench_train.py [--iters N] [--model-only | --text]"""
 import json
 import math
 import os
@@ -216,10 +219,108 @@ def model_case(n):
     return res
 
 
+def text_case(n):
+    import numpy as np
+    from mgnns_amd import harness, synth
+    from mgnns_amd import train as T_
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=cfg.B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV).train().freeze_text_encoders()
+    args = harness.call_args(inp, DEV)
+    B, T = args[0].shape
+    G = torch.randn(B, cfg.NL, device=DEV)
+    res = {"case": "text_%s_fp32" % cfg.name, "B": B, "T": T}
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        torch.autograd.backward(model(*args), G)
+
+    res["model_fwd_bwd_frozen_us"] = timeit(step, n)
+    model.unfreeze_text_encoders()
+    res["model_fwd_bwd_trainable_us"] = timeit(step, n)
+    tok, lens = args[0].long().contiguous(), args[1].to(DEV).long().contiguous()
+    rows = int(lens.clamp(0, T).sum())
+    emb, lstm = model.embedding.weight.detach(), model.lstm
+    ws = [tuple(getattr(lstm, "%s_l%d%s" % (k, l, s)).detach() for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+          for l in range(2) for s in ("", "_reverse")]
+    rate = lstm.dropout
+    bank, saved = ops.bilstm_train(tok, lens, emb, ws, 150, 2, 5, rate)
+    t_fwd = timeit(lambda: ops.bilstm_train(tok, lens, emb, ws, 150, 2, 5, rate), n)
+    t_eval = timeit(lambda: ops.bilstm(tok, lens, emb, ws, 150, 2, recurrence="f32"), n)
+    dbank = torch.randn_like(bank)
+    t_bwd = timeit(lambda: ops.bilstm_train_backward(dbank, saved, ws, emb), n)
+    L = ops._lib.lib()
+    dz = torch.empty(rows, 1200, device=DEV)
+
+    def rec():
+        ops._launch("x", "x", L.mgnns_bilstm_train_bwd_rec, ops._p(dbank), ops._p(lens), B, T, ops._p(saved["meta"]), saved["rows"],
+                    ops._p(saved["gates"][1]), ops._p(saved["cells"][1]), ops._p(ws[2][1]), ops._p(ws[3][1]), ops._p(dz), ops._stream())
+    t_rec = timeit(rec, n)
+    res["bilstm"] = {"rows": rows, "eval_fwd_us": round(t_eval, 1), "train_fwd_us": round(t_fwd, 1), "bwd_us": round(t_bwd, 1),
+                     "bwd_rec_one_layer_us": round(t_rec, 1),
+                     "bwd_rec_MB": round(rows * (600 + 150 + 150 + 1200 + 150) * 4 / 1e6, 1)}
+    tg = model.text_features
+    pmi_dev = tg.edges_matrix.device_arrays(tok.device)
+    nh, ew = tg.node_hidden.weight.detach(), tg.seq_edge_w.weight.detach()
+    out, ts = ops.textgcn_train(tok, nh, ew, pmi_dev, tg.ngram, tg.max_length, 5, tg.dropout.p)
+    dy = torch.randn_like(out)
+    t_tf = timeit(lambda: ops.textgcn_train(tok, nh, ew, pmi_dev, tg.ngram, tg.max_length, 5, tg.dropout.p), n)
+    t_tb = timeit(lambda: ops.textgcn_train_backward(dy, tok, nh, ew, pmi_dev, ts), n)
+    keys = torch.randint(0, nh.shape[0], (rows,), device=DEV)
+    vals = torch.randn(rows, 300, device=DEV)
+    t_ks = timeit(lambda: ops.keyed_row_sum(keys, vals, nh.shape[0]), n)
+    res["text_gcn"] = {"train_fwd_us": round(t_tf, 1), "bwd_us": round(t_tb, 1),
+                       "keyed_sum_rows": rows, "keyed_sum_us": round(t_ks, 1),
+                       "keyed_sum_GB/s": round((rows * 300 * 4 * 2 + nh.numel() * 4) / t_ks / 1e3, 1)}
+    # plain torch autograd over the same formulation
+    tl = torch.nn.LSTM(300, 150, 2, bidirectional=True, batch_first=True, dropout=rate).to(DEV)
+    te = torch.nn.Embedding(emb.shape[0], 300, padding_idx=0).to(DEV)
+    lens_cpu = lens.clamp(min=1).cpu()
+
+    def torch_lstm():
+        x = torch.nn.utils.rnn.pack_padded_sequence(te(tok), lens_cpu, batch_first=True, enforce_sorted=False)
+        o, _ = tl(x)
+        o, _ = torch.nn.utils.rnn.pad_packed_sequence(o, batch_first=True, total_length=T)
+        o.backward(dbank)
+    res["torch_lstm_fwd_bwd_us"] = round(timeit(torch_lstm, n), 1)
+    toks = tok.cpu().numpy()
+    src, dst, eid, doc = [], [], [], []
+    node_base = 0
+    for b in range(B):
+        t = [int(x) for x in toks[b][:tg.max_length] if x != 0]
+        nodes = {}
+        for v in t:
+            nodes.setdefault(v, node_base + len(nodes))
+        for i, u in enumerate(t):
+            for j in range(max(0, i - tg.ngram), min(len(t), i + tg.ngram + 1)):
+                src.append(u); dst.append(nodes[t[j]]); eid.append(tg.edges_matrix[u, t[j]])
+        doc += [b] * len(nodes)
+        node_base += len(nodes)
+    src, dst, eid = (torch.tensor(a, device=DEV, dtype=torch.long) for a in (src, dst, eid))
+    doc = torch.tensor(doc, device=DEV, dtype=torch.long)
+    tnh = tg.node_hidden.weight.detach().clone().requires_grad_()
+    tew = tg.seq_edge_w.weight.detach().clone().requires_grad_()
+
+    def torch_gcn():
+        msg = tew[eid] * tnh[src]
+        h = torch.full((node_base, 300), -float("inf"), device=DEV).scatter_reduce(0, dst[:, None].expand(-1, 300), msg, "amax")
+        s = torch.zeros(B, 300, device=DEV).index_add(0, doc, h)
+        torch.relu(F.dropout(s, tg.dropout.p)).backward(dy)
+    res["torch_textgcn_fwd_bwd_us"] = round(timeit(torch_gcn, n), 1)
+    for k in ("model_fwd_bwd_frozen_us", "model_fwd_bwd_trainable_us"):
+        res[k] = round(res[k], 1)
+    return res
+
+
 def main():
     n = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 20
     if not torch.cuda.is_available():
         raise SystemExit("bench_train: no GPU")
+    if "--text" in sys.argv:
+        print(json.dumps(text_case(n)), flush=True)
+        return
     if "--model-only" not in sys.argv:
         for B, H, L, masked in ((256, 4, 196, False), (256, 4, 100, True)):
             print(json.dumps(case(B, H, L, masked, n)), flush=True)
