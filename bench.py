@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- forward samples/s of the MGNNS hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dtype f32] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dtype f32] [--scaling weak|strong] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,13 +10,19 @@ label attention + 4 stacks of single-query multi-head fusion + classifier) over 
 MVSA-Multiple-shaped batch (configs[2]: B=256, T=100, V=20154, 8 heads, 2 layers), entered at
 the [B,2048,14,14] feature maps, inputs resident in HBM.
 
+A plain run does what the headline needs and nothing else: set-up, the warm-up and timed steps, --dump-outputs, the
+result line.  `--full` adds every other measurement behind the timed steps: the one-forward-at-a-time replay, the
+per-kernel roofline leg, the variants (other precisions, the other attention formulation, smaller batches), the
+configs[4] stress, text-pipeline and CNN-trunk legs, the CPU oracle baseline with its parity figure, and at N>1 the
+scaling the headline is not (--no-variants / --no-cpu-baseline drop legs of a --full run).
+
 N>1: one process per GPU.  `python bench.py --gpus N` WITHOUT a torchrun environment starts the N ranks itself
 (child processes, the parent never touches a GPU) and fails non-zero unless all N join; under torchrun it is one
 rank.  The batch shards over ranks with replicated weights and ONE collective, the RCCL all-gather of the logits,
 inside the timed region (a node of the step's hipGraph when the capture probe passes, else right behind the
-replay).  Both scalings are timed: weak (256 samples per GPU, the headline `value`, "scaling": "weak") and strong
-(configs[3]: the global B=256 batch split 256/N per GPU, reported under "strong_scaling"); `--scaling strong` makes
-the strong figure the headline.  Rank 0 prints ONE JSON line.
+replay).  Two scalings: weak (256 samples per GPU, the headline `value`, "scaling": "weak") and strong (configs[3]:
+the global B=256 batch split 256/N per GPU); `--scaling strong` makes the strong figure the headline.  A --full run
+times both and reports them under "weak_scaling" / "strong_scaling".  Rank 0 prints ONE JSON line.
 
 `--dry-launch` runs the same launcher / rank seeding / barrier + MAX-over-ranks timing / single-line protocol on
 the gloo backend with no GPU and no model (tests/test_bench_launch_cpu.py).
@@ -58,9 +64,12 @@ def parse_args(argv=None):
                          "formulation the north-star's MFMA figure is quoted on); folded = the projections folded away algebraically "
                          "(one read of the memory bank; always reported next to the headline as a variant and in roofline_all); "
                          "auto = folded in bf16 mode, faithful in fp32 mode")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra legs (fp32 parity mode, folded attention, "
-                                                               "configs[4] stress, CNN trunks)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other measurement and check: one-at-a-time replay, roofline leg, variants, "
+                         "stress / text-pipeline / trunk legs, CPU baseline + parity, the other scaling at N>1 (off: the headline only)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the extra legs (fp32 parity mode, folded "
+                                                               "attention, configs[4] stress, CNN trunks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one hipGraph replay per step")
     ap.add_argument("--in-flight", type=int, default=2,
                     help="forwards in flight: captures of the forward replayed round robin without a join between them "
@@ -1089,7 +1098,7 @@ def run_rank(args):
         serial = None
         total = world * b_local
         with torch.no_grad():
-            if pipe is not None:
+            if pipe is not None and args.full:
                 # the same forward one at a time (every replay joins the four streams before the next starts): reported next
                 # to the headline as `serial_replay`
                 ds, _, sreg = regions(step_serial)
@@ -1104,14 +1113,67 @@ def run_rank(args):
                 "value": total / (dt / args.steps), "ms": dt / args.steps * 1e3, "global_batch": total, "regions_ms": reg,
                 "logits": out["logits"], "serial": serial, "in_flight": 1 if pipe is None else len(pipe.items)}
 
-    if os.environ.get("MGNNS_BENCH_ORDER") == "strong_first" and world > 1:      # test hook: order effects
+    if not args.full:                            # the headline's scaling only
+        weak = strong = None
+        if args.scaling == "strong" and world > 1:
+            strong = measure("strong")
+        else:
+            weak = measure("weak")
+    elif os.environ.get("MGNNS_BENCH_ORDER") == "strong_first" and world > 1:      # test hook: order effects
         strong = measure("strong")
         weak = measure("weak")
     else:
         weak = measure("weak")
         strong = measure("strong") if (world > 1 or os.environ.get("MGNNS_BENCH_FORCE_STRONG") == "1") else None
+    head = weak if (args.scaling == "weak" or strong is None) else strong
     if args.dump_outputs and rank == 0:         # the headline's logits of its last timed step (gathered over the ranks)
-        dump_outputs(args.dump_outputs, {"logits": (weak if (args.scaling == "weak" or strong is None) else strong)["logits"]})
+        dump_outputs(args.dump_outputs, {"logits": head["logits"]})
+
+    def headline_line():
+        """The result object of the headline measurement: the contract's keys, the configuration it ran, its timed regions."""
+        line = {
+            "metric": "forward samples/sec at batch 256 (3-channel GCN + fusion)",
+            "value": round(head["value"], 1), "unit": "samples/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(head["ms"], 4),
+            "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None,
+            "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": "%s: B=%d/GPU, T=%d, V=%d, %d heads x %d layers, C=(%d,%d), fp32 feature maps [B,2048,14,14] "
+                                   "resident in HBM"
+                                   % (cfg.name, head["b_local"], cfg.T, cfg.V, cfg.n_head, cfg.stack_num, cfg.C_obj, cfg.C_place),
+                       "global_batch": head["global_batch"], "parallelism": "batch-shard x%d" % world,
+                       "launch": head["launch"],
+                       "attention": attn + (" (K/V and query/output projections composed into the maps either side of the attention: "
+                                            "one read of the memory bank per layer; the reference's explicit formulation is "
+                                            "variants['attention=faithful ...'] of a --full run)" if folded_c16 else ""),
+                       "collective": (None if dist is None else "RCCL all-gather via the C ABI (mgnns_allgather_logits)" if comm is not None
+                                      else "RCCL all-gather via torch.distributed" if backend == "nccl" else backend)},
+        }
+        line["config"]["forwards_in_flight"] = head.get("in_flight", 1)
+        built, tree, same = _lib.source_state()          # which sources the library that ran was built from (mgnns_amd/build.py)
+        line["config"]["sources"] = built if same else "%s (the tree next to it: %s)" % (built, tree)
+        if hasattr(model, "resolve_schedule"):      # segment -> stream schedule of the timed forward (mgnns_amd/model.py::SCHEDULES)
+            line["config"]["schedule"] = model.resolve_schedule((weak or head)["b_local"])
+        if args.dtype == "bf16":
+            line["config"]["lstm_layer0_projection"] = ("rows of the table emb . W_ih^T + b_ih folded once per weight version (weights only)"
+                                                        if ops.LSTM_FOLD_EMBEDDING else "bf16 GEMM on the gathered rows, every forward")
+        # `steps` steps per region; ms_per_step / value = the median of these regions (one warm-up in front of the first)
+        line["timing"] = {"regions": len(head["regions_ms"]), "steps_per_region": args.steps, "statistic": "median region",
+                          "regions_ms_per_step": head["regions_ms"], "min_ms_per_step": min(head["regions_ms"]),
+                          "max_ms_per_step": max(head["regions_ms"]),
+                          "value_is": ("throughput with %d forwards in flight (captures with buffers of their own, no join between "
+                                       "replays); one forward at a time = serial_replay of a --full run" % head.get("in_flight", 1))
+                          if head.get("in_flight", 1) > 1 else "one forward at a time"}
+        return line
+
+    if not args.full:
+        line = headline_line() if rank == 0 else None
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            assert line["n_gpus"] == args.gpus
+            emit(line)
+        return
 
     # ---- roofline leg: every C-ABI launch timed with HIP events on the stream it runs on, over eager single-stream
     #      forwards right after the timed region (events cannot sit inside a graph); rank 0's shard ----
@@ -1310,45 +1372,13 @@ def run_rank(args):
     for v in variants.values():
         del v["_out"]
 
-    head = weak if (args.scaling == "weak" or strong is None) else strong
-    line = {
-        "metric": "forward samples/sec at batch 256 (3-channel GCN + fusion)",
-        "value": round(head["value"], 1), "unit": "samples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(head["ms"], 4),
-        "higher_is_better": True, "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "%s: B=%d/GPU, T=%d, V=%d, %d heads x %d layers, C=(%d,%d), fp32 feature maps [B,2048,14,14] "
-                               "resident in HBM"
-                               % (cfg.name, head["b_local"], cfg.T, cfg.V, cfg.n_head, cfg.stack_num, cfg.C_obj, cfg.C_place),
-                   "global_batch": head["global_batch"], "parallelism": "batch-shard x%d" % world,
-                   "launch": head["launch"],
-                   "attention": attn + (" (K/V and query/output projections composed into the maps either side of the attention: "
-                                        "one read of the memory bank per layer; the reference's explicit formulation is "
-                                        "variants['attention=faithful ...'])" if folded_c16 else ""),
-                   "collective": (None if dist is None else "RCCL all-gather via the C ABI (mgnns_allgather_logits)" if comm is not None
-                                  else "RCCL all-gather via torch.distributed" if backend == "nccl" else backend)},
-        "roofline": roofline, "cpu_baseline": cpu, "max_abs_logit_diff_vs_cpu_oracle": parity,
-    }
-    line["config"]["forwards_in_flight"] = head.get("in_flight", 1)
-    built, tree, same = _lib.source_state()          # which sources the library that ran was built from (mgnns_amd/build.py)
-    line["config"]["sources"] = built if same else "%s (the tree next to it: %s)" % (built, tree)
-    if hasattr(model, "resolve_schedule"):      # segment -> stream schedule of the timed forward (mgnns_amd/model.py::SCHEDULES)
-        line["config"]["schedule"] = model.resolve_schedule(B)
-    if args.dtype == "bf16":
-        line["config"]["lstm_layer0_projection"] = ("rows of the table emb . W_ih^T + b_ih folded once per weight version (weights only)"
-                                                    if ops.LSTM_FOLD_EMBEDDING else "bf16 GEMM on the gathered rows, every forward")
+    line = headline_line()
+    line.update({"roofline": roofline, "cpu_baseline": cpu, "max_abs_logit_diff_vs_cpu_oracle": parity})
     try:            # the placement assumption of the slab / row-range kernels (speed only), measured on this device
         ok, ids = _lib.xcd_probe()
         line["config"]["xcd_map"] = {"blockIdx_and_7_selects_the_xcd": ok, "xcc_id_per_residue": ids}
     except Exception as e:
         line["config"]["xcd_map"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    # `steps` steps per region; ms_per_step / value = the median of these regions (one warm-up in front of the first)
-    line["timing"] = {"regions": len(head["regions_ms"]), "steps_per_region": args.steps, "statistic": "median region",
-                      "regions_ms_per_step": head["regions_ms"], "min_ms_per_step": min(head["regions_ms"]),
-                      "max_ms_per_step": max(head["regions_ms"]),
-                      "value_is": ("throughput with %d forwards in flight (captures with buffers of their own, no join between "
-                                   "replays); one forward at a time = serial_replay" % head.get("in_flight", 1))
-                      if head.get("in_flight", 1) > 1 else "one forward at a time"}
     if head.get("serial"):
         line["serial_replay"] = head["serial"]
         # the same figures as top-level scalars (a parser that keeps only scalar keys keeps them)

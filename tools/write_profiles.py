@@ -64,11 +64,11 @@ def main():
     from mgnns_amd import _lib
     fp = _lib.check_sources("tools/write_profiles.py")
     stamp = "Library sources: fingerprint `%s` (`python -m mgnns_amd.build --fingerprint` on the commit that holds this file).\n\n" % fp
-    cmds = {"bf16": "--steps 20 --warmup 5 --no-cpu-baseline --no-variants",
-            "bf16_serial": "--steps 10 --warmup 3 --no-cpu-baseline --no-variants --no-graph --single-stream",
-            "f32": "--steps 10 --warmup 3 --no-cpu-baseline --no-variants --dtype f32",
-            "folded": "--steps 20 --warmup 5 --no-cpu-baseline --no-variants --attn folded",
-            "bf16x3_serial": "--steps 10 --warmup 3 --no-cpu-baseline --no-variants --no-graph --single-stream --dtype bf16x3 --attn faithful"}
+    cmds = {"bf16": "--full --steps 20 --warmup 5 --no-cpu-baseline --no-variants",
+            "bf16_serial": "--full --steps 10 --warmup 3 --no-cpu-baseline --no-variants --no-graph --single-stream",
+            "f32": "--full --steps 10 --warmup 3 --no-cpu-baseline --no-variants --dtype f32",
+            "folded": "--full --steps 20 --warmup 5 --no-cpu-baseline --no-variants --attn folded",
+            "bf16x3_serial": "--full --steps 10 --warmup 3 --no-cpu-baseline --no-variants --no-graph --single-stream --dtype bf16x3 --attn faithful"}
     for m, args in cmds.items():
         db = os.path.join(GO, "prof_%s_%s" % (tag, m), "%s_%s_results.db" % (tag, m))
         if not os.path.exists(db):
@@ -138,7 +138,7 @@ def main():
                     "kernel_source_sha16": __import__("hashlib").sha256(open(os.path.join(ROOT, "mgnns_amd/csrc/imgbank_bf16.hip"), "rb").read()).hexdigest()[:16]}
         busy = pmc(dbs["SQ_VALU_MFMA_BUSY_CYCLES"], "sq_mha_core_bf16_kernel")
         with open(os.path.join(PR, "%s_pmc_summary.md" % pre), "w") as f:
-            f.write("# rocprofv3 PMC passes, %s (bf16 mode, eager single forwards: `bench.py --steps 3 --warmup 1 --no-cpu-baseline "
+            f.write("# rocprofv3 PMC passes, %s (bf16 mode, eager single forwards: `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "
                     "--no-variants --no-graph`)\n\n" % pre)
             f.write(stamp)
             f.write("One counter per pass (`rocprofv3 --pmc <ctr> --kernel-trace`, tools/pmc.sh). FETCH_SIZE/WRITE_SIZE are in KiB; per "
@@ -151,7 +151,7 @@ def main():
                 hi = sum(busy) / len(busy) if has_packed else half(busy, True)
                 f.write("MFMA pipe: `SQ_VALU_MFMA_BUSY_CYCLES` = %.4e per L=196 launch of sq_mha_core_bf16 (= 256 WG x 8 waves x 2080 MFMA x "
                         "16 cycles: every issued 16x16x32 MFMA, padding included). Divide by 1024 SIMDs x launch time x clock for the pipe "
-                        "occupancy; algorithmic utilisation (61.86 GFLOP / time / 2.5 PF) is what bench.py reports.\n" % hi)
+                        "occupancy; algorithmic utilisation (61.86 GFLOP / time / 2.5 PF) is what bench.py --full reports.\n" % hi)
         # the split-bf16 attention core (bf16x3 mode): its own two passes
         dx = {c: os.path.join(GO, "pmc_%s_x3_%s" % (tag, c), "%s_x3_%s_results.db" % (tag, c)) for c in ("FETCH_SIZE", "WRITE_SIZE")}
         if all(os.path.exists(p) for p in dx.values()):
