@@ -83,7 +83,7 @@ int mgnns_textgcn_fwd(const int64_t* tok, int B, int T,
                       int ngram, int max_length, float* out, mgnns_stream_t stream);
 /* Launch form of mgnns_textgcn_fwd (results agree to fp32 summation order; a test / measurement knob, process wide):
  * 0 = by batch and shape (default): batches of at least 64 documents run ONE launch of the lean kernel (256 threads, 8 KB of LDS,
- *     <= 64 registers, node rows read from L2: it fits beside an image-bank workgroup of the same forward; also MGNNS_TEXTGCN_LEAN),
+ *     <= 64 registers, node rows read from L2: it fits beside an image-bank workgroup of the same forward),
  *     smaller ones one launch of 1024-thread workgroups with the document's node rows in LDS;
  * 1 = always that 1024-thread form, 2 = two launches (documents of <= 24 tokens on 256-thread workgroups, then the others on the
  *     1024-thread form; round 3-4's form for large batches), 3 = always the lean kernel (needs D % 4 == 0). */
@@ -236,7 +236,7 @@ int mgnns_imgbank_pool_fwd(const float* feat, int B, int K, int P,
  * consumes these itself, e.g. mgnns_label_tail_fwd with n_parts = 2).  16 <= P <= 208, P % 4 == 0, N <= 304, K % 64 == 0.
  * Two forms, chosen by the batch: one workgroup per sample streaming the map through an LDS-DMA ring (chip-filling batches),
  * two workgroups per sample (region halves; needs 104 < P <= 200, K % 128 == 0) up to half a chip of samples.
- * mgnns_imgbank_set_form: 0 = by batch (default; also MGNNS_IMGBANK_FORM), 1 = always the stream form, 2 = always the pair form
+ * mgnns_imgbank_set_form: 0 = by batch (default), 1 = always the stream form, 2 = always the pair form
  * where its limits allow -- for tests and measurements; process-wide.
  */
 int mgnns_imgbank_set_form(int form);
@@ -671,10 +671,9 @@ size_t mgnns_gemm_bf16_workspace_bytes(void);
  * its transpose and still leaves the K-contiguous operand the next product needs; the 160 x 256 kernel only: ceil(M / 160) >= 8, N >= 256, K >= 320). */
 int mgnns_gemm_bf16_nt_fwd(const void* A, const void* Bt, int M, int N, int Kp, const float* bias, void* C, int ldc,
                            int c_bf16, int act, void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
-/* Which tile shape mgnns_gemm_bf16_nt_fwd runs (tests and A/B timings; production leaves it alone): -1 the environment
- * (MGNNS_GEMM_160, default 2), 0 round 4's kernels only (256 x 128, 256 x 256), 1 the 160 x 256 kernel whenever the shape fits it,
- * 2 by the launcher's estimate, 3 the 320 x 256 kernel whenever the shape fits it.  100 / 101 / 102: the K-slice width of the 160 x 256 tile --
- * the environment (MGNNS_GEMM160_BK, default 64) / 32 (round 5's kernel: 64-B row segments) / 64 (round 6: whole 128-B lines, half the requests). */
+/* Which tile shape mgnns_gemm_bf16_nt_fwd runs (tests and A/B timings; production leaves it alone; process-wide): 0 round 4's kernels
+ * only (256 x 128, 256 x 256), 1 the 160 x 256 kernel whenever the shape fits it, 2 by the launcher's estimate (the default),
+ * 3 the 320 x 256 kernel whenever the shape fits it; -1 = back to the default. */
 int mgnns_gemm_bf16_set_form(int form);
 /* The launcher's choice for a product, by its estimate (host arithmetic, no device call; n_cu = compute units of the device, 256 on
  * MI355X; with_workspace: the workspace of mgnns_gemm_bf16_workspace_bytes() is passed): 4 = 160 x 256 tiles, 5 = 320 x 256 tiles,

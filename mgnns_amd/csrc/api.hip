@@ -1,6 +1,5 @@
 // Error channel + ABI version of libmgnns_hip.so.
 #include "common.hpp"
-#include <stdlib.h>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -87,20 +86,6 @@ int mg_cu_count() {
         cached[dev] = n;
     }
     return cached[dev];
-}
-
-// integer tuning knob from the environment, read ONCE per process (the launchers sit on the per-forward path)
-int mg_env_int(const char* name, int fallback, int slot) {
-    static std::mutex mu;
-    static bool have[16] = {false};
-    static int val[16] = {0};
-    std::lock_guard<std::mutex> lk(mu);
-    if (!have[slot]) {
-        const char* e = getenv(name);
-        val[slot] = e ? atoi(e) : fallback;
-        have[slot] = true;
-    }
-    return val[slot];
 }
 
 extern "C" const char* mgnns_last_error(void) { return g_err; }

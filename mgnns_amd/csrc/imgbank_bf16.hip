@@ -419,7 +419,7 @@ extern "C" int mgnns_imgbank_pack_weights_bf16(const float* W, int N, int K, voi
 int mg_imgbank_pool_bf16_pairs(const float* feat, int B, int K, int P, const void* Wp, const float* bias, int N, void* bank_bf16, int ld,
                                float* pooled, float* pooled_work, mgnns_stream_t stream);
 
-static int g_imgbank_form = -1;          // -1: not set (MGNNS_IMGBANK_FORM or 0)
+static int g_imgbank_form = 0;           // 0 by batch, 1 stream, 2 pairs
 extern "C" int mgnns_imgbank_set_form(int form) {
     MG_REQUIRE(form >= 0 && form <= 2, "mgnns_imgbank_set_form: form=%d (0 by batch, 1 stream, 2 pairs)", form);
     g_imgbank_form = form;
@@ -439,10 +439,10 @@ extern "C" int mgnns_imgbank_pool_bf16_fwd(const float* feat, int B, int K, int 
                "mgnns_imgbank_pool_bf16_fwd: feat/Wp/bank must be 16-byte aligned");
     if (B == 0) return 0;
     // A workgroup of the stream kernel needs ~95 us for its sample whatever the batch; up to half a chip of samples the
-    // two-workgroups-per-sample form (half the chain per workgroup) is the faster one.  MGNNS_IMGBANK_FORM=1 / 2 forces one.
+    // two-workgroups-per-sample form (half the chain per workgroup) is the faster one.  mgnns_imgbank_set_form(1 / 2) forces one.
     const int n_cu = mg_cu_count();
     if (n_cu <= 0) return MGNNS_ERR_LAUNCH;
-    const int form = g_imgbank_form >= 0 ? g_imgbank_form : mg_env_int("MGNNS_IMGBANK_FORM", 0, 3);
+    const int form = g_imgbank_form;
     const bool pairs_ok = K % 128 == 0 && P > 104 && P <= 200;
     if (pairs_ok && (form == 2 || (form == 0 && 2 * B <= n_cu)))
         return mg_imgbank_pool_bf16_pairs(feat, B, K, P, Wp, bias, N, bank_bf16, ld, pooled, pooled_work, stream);

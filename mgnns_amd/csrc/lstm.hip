@@ -760,10 +760,8 @@ static int bilstm_impl(bool bf16_rec, const void* prepacked, const int64_t* tok,
         const int n_cu = mg_cu_count();
         if (n_cu <= 0) return MGNNS_ERR_LAUNCH;
         // default: half of the CUs (LPT over the length-sorted chains keeps the makespan at ~the longest chain as long
-        // as total steps / workgroups stays below it); MGNNS_LSTM_GRID overrides (bench.py decided the default)
+        // as total steps / workgroups stays below it; bench.py decided it)
         int cap = n_cu / 2;
-        if (const int e = mg_env_int("MGNNS_LSTM_GRID", 0, 0)) cap = e;
-        if (cap > n_cu) cap = n_cu;
         cap &= ~1;
         if (cap < 2) cap = 2;
         if (grid_rec > cap) grid_rec = cap;

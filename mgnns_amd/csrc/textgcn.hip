@@ -364,21 +364,21 @@ extern "C" int mgnns_textgcn_fwd(const int64_t* tok, int B, int T, const float* 
     const int vec = (D % 4 == 0) && mg_aligned16(node_hidden);
     hipStream_t st = (hipStream_t)stream;
     // short documents four to a CU, then the long ones (see the kernel's comment); one launch for small batches, short rows or
-    // shapes whose 256-thread form does not fit (MGNNS_TEXTGCN_SPLIT=0: always one launch)
+    // shapes whose 256-thread form does not fit
     int Cs = TG_SHORT_THREADS / D4;
     Cs = Cs > TG_MAX_CHUNKS ? TG_MAX_CHUNKS : Cs;
     const size_t lds_s = lds_of(TG_SHORT_CAP, Cs);
     const int form = g_textgcn_form;
     const bool split_ok = Tm > TG_SHORT_CAP && Cs >= 1 && lds_s <= 40 * 1024;
-    const bool split = form == 2 ? split_ok : (form == 0 && B >= 64 && split_ok && mg_env_int("MGNNS_TEXTGCN_SPLIT", 1, 7) != 0);
+    const bool split = form == 2 ? split_ok : (form == 0 && B >= 64 && split_ok);
     // large batches (the forward of a B >= 64 batch runs the text GCN next to the image-bank kernels): ONE launch of the LEAN kernel,
     // every document -- the 256-thread short form's 33 KB of LDS does not fit beside a bank workgroup either (12 KB are left), and
-    // its launch sat in front of the long documents' in the stream.  MGNNS_TEXTGCN_LEAN=0 or a shape it does not take (D % 4,
-    // alignment, a band beyond 12 KB): the two-launch form
+    // its launch sat in front of the long documents' in the stream.  A shape it does not take (D % 4, alignment, a band beyond
+    // 12 KB): the two-launch form
     const size_t lds_lean = ((size_t)Cs * Dp + (size_t)Tm * W) * sizeof(float) + (3 * (size_t)Tm + 4) * sizeof(int);
     // (the lean kernel addresses node rows with 32-bit buffer offsets: tables of 2 GiB and more take the 64-bit forms)
     const bool lean_ok = Cs >= 1 && vec && D % 4 == 0 && lds_lean <= 12 * 1024 && (size_t)V * D * 4 < ((size_t)1 << 31);
-    const bool lean = form == 3 ? lean_ok : (form == 0 && B >= 64 && lean_ok && mg_env_int("MGNNS_TEXTGCN_LEAN", 1, 8) != 0);
+    const bool lean = form == 3 ? lean_ok : (form == 0 && B >= 64 && lean_ok);
 #define TG_ARGS(Tn_, C_, mode_, lds_) tok, B, T, Tm, node_hidden, V, D, edge_w, n_edge_w, pmi_row_ptr, pmi_col, pmi_eid, ngram, out, vec, C_, Tn_, mode_, TG_SHORT_CAP, lds_, st
 #define TG_LAUNCH(GT_)                                                                                     \
     {                                                                                                      \

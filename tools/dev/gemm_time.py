@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Dense bf16 GEMM of configs[4] ([n, n] adjacency x [n, F]), cache-cold rotation, hipGraph replays: us and fraction of 2.5 PF.
-    python tools/dev/gemm_time.py [F ...]      MGNNS_GEMM_TILE=128 selects the 256 x 128 kernel; every F is timed with the 160 x 256
-    kernel off / forced / chosen by the launcher's estimate (ops.gemm_bf16_set_form 0 / 1 / 2)"""
+    python tools/dev/gemm_time.py [F ...]      every F is timed with round 4's kernels only / the 160 x 256 kernel forced / the
+    320 x 256 kernel forced / the launcher's estimate (ops.gemm_bf16_set_form 0 / 1 / 3 / 2)"""
 import os
 import statistics
 import sys
