@@ -427,7 +427,8 @@ int mgnns_sq_mha_folded_bf16_fwd(const float* U, const void* bank_bf16, const fl
  * o [B, HK] (HK = n_head*d_v), q [B, 300] (the layer's query = the residual), out [B, 300], qh_next [B, HK_next].
  * Every weight is passed PRE-PACKED by mgnns_pack_weight_f32 (MFMA-fragment-major fp32, one 16-B load = four
  * k-steps): fc [300, HK], w_1 / w_2 [300, 300] (Conv1d k=1 weight viewed 2-D), w_qs' [HK_next, 300].
- * wq_next_wp == NULL skips the last step.  Exact fp32.  d_model == 300.
+ * wq_next_wp == NULL skips the last step.  Exact fp32.  d_model == 300; HK a multiple of 4, <= 1888 (16 rows of o and the two
+ * activation tiles share the 160 KiB of LDS); HK_next any positive width.
  */
 size_t mgnns_packed_f32_weight_bytes(int N, int K);
 int mgnns_pack_weight_f32(const float* W, int N, int K, float* Wp, mgnns_stream_t stream);

@@ -339,10 +339,10 @@ extern "C" size_t mgnns_gemm_workspace_bytes(void) { return (size_t)16 << 20; } 
 extern "C" int mgnns_linear_fwd(const float* X, int M, int K, const float* W, const float* bias, int N,
                                 const float* residual, float* Y, int act, void* workspace, size_t workspace_bytes,
                                 mgnns_stream_t stream) {
-    MG_REQUIRE(X && W && Y, "mgnns_linear_fwd: null pointer");
     MG_REQUIRE(M >= 0 && K > 0 && N > 0, "mgnns_linear_fwd: bad dims M=%d K=%d N=%d", M, K, N);
     MG_REQUIRE(act >= 0 && act <= 2, "mgnns_linear_fwd: unknown activation %d", act);
-    if (M == 0) return 0;
+    if (M == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(X && W && Y, "mgnns_linear_fwd: null pointer");
     launch_gemm<false>(X, M, K, W, N, bias, residual, Y, N, act, nullptr, nullptr, reinterpret_cast<float*>(workspace),
                        workspace ? workspace_bytes / sizeof(float) : 0, (hipStream_t)stream);
     MG_CHECK_LAUNCH("mgnns_linear_fwd");
@@ -351,10 +351,10 @@ extern "C" int mgnns_linear_fwd(const float* X, int M, int K, const float* W, co
 
 extern "C" int mgnns_matmul_fwd(const float* X, int M, int K, const float* W, int N, float* Y, int act, void* workspace,
                                 size_t workspace_bytes, mgnns_stream_t stream) {
-    MG_REQUIRE(X && W && Y, "mgnns_matmul_fwd: null pointer");
     MG_REQUIRE(M >= 0 && K > 0 && N > 0, "mgnns_matmul_fwd: bad dims M=%d K=%d N=%d", M, K, N);
     MG_REQUIRE(act >= 0 && act <= 2, "mgnns_matmul_fwd: unknown activation %d", act);
-    if (M == 0) return 0;
+    if (M == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(X && W && Y, "mgnns_matmul_fwd: null pointer");
     launch_gemm<true>(X, M, K, W, N, nullptr, nullptr, Y, N, act, nullptr, nullptr, reinterpret_cast<float*>(workspace),
                       workspace ? workspace_bytes / sizeof(float) : 0, (hipStream_t)stream);
     MG_CHECK_LAUNCH("mgnns_matmul_fwd");

@@ -139,13 +139,13 @@ __global__ __launch_bounds__(NTHR) void imgbank_pool_kernel(const float* __restr
 extern "C" int mgnns_imgbank_pool_fwd(const float* feat, int B, int K, int P, const float* Wt, int ldw,
                                       const float* bias, int N, float* bank, float* pooled,
                                       mgnns_stream_t stream) {
-    MG_REQUIRE(feat && Wt && bank, "mgnns_imgbank_pool_fwd: null pointer");
     MG_REQUIRE(B >= 0 && K > 0 && K % BK == 0, "mgnns_imgbank_pool_fwd: K=%d must be a positive multiple of %d", K, BK);
     MG_REQUIRE(P > 0 && P <= LDA && P % 4 == 0, "mgnns_imgbank_pool_fwd: P=%d unsupported (multiple of 4, <= %d)", P, LDA);
     MG_REQUIRE(N > 0 && N <= LDB, "mgnns_imgbank_pool_fwd: N=%d unsupported (<= %d)", N, LDB);
     MG_REQUIRE(ldw >= LDB && ldw % 4 == 0, "mgnns_imgbank_pool_fwd: ldw=%d must be >= %d and a multiple of 4", ldw, LDB);
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(feat && Wt && bank, "mgnns_imgbank_pool_fwd: null pointer");
     MG_REQUIRE(mg_aligned16(feat) && mg_aligned16(Wt), "mgnns_imgbank_pool_fwd: feat/Wt must be 16-byte aligned");
-    if (B == 0) return 0;
     hipLaunchKernelGGL(imgbank_pool_kernel, dim3(B), dim3(NTHR), 0, (hipStream_t)stream, feat, K, P, Wt, ldw, bias, N,
                        bank, pooled);
     MG_CHECK_LAUNCH("mgnns_imgbank_pool_fwd");

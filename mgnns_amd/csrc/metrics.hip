@@ -43,10 +43,10 @@ __global__ __launch_bounds__(256) void softmax_argmax_kernel(const float* __rest
 
 extern "C" int mgnns_softmax_argmax_fwd(const float* logits, int B, int NL, float* probs, int32_t* pred,
                                         const int64_t* target, int32_t* confusion, mgnns_stream_t stream) {
-    MG_REQUIRE(logits, "mgnns_softmax_argmax_fwd: null logits");
     MG_REQUIRE(B >= 0 && NL > 0 && NL <= MAXNL, "mgnns_softmax_argmax_fwd: NL=%d unsupported (1..%d)", NL, MAXNL);
-    MG_REQUIRE(!confusion || target, "mgnns_softmax_argmax_fwd: a confusion matrix needs the targets");
-    if (B == 0) return 0;
+    MG_REQUIRE(!confusion || target || B == 0, "mgnns_softmax_argmax_fwd: a confusion matrix needs the targets");
+    if (B == 0) return 0;                  // an empty batch has no storage: its data pointers are null
+    MG_REQUIRE(logits, "mgnns_softmax_argmax_fwd: null logits");
     hipLaunchKernelGGL(softmax_argmax_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, B, NL, probs,
                        pred, target, confusion);
     MG_CHECK_LAUNCH("mgnns_softmax_argmax_fwd");

@@ -123,6 +123,8 @@ __global__ __launch_bounds__(NTHR) void mha_tail_kernel(const float* __restrict_
     // ---- stage o rows (zero beyond B), zero the pads the k-loops may touch: 16-B loads, all in flight first -------------
     {
         const int hk4 = HK >> 2;                                   // HK % 4 == 0 (checked by the launcher)
+        // sized for HK = 2048; mgnns_mha_tail_fwd takes HK <= 1888 (what the LDS holds), the iterations beyond ROWS * hk4 are
+        // predicated off.  Kept at 2048 so that the unrolled code of the shapes in use stays as it is.
         constexpr int MAXIT = (ROWS * (2048 / 4) + NTHR - 1) / NTHR;
         f32x4 v[MAXIT];
 #pragma unroll
@@ -237,12 +239,15 @@ extern "C" int mgnns_mha_tail_fwd(const float* o, int HK, const float* q, int B,
                                   const float* ln2_gamma, const float* ln2_beta, float eps, float* out,
                                   const float* wq_next_wp, const float* bq_next, int HK_next, float* qh_next,
                                   mgnns_stream_t stream) {
+    MG_REQUIRE(d_model == D, "mgnns_mha_tail_fwd: d_model=%d unsupported (300 only)", d_model);
+    // 16 rows of o (row stride HK rounded up to 32, + 2) and the two 300-wide activation tiles share the 160 KiB of LDS: 1888 is
+    // the widest o that fits (the bound used to read 2048, which the LDS check below then refused)
+    MG_REQUIRE(HK > 0 && HK % 4 == 0 && HK <= 1888, "mgnns_mha_tail_fwd: n_head*d_v=%d unsupported (multiple of 4, <= 1888)", HK);
+    MG_REQUIRE(!wq_next_wp || HK_next > 0, "mgnns_mha_tail_fwd: next-layer projection needs qh_next and HK_next");
+    if (B <= 0) return 0;                  // an empty batch has no storage: o, q, out and qh_next are null
     MG_REQUIRE(o && q && fc_wp && fc_b && ln1_gamma && ln1_beta && w1_wp && b1 && w2_wp && b2 && ln2_gamma && ln2_beta && out,
                "mgnns_mha_tail_fwd: null pointer");
-    MG_REQUIRE(d_model == D, "mgnns_mha_tail_fwd: d_model=%d unsupported (300 only)", d_model);
-    MG_REQUIRE(HK > 0 && HK % 4 == 0 && HK <= 2048, "mgnns_mha_tail_fwd: n_head*d_v=%d unsupported (multiple of 4, <= 2048)", HK);
-    MG_REQUIRE(!wq_next_wp || (qh_next && HK_next > 0), "mgnns_mha_tail_fwd: next-layer projection needs qh_next and HK_next");
-    if (B <= 0) return 0;
+    MG_REQUIRE(!wq_next_wp || qh_next, "mgnns_mha_tail_fwd: next-layer projection needs qh_next and HK_next");
     const int so = HK + 2 + ((32 - (HK % 32)) % 32);
     const size_t lds = ((size_t)ROWS * so + 2 * (size_t)ROWS * SD) * sizeof(float);
     MG_REQUIRE(lds <= 160 * 1024, "mgnns_mha_tail_fwd: needs %zu B of LDS", lds);

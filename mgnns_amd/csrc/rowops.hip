@@ -257,9 +257,9 @@ __global__ __launch_bounds__(256) void head_diff_kernel(const float* __restrict_
 }
 
 extern "C" int mgnns_head_diff_fwd(const float* o, int B, int H, int dv, float* out, mgnns_stream_t stream) {
-    MG_REQUIRE(o && out, "mgnns_head_diff_fwd: null pointer");
     MG_REQUIRE(B >= 0 && H > 0 && H <= 16 && dv > 0, "mgnns_head_diff_fwd: bad dims B=%d n_head=%d (<= 16) d_v=%d", B, H, dv);
-    if (B == 0) return 0;
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(o && out, "mgnns_head_diff_fwd: null pointer");
     hipLaunchKernelGGL(head_diff_kernel<16>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, o, B, H, dv, out);
     MG_CHECK_LAUNCH("mgnns_head_diff_fwd");
     return 0;
@@ -267,9 +267,9 @@ extern "C" int mgnns_head_diff_fwd(const float* o, int B, int H, int dv, float* 
 
 extern "C" int mgnns_embedding_fwd(const int64_t* idx, int64_t n, const float* table, int V, int D,
                                    float* out, mgnns_stream_t stream) {
-    MG_REQUIRE(idx && table && out, "mgnns_embedding_fwd: null pointer");
     MG_REQUIRE(n >= 0 && V > 0 && D > 0, "mgnns_embedding_fwd: bad dims n=%lld V=%d D=%d", (long long)n, V, D);
-    if (n == 0) return 0;
+    if (n == 0) return 0;                  // no indices, no storage: the pointers are null
+    MG_REQUIRE(idx && table && out, "mgnns_embedding_fwd: null pointer");
     const int vec = (D % 4 == 0) && mg_aligned16(table) && mg_aligned16(out);
     int64_t blocks = (n + 3) / 4;
     if (blocks > 8192) blocks = 8192;
@@ -281,9 +281,9 @@ extern "C" int mgnns_embedding_fwd(const int64_t* idx, int64_t n, const float* t
 
 extern "C" int mgnns_layernorm_fwd(const float* x, int rows, int D, const float* gamma, const float* beta,
                                    float eps, float* y, mgnns_stream_t stream) {
-    MG_REQUIRE(x && gamma && beta && y, "mgnns_layernorm_fwd: null pointer");
     MG_REQUIRE(rows >= 0 && D > 1 && D <= 1024, "mgnns_layernorm_fwd: D=%d out of range (2..1024)", D);
-    if (rows == 0) return 0;
+    if (rows == 0) return 0;               // no rows, no storage: the pointers are null
+    MG_REQUIRE(x && gamma && beta && y, "mgnns_layernorm_fwd: null pointer");
     dim3 grid((rows + 3) / 4);
     if (D <= 320)
         hipLaunchKernelGGL(layernorm_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, x, rows, D, gamma, beta, eps, y);
@@ -295,10 +295,10 @@ extern "C" int mgnns_layernorm_fwd(const float* x, int rows, int D, const float*
 
 extern "C" int mgnns_label_attn_core_masked_fwd(const float* Q, const float* K, const float* V, const unsigned char* mask,
                                                 int B, int NLQ, int n_heads, int dh, float* x, mgnns_stream_t stream) {
-    MG_REQUIRE(Q && K && V && x, "mgnns_label_attn_core_fwd: null pointer");
     MG_REQUIRE(B >= 0 && NLQ > 0 && n_heads > 0 && dh > 0 && dh <= 64,
                "mgnns_label_attn_core_fwd: bad dims B=%d NLQ=%d heads=%d dh=%d (dh<=64)", B, NLQ, n_heads, dh);
-    if (B == 0) return 0;
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(Q && K && V && x, "mgnns_label_attn_core_fwd: null pointer");
     const int64_t total = (int64_t)B * NLQ * n_heads;
     hipLaunchKernelGGL(label_attn_core_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        Q, K, V, B, NLQ, n_heads, dh, 1.0f / sqrtf((float)dh), x, mask);

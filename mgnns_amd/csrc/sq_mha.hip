@@ -218,13 +218,13 @@ __global__ __launch_bounds__(256) void sq_mha_core_kernel(const float* __restric
 extern "C" int mgnns_sq_mha_core_fwd(const float* qh, const float* bank, const float* mask, int B, int L, int D,
                                      int H, int dk, const float* Wk, const float* bk, const float* Wv,
                                      const float* bv, float* o, float* attn, mgnns_stream_t stream) {
-    MG_REQUIRE(qh && bank && Wk && Wv && o, "mgnns_sq_mha_core_fwd: null pointer");
     MG_REQUIRE(dk == DK, "mgnns_sq_mha_core_fwd: d_kv=%d unsupported (128 only)", dk);
     MG_REQUIRE(B >= 0 && H > 0 && L > 0 && L <= LMAX, "mgnns_sq_mha_core_fwd: L=%d unsupported (1..%d)", L, LMAX);
     MG_REQUIRE(D > 0 && D % 4 == 0 && D <= 320, "mgnns_sq_mha_core_fwd: D=%d unsupported (multiple of 4, <= 320)", D);
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(qh && bank && Wk && Wv && o, "mgnns_sq_mha_core_fwd: null pointer");
     MG_REQUIRE(mg_aligned16(bank) && mg_aligned16(Wk) && mg_aligned16(Wv),
                "mgnns_sq_mha_core_fwd: bank/Wk/Wv must be 16-byte aligned");
-    if (B == 0) return 0;
     const float temp = (float)sqrt((double)dk);      // np.power(d_k, 0.5), submodules.py:31
     hipLaunchKernelGGL(sq_mha_core_kernel, dim3(B * H), dim3(256), 0, (hipStream_t)stream, qh, bank, mask, B, L, D, H,
                        Wk, bk, Wv, bv, temp, o, attn);

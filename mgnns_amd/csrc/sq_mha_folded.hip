@@ -229,17 +229,17 @@ extern "C" int mgnns_sq_mha_folded_fwd(const float* qh, const void* bank, int ba
                                        const float* mask, int B, int L, int D, int H, int dk, const float* Wk,
                                        const float* Wv, const float* bv, void* workspace, size_t workspace_bytes,
                                        float* o, float* attn, mgnns_stream_t stream) {
-    MG_REQUIRE(qh && bank && Wk && Wv && o && workspace, "mgnns_sq_mha_folded_fwd: null pointer");
     MG_REQUIRE(B >= 0 && L > 0 && L <= MAXL, "mgnns_sq_mha_folded_fwd: need 0 < L <= %d (L=%d)", MAXL, L);
     MG_REQUIRE(D > 0 && D <= FD && D % 4 == 0, "mgnns_sq_mha_folded_fwd: need D <= %d, D %% 4 == 0 (D=%d)", FD, D);
     MG_REQUIRE(H > 0 && H <= MAXH && dk > 0 && dk % 4 == 0, "mgnns_sq_mha_folded_fwd: need H <= %d, dk %% 4 == 0 (H=%d dk=%d)",
                MAXH, H, dk);
     MG_REQUIRE(bank_is_bf16 ? (ld_bank >= D && ld_bank % 4 == 0 && ld_bank <= FD) : ld_bank == D,
                "mgnns_sq_mha_folded_fwd: bad bank row stride %d (D=%d, bf16=%d)", ld_bank, D, bank_is_bf16);
-    MG_REQUIRE(mg_aligned16(bank) && mg_aligned16(workspace), "mgnns_sq_mha_folded_fwd: bank/workspace must be 16-byte aligned");
     MG_REQUIRE(workspace_bytes >= mgnns_sq_mha_folded_workspace_bytes(B, D, H),
                "mgnns_sq_mha_folded_fwd: workspace too small (%zu bytes)", workspace_bytes);
-    if (B == 0) return 0;
+    if (B == 0) return 0;                  // an empty batch has no storage: its data pointers are null
+    MG_REQUIRE(qh && bank && Wk && Wv && o && workspace, "mgnns_sq_mha_folded_fwd: null pointer");
+    MG_REQUIRE(mg_aligned16(bank) && mg_aligned16(workspace), "mgnns_sq_mha_folded_fwd: bank/workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     float* Uw = reinterpret_cast<float*>(workspace);           // [H][B][D]
     float* Cw = Uw + (size_t)H * B * D;                        // [H][B][D]
