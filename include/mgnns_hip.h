@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 22
+#define MGNNS_ABI_VERSION 23
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -579,6 +579,16 @@ int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float
  * map X [B, K, P] in its native layout: dW[N, K] = sum_{b,p} dbank[b,p,:] (x) X[b,:,p], db[N] (written).  N <= 320.  Exact-f32
  * MFMA, the (b, p) reduction split into slabs combined in a fixed order.  workspace:
  * mgnns_imgbank_wgrad_workspace_bytes(B, K, P, N) bytes.  B = 0: dW and db are zeroed, X and dbank may be NULL.
+ * mgnns_map_argmax: arg[b, k] (int32, written) = the FIRST p at which row X[b, k, :] of a feature map X [B, K, P] attains its
+ * maximum -- where torch's max_pool2d backward sends the gradient of pooled[b, k] = max_p X[b, k, p] (a tie, e.g. a channel that
+ * is zero over a whole image after the ReLU, goes to the smallest index).  NaN in X is not supported.  B = 0: nothing is launched,
+ * X and arg may be NULL.
+ * mgnns_imgbank_dgrad: gradient of the loss with respect to the feature map X [B, K, P] of an image memory bank:
+ * dX[b,k,p] = sum_o W[o,k] dbank[b,p,o] + (p == arg[b,k] ? dpooled[b,k] : 0), written in full, from dbank [B, P, N], the
+ * nn.Linear weight W [N, K], and the max-pool's gradient dpooled [B, K] with arg [B, K] from mgnns_map_argmax (entries outside
+ * [0, P) add nothing).  dpooled and arg are both NULL (no pooled term) or both given; dbank may be NULL (the pooled term alone; W
+ * is then not read), but not dbank and dpooled both.  N <= 320.  Exact-f32 MFMA; the o reduction runs inside one workgroup in a
+ * fixed order, no workspace.  B = 0: nothing is launched, the tensors may be NULL.
  * mgnns_label_attn_train_fwd: the label attention between its projections with dropout: Q [NLQ, H*dh], K = w_k(x), V = w_v(x)
  * [B, H*dh] -> x [B, NLQ, H*dh] = dropout(softmax_dh(Q K / sqrt(dh))) V, and for the backward P (softmax before dropout) and
  * keep (bytes), both [B, NLQ, H*dh].  dh <= 64.
@@ -593,6 +603,9 @@ int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float
 size_t mgnns_imgbank_wgrad_workspace_bytes(int B, int K, int P, int N);
 int mgnns_imgbank_wgrad(const float* X, const float* dbank, int B, int K, int P, int N, float* dW, float* db, void* workspace,
                         size_t workspace_bytes, mgnns_stream_t stream);
+int mgnns_map_argmax(const float* X, int B, int K, int P, int32_t* arg, mgnns_stream_t stream);
+int mgnns_imgbank_dgrad(const float* dbank, const float* W, const float* dpooled, const int32_t* arg, int B, int K, int P, int N,
+                        float* dX, mgnns_stream_t stream);
 int mgnns_label_attn_train_fwd(const float* Q, const float* K, const float* V, int B, int NLQ, int H, int dh, uint64_t seed,
                                float rate, float* x, float* P, uint8_t* keep, mgnns_stream_t stream);
 size_t mgnns_label_attn_train_bwd_workspace_bytes(int B, int NLQ, int H, int dh);

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _c = ctypes
 _P = _c.c_void_p
@@ -98,6 +98,8 @@ SIGNATURES = {
     "mgnns_drop_res_ln_bwd": [_P, _P, _P, _P, _P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
     "mgnns_train_eltwise": [_I, _P, _P, _L, _P, _P],
     "mgnns_imgbank_wgrad": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_map_argmax": [_P, _I, _I, _I, _P, _P],
+    "mgnns_imgbank_dgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "mgnns_label_attn_train_fwd": [_P, _P, _P, _I, _I, _I, _I, _U64, _F, _P, _P, _P, _P],
     "mgnns_label_attn_train_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _SZ, _P],
     "mgnns_dropout_fwd": [_P, _L, _U64, _I, _F, _P, _P, _P],

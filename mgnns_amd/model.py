@@ -654,10 +654,11 @@ class Multi_GCN_Multihead_Att(nn.Module):
 
     def _forward_train(self, text, text_lens, text_mask, object_feature, place_feature, object_inp, place_inp):
         """The reference's training forward (MODEL:431-567) as one chain of autograd Functions over HIP kernels on the current
-        stream.  The text feature and the text memory bank are constants from the eval kernels (frozen encoders); the feature
-        maps get no gradient even if they require one.  Dropout: the fusion layers' three sites, each label Attention's
-        probabilities and the classifier's; every dropping module draws one seed from torch's default generator
-        (last_dropout_seed)."""
+        stream.  The text feature and the text memory bank are constants from the eval kernels (frozen encoders) or carry
+        gradients (unfreeze_text_encoders); feature maps that require a gradient get one, in the caller's tensor, shape and
+        dtype (ImgBankFunction: the bank's data gradient plus the max-pool's).  Dropout: the fusion layers' three sites, each
+        label Attention's probabilities and the classifier's; every dropping module draws one seed from torch's default
+        generator (last_dropout_seed)."""
         self._refuse_untrainable()
         B = text.shape[0]
         if self.text_encoders_trainable:
@@ -675,7 +676,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
                  self.place_linear_5, self.place_x_linear)):
             maps = self._train_maps(trunk_in, 'object_feature' if tag == 'obj' else 'place_feature')
             setattr(self, 'object_feature' if tag == 'obj' else 'place_feature', maps)      # MODEL:450,482 keep them
-            f3 = maps.detach().float().contiguous().view(B, maps.shape[1], -1)
+            f3 = (maps if maps.requires_grad else maps.detach()).float().contiguous().view(B, maps.shape[1], -1)
             bank[tag], pooled = _train.ImgBankFunction.apply(f3, lin.weight, lin.bias, self._wt(lin))
             pair = self._adj_pair(A)
             G = self.gc2(self.gc1(inp[0].float().contiguous(), pair, act=ops.ACT_LRELU2), pair)       # [C, 2048]

@@ -1701,6 +1701,56 @@ def imgbank_wgrad(feat, dbank):
     return dW, db
 
 
+def map_argmax(feat):
+    """arg [B, K] (int32) = the first p at which each row feat[b, k, :] of a feature map [B, K, P] attains its maximum
+    (mgnns_map_argmax): where the max-pool's gradient goes, ties to the smallest index as in torch's max_pool2d backward."""
+    _chk(feat, "feature map", ndim=3)
+    B, K, P = feat.shape
+    if K <= 0 or P <= 0:
+        raise ValueError("feature map %s: need K, P > 0" % (tuple(feat.shape),))
+    arg = torch.empty(B, K, device=feat.device, dtype=torch.int32)
+    _launch("mgnns_map_argmax", ("mgnns_map_argmax", B, P), _lib.lib().mgnns_map_argmax, _p(feat), B, K, P, _p(arg), _stream())
+    return arg
+
+
+def imgbank_dgrad(dbank, weight, dpooled=None, arg=None, positions=None, out=None):
+    """Gradient with respect to the feature map of an image memory bank and its max-pool (mgnns_imgbank_dgrad):
+    dX[b,k,p] = sum_o weight[o,k] dbank[b,p,o] + (p == arg[b,k]) dpooled[b,k] -> dX [B, K, P].  dbank [B, P, N], or None for the
+    pooled term alone (then `positions` = P); weight [N, K] (the nn.Linear's); dpooled [B, K] with arg [B, K] int32 (map_argmax),
+    or both None; out: a [B, K, P] tensor to write instead of a new one.  Exact-f32 MFMA, bit-identical from call to call."""
+    _chk(weight, "weight", ndim=2)
+    N, K = weight.shape
+    if (dpooled is None) != (arg is None):
+        raise ValueError("imgbank_dgrad: dpooled and arg come together")
+    if dpooled is not None:
+        _chk(dpooled, "dpooled", ndim=2)
+        _chk(arg, "arg", dtype=torch.int32, ndim=2)
+        if dpooled.shape[1] != K or arg.shape != dpooled.shape:
+            raise ValueError("dpooled %s / arg %s do not match weight %s" % (tuple(dpooled.shape), tuple(arg.shape),
+                                                                             tuple(weight.shape)))
+    if dbank is not None:
+        _chk(dbank, "dbank", ndim=3)
+        B, P = dbank.shape[:2]
+        if dbank.shape[2] != N or (dpooled is not None and dpooled.shape[0] != B) or positions not in (None, P):
+            raise ValueError("dbank %s does not match weight %s, dpooled %s, positions %s"
+                             % (tuple(dbank.shape), tuple(weight.shape), None if dpooled is None else tuple(dpooled.shape), positions))
+    elif dpooled is None or positions is None:
+        raise ValueError("imgbank_dgrad: without dbank, dpooled / arg and positions (= P) are needed")
+    else:
+        B, P = dpooled.shape[0], int(positions)
+    if P <= 0 or K <= 0 or N <= 0:
+        raise ValueError("imgbank_dgrad: need K, P, N > 0 (K=%d P=%d N=%d)" % (K, P, N))
+    if out is None:
+        dX = torch.empty(B, K, P, device=weight.device, dtype=torch.float32)
+    else:
+        dX = _chk(out, "out", ndim=3)
+        if tuple(dX.shape) != (B, K, P):
+            raise ValueError("out %s is not [%d, %d, %d]" % (tuple(dX.shape), B, K, P))
+    _launch("mgnns_imgbank_dgrad", ("mgnns_imgbank_dgrad", B, P), _lib.lib().mgnns_imgbank_dgrad, _p(dbank), _p(weight), _p(dpooled),
+            _p(arg), B, K, P, N, _p(dX), _stream())
+    return dX
+
+
 def label_attn_train(Q, K, V, n_heads, seed, rate, return_masks=False):
     """Training forward of the label attention between its projections (mgnns_label_attn_train_fwd, MODEL:101-131): Q [NLQ,hid],
     K = V's source projections [B, hid] -> (x [B, NLQ, hid] with dropout(rate) on softmax(energy) over each head's dh axis,

@@ -8,9 +8,10 @@ generator per training forward (kept as `last_dropout_seed`), so torch.manual_se
 
 The rest of the model trains through the Functions below the fusion layers' (csrc/model_train.hip): the image memory banks
 (their weight gradient is the backward's hot path), the label GCN (propagated back with the transposed adjacency), the label
-attention with dropout on its probabilities, the channel tails and the classifier with its dropout.  The CNN trunks and the
-text encoders have no backward here: Multi_GCN_Multihead_Att refuses training mode unless the text encoders are frozen and
-in eval mode, and it takes precomputed feature maps.
+attention with dropout on its probabilities, the channel tails and the classifier with its dropout.  The text encoders train
+through the Functions at the end of this file once unfrozen.  The CNN trunks have no backward here: the model takes precomputed
+feature maps, and maps that require a gradient get one (ImgBankFunction, csrc/map_grad.hip), so a torch trunk in front of the
+model fine-tunes through torch's own backward.
 """
 import torch
 
@@ -148,23 +149,42 @@ def linear(x, lin_or_w, b=None):
 
 class ImgBankFunction(torch.autograd.Function):
     """(bank [B, P, N], pooled [B, K]) = the fp32 memory bank and max-pool of a feature map f [B, K, P] (ops.imgbank_pool; wt =
-    the bank kernel's transposed weight).  Only the weight and bias get gradients (ops.imgbank_wgrad, skipped when neither
-    requires one); the map gets none -- the trunks do not train -- and pooled is a constant."""
+    the bank kernel's transposed weight).  The weight and bias get gradients from ops.imgbank_wgrad (skipped when neither requires
+    one).  A map that requires a gradient gets dX = W^T dbank + the max-pool's gradient at each row's first maximum
+    (ops.imgbank_dgrad over ops.map_argmax of the saved map, both in the backward only); either incoming gradient may be absent.
+    For a map that requires none, pooled is a constant and neither kernel is launched."""
 
     @staticmethod
     def forward(ctx, f, weight, bias, wt):
         bank, pooled = ops.imgbank_pool(f, wt, bias.detach(), weight.shape[0])
-        ctx.save_for_backward(f)
-        ctx.mark_non_differentiable(pooled)
+        ctx.map_grad = ctx.needs_input_grad[0]
+        if ctx.map_grad:
+            ctx.save_for_backward(f, weight)
+            ctx.set_materialize_grads(False)       # an unused bank must not cost a zero-filled dbank
+        else:
+            ctx.save_for_backward(f)
+            ctx.mark_non_differentiable(pooled)
         return bank, pooled
 
     @staticmethod
-    def backward(ctx, dbank, _dpooled):
-        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-            return None, None, None, None
-        f, = ctx.saved_tensors
-        dw, db = ops.imgbank_wgrad(f, dbank.contiguous())
-        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
+    def backward(ctx, dbank, dpooled):
+        want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not ctx.map_grad:
+            if not want_w:
+                return None, None, None, None
+            f, = ctx.saved_tensors
+            dw, db = ops.imgbank_wgrad(f, dbank.contiguous())
+            return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
+        f, weight = ctx.saved_tensors
+        dbank = None if dbank is None else dbank.contiguous()
+        dw = db = dx = None
+        if want_w and dbank is not None:
+            dw, db = ops.imgbank_wgrad(f, dbank)
+        if dpooled is not None:
+            dx = ops.imgbank_dgrad(dbank, weight, dpooled.contiguous(), ops.map_argmax(f), positions=f.shape[2])
+        elif dbank is not None:
+            dx = ops.imgbank_dgrad(dbank, weight)
+        return dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
 
 
 class GCNFunction(torch.autograd.Function):

@@ -8,7 +8,11 @@ formulation.
 --text: the text encoders' training (csrc/text_train.hip) at mvsa_multiple_b256 in fp32 -- the whole-model step with frozen and
 with trainable encoders, each new kernel alone (with algorithmic bytes or FLOPs), and plain torch autograd over the same text
 formulation (nn.LSTM on packed sequences, a scatter-max text GCN).
-Usage: python tools/bench_train.py [--iters N] [--model-only | --text]"""
+--maps: the feature maps' gradient (csrc/map_grad.hip) at mvsa_multiple_b256 in fp32 -- the whole-model step without and with
+map gradients, imgbank_dgrad alone (dense, and with the max-pool scatter) with its % of the fp32 matrix peak next to imgbank_wgrad
+at the same shape, map_argmax alone with its GB/s next to a torch copy of the same bytes, and torch autograd's F.linear
+backward-to-input at the same shape.
+Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps]"""
 import json
 import math
 import os
@@ -314,10 +318,77 @@ def text_case(n):
     return res
 
 
+def maps_case(n):
+    from mgnns_amd import harness, synth
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=cfg.B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV).train().freeze_text_encoders()
+    args = list(harness.call_args(inp, DEV))
+    B = args[0].shape[0]
+    G = torch.randn(B, cfg.NL, device=DEV)
+    res = {"case": "maps_%s_fp32" % cfg.name, "B": B}
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        args[3].grad = args[4].grad = None
+        torch.autograd.backward(model(*args), G)
+
+    res["model_fwd_bwd_us"] = round(timeit(step, n), 1)
+    for i in (3, 4):
+        args[i] = args[i].detach().clone().requires_grad_(True)
+    res["model_fwd_bwd_map_grads_us"] = round(timeit(step, n), 1)
+    assert args[3].grad is not None and args[4].grad is not None
+
+    f3 = args[3].detach().float().contiguous().view(B, args[3].shape[1], -1)
+    K, P = f3.shape[1], f3.shape[2]
+    W = model.liner_img_object.weight.detach()
+    N = W.shape[0]
+    dbank = torch.randn(B, P, N, device=DEV)
+    dpooled = torch.randn(B, K, device=DEV)
+    arg = ops.map_argmax(f3)
+    flop = 2.0 * B * P * K * N
+
+    def mfma(t):
+        return {"us": round(t, 1), "GFLOP": round(flop / 1e9, 1), "TF/s": round(flop / t / 1e6, 1),
+                "pct_fp32_peak": round(100.0 * flop / t / 1e6 / (FP32_PEAK / 1e12), 1)}
+
+    # interleaved, so that a clock drift between the two kernels shows in both
+    tw, td = [], []
+    for _ in range(3):
+        tw.append(timeit(lambda: ops.imgbank_wgrad(f3, dbank), n))
+        td.append(timeit(lambda: ops.imgbank_dgrad(dbank, W), n))
+    res["bank_wgrad"] = dict(mfma(min(tw)), runs_us=[round(t, 1) for t in tw])
+    res["bank_dgrad"] = dict(mfma(min(td)), runs_us=[round(t, 1) for t in td], vs_wgrad=round(min(td) / min(tw), 3))
+    res["bank_dgrad_with_scatter"] = mfma(timeit(lambda: ops.imgbank_dgrad(dbank, W, dpooled, arg), n))
+    res["bank_dgrad_pooled_only_us"] = round(timeit(lambda: ops.imgbank_dgrad(None, W, dpooled, arg, positions=P), n), 1)
+    nbytes = f3.numel() * 4
+    t = timeit(lambda: ops.map_argmax(f3), n)
+    res["map_argmax"] = {"us": round(t, 1), "MB": round(nbytes / 1e6, 1), "GB/s": round(nbytes / t / 1e3, 1)}
+    dst = torch.empty_like(f3)
+    t = timeit(lambda: dst.copy_(f3), n)
+    res["torch_copy_same_bytes"] = {"us": round(t, 1), "read_GB/s": round(nbytes / t / 1e3, 1)}
+    del dst
+    # torch autograd: the bank as F.linear over the transposed map, backward to the input only
+    xt = f3.transpose(1, 2).contiguous().requires_grad_(True)                 # [B, P, K]
+
+    def torch_dgrad():
+        xt.grad = None
+        torch.autograd.backward(F.linear(xt, W), dbank)
+    t_all = timeit(torch_dgrad, n)
+    t_fwd = timeit(lambda: F.linear(xt.detach(), W), n)
+    res["torch_linear_bwd_to_input_us"] = round(t_all - t_fwd, 1)
+    return res
+
+
 def main():
     n = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 20
     if not torch.cuda.is_available():
         raise SystemExit("bench_train: no GPU")
+    if "--maps" in sys.argv:
+        print(json.dumps(maps_case(n)), flush=True)
+        return
     if "--text" in sys.argv:
         print(json.dumps(text_case(n)), flush=True)
         return
