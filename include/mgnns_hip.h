@@ -237,7 +237,8 @@ int mgnns_imgbank_pool_fwd(const float* feat, int B, int K, int P,
  * Two forms, chosen by the batch: one workgroup per sample streaming the map through an LDS-DMA ring (chip-filling batches),
  * two workgroups per sample (region halves; needs 104 < P <= 200, K % 128 == 0) up to half a chip of samples.
  * mgnns_imgbank_set_form: 0 = by batch (default), 1 = always the stream form, 2 = always the pair form
- * where its limits allow -- for tests and measurements; process-wide.
+ * where its limits allow -- for tests and measurements; process-wide.  B = 0: the shape is checked, nothing is launched, the
+ * tensors may be NULL.
  */
 int mgnns_imgbank_set_form(int form);
 size_t mgnns_imgbank_packed_weight_bytes(int K);
@@ -336,7 +337,9 @@ int mgnns_head_diff_fwd(const float* o, int B, int H, int dv, float* out, mgnns_
  * fp32 accumulation; scores/softmax/weighted sum fp32).  The memory bank is bf16 [B, L, ld] with ld == 320
  * (model dim 300 zero padded; build with mgnns_cast_pad_bf16 or let mgnns_imgbank_pool_bf16_fwd emit it);
  * the K/V weights are pre-packed once per weight version by mgnns_sq_mha_pack_weights_bf16 into
- * mgnns_sq_mha_packed_weight_bytes(H) bytes (MFMA-fragment-major, 1 KiB per fragment).
+ * mgnns_sq_mha_packed_weight_bytes(H) bytes (MFMA-fragment-major, 1 KiB per fragment).  L <= 208, H <= 16, D <= 320 at the packer.
+ * mgnns_cast_pad_bf16: y [rows, ld] = bf16(x [rows, D]) zero padded, round to nearest even, a NaN stays a quiet NaN of its sign
+ * whatever its payload; ld >= D, ld % 8 == 0.  B = 0 / rows = 0: the shape is checked, nothing is launched, the tensors may be NULL.
  */
 size_t mgnns_sq_mha_packed_weight_bytes(int H);
 int mgnns_sq_mha_pack_weights_bf16(const float* Wk, const float* Wv, int H, int dk, int D, void* Wp,
@@ -357,6 +360,8 @@ int mgnns_sq_mha_core_bf16_fwd(const float* qh, const void* bank_bf16, const flo
  * 509-527: both image->text stacks, every layer).  With a plan the live rows of several short samples share a workgroup
  * (8-row aligned, <= 128 rows and <= 16 samples per group): the weight stream is read once per group instead of once per
  * sample.  Same results as without a plan up to fp32 summation order.  plan == NULL: one workgroup per sample.
+ * B = 0: the shape is checked, nothing is launched, the tensors may be NULL (mgnns_sq_mha32_plan: the mask may be NULL, the plan
+ * is its four header ints).  H <= 16, D <= 304 at the packer, B <= 4096 at the plan.
  */
 size_t mgnns_sq_mha32_packed_weight_bytes(int H);
 int mgnns_sq_mha32_pack_weights_bf16(const float* Wk, const float* Wv, int H, int dk, int D, void* Wp,
@@ -416,6 +421,7 @@ int mgnns_sq_mha_folded_fwd(const float* qh, const void* bank, int bank_is_bf16,
  * U: fp32 [B, H*D] (head h at h*D); bank: bf16 [B, L, 320] zero padded; mask: fp32 [B, L] (0 = masked) or NULL;
  * C: bf16 [B, ldc] (ldc >= H*D, ldc % 8 == 0; head h at h*D, zeros behind H*D -- ldc = H*D rounded up to 32 is what
  * mgnns_mha_tail_c16_fwd takes); attn: fp32 [H*B, L] or NULL.  D <= 320, D % 4 == 0, H <= 8, L <= 208.  One read of the bank.
+ * B = 0: the shape is checked, nothing is launched, the tensors may be NULL.
  */
 int mgnns_sq_mha_folded_bf16_fwd(const float* U, const void* bank_bf16, const float* mask, int B, int L, int D, int H,
                                  float inv_temp, void* C_bf16, int ldc, float* attn, mgnns_stream_t stream);

@@ -429,15 +429,15 @@ extern "C" int mgnns_imgbank_set_form(int form) {
 extern "C" int mgnns_imgbank_pool_bf16_fwd(const float* feat, int B, int K, int P, const void* Wp, const float* bias, int N,
                                            void* bank_bf16, int ld, float* pooled, float* pooled_work,
                                            mgnns_stream_t stream) {
-    MG_REQUIRE(feat && Wp && bank_bf16 && pooled_work, "mgnns_imgbank_pool_bf16_fwd: null pointer");
     MG_REQUIRE(B >= 0 && K > 0 && K % BK == 0, "mgnns_imgbank_pool_bf16_fwd: K=%d must be a positive multiple of %d", K, BK);
     MG_REQUIRE(P % 4 == 0 && P >= 16 && P <= PMAX, "mgnns_imgbank_pool_bf16_fwd: P=%d unsupported (multiple of 4 in [16, %d])", P, PMAX);
     MG_REQUIRE((double)K * P * 4 < 2147483648.0, "mgnns_imgbank_pool_bf16_fwd: a sample's map must stay below 2 GiB");
     MG_REQUIRE(N > 0 && N <= NT * 16, "mgnns_imgbank_pool_bf16_fwd: N=%d unsupported (<= %d)", N, NT * 16);
     MG_REQUIRE(ld == OUT_LD, "mgnns_imgbank_pool_bf16_fwd: bank row length must be %d", OUT_LD);
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(feat && Wp && bank_bf16 && pooled_work, "mgnns_imgbank_pool_bf16_fwd: null pointer");
     MG_REQUIRE(mg_aligned16(feat) && mg_aligned16(Wp) && mg_aligned16(bank_bf16),
                "mgnns_imgbank_pool_bf16_fwd: feat/Wp/bank must be 16-byte aligned");
-    if (B == 0) return 0;
     // A workgroup of the stream kernel needs ~95 us for its sample whatever the batch; up to half a chip of samples the
     // two-workgroups-per-sample form (half the chain per workgroup) is the faster one.  mgnns_imgbank_set_form(1 / 2) forces one.
     const int n_cu = mg_cu_count();

@@ -809,8 +809,8 @@ extern "C" int mgnns_sq_mha32_pack_weights_bf16(const float* Wk, const float* Wv
 extern "C" size_t mgnns_sq_mha32_plan_ints(int B) { return (size_t)PLAN_HDR + 6 * (size_t)(B > 0 ? B : 0); }
 
 extern "C" int mgnns_sq_mha32_plan(const float* mask, int B, int L, int32_t* plan, mgnns_stream_t stream) {
-    MG_REQUIRE(mask && plan, "mgnns_sq_mha32_plan: null pointer");
     MG_REQUIRE(B >= 0 && B <= 4096 && L > 0 && L <= PR, "mgnns_sq_mha32_plan: B=%d (<= 4096), L=%d (1..%d) unsupported", B, L, PR);
+    MG_REQUIRE((mask || B == 0) && plan, "mgnns_sq_mha32_plan: null pointer");      // (an empty batch's mask has no storage; its plan: the header)
     const size_t lds = mg_plan::lds_bytes(B);
     MG_DYN_LDS(sq_mha32_plan_kernel, lds);
     hipLaunchKernelGGL(sq_mha32_plan_kernel, dim3(1), dim3(1024), lds, (hipStream_t)stream, mask, B, L, plan);
@@ -822,15 +822,16 @@ extern "C" int mgnns_sq_mha32_core_bf16_fwd(const float* qh, const void* bank_bf
                                             int H, int dk, const void* Wp, const float* bk, const float* bv, float* o,
                                             float* attn, const int32_t* plan, mgnns_stream_t stream) {
     (void)bk;                           // q.b_k shifts every score of a head equally: softmax invariant
-    MG_REQUIRE(qh && bank_bf16 && Wp && o, "mgnns_sq_mha32_core_bf16_fwd: null pointer");
     MG_REQUIRE(dk == DK, "mgnns_sq_mha32_core_bf16_fwd: d_kv=%d unsupported (128 only)", dk);
     MG_REQUIRE(ld == CH * 8, "mgnns_sq_mha32_core_bf16_fwd: bank row length %d must be %d (bf16, zero padded)", ld, CH * 8);
     MG_REQUIRE(B >= 0 && H > 0 && L > 0 && L <= LMAX, "mgnns_sq_mha32_core_bf16_fwd: L=%d unsupported (1..%d)", L, LMAX);
     MG_REQUIRE((double)H * B * L * 4 < 2147483648.0, "mgnns_sq_mha32_core_bf16_fwd: attn output beyond 2 GiB (B=%d)", B);
     MG_REQUIRE(H * DK <= QMAX, "mgnns_sq_mha32_core_bf16_fwd: n_head=%d unsupported (<= %d)", H, QMAX / DK);
+    MG_REQUIRE(!plan || L <= PR, "mgnns_sq_mha32_core_bf16_fwd: a packing plan needs a mask and L <= %d", PR);
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(qh && bank_bf16 && Wp && o, "mgnns_sq_mha32_core_bf16_fwd: null pointer");
     MG_REQUIRE(mg_aligned16(bank_bf16) && mg_aligned16(Wp) && mg_aligned16(qh), "mgnns_sq_mha32_core_bf16_fwd: qh/bank/Wp must be 16-byte aligned");
-    MG_REQUIRE(!plan || (mask && L <= PR), "mgnns_sq_mha32_core_bf16_fwd: a packing plan needs a mask and L <= %d", PR);
-    if (B == 0) return 0;
+    MG_REQUIRE(!plan || mask, "mgnns_sq_mha32_core_bf16_fwd: a packing plan needs a mask and L <= %d", PR);
     const int n_cu = mg_cu_count();
     if (n_cu <= 0) return MGNNS_ERR_LAUNCH;
     const float temp = (float)sqrt((double)dk);

@@ -40,8 +40,9 @@ constexpr int DK = 128;
 constexpr int NTHR = MG_MHA_NTHR;
 constexpr int QMAX = 2048;              // floats of the projected query kept in LDS (H * 128 <= QMAX)
 
-__device__ __forceinline__ unsigned short f2bf(float x) {      // round-to-nearest-even
+__device__ __forceinline__ unsigned short f2bf(float x) {      // round-to-nearest-even; NaN stays a quiet NaN
     unsigned int u = __float_as_uint(x);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x40u);     // (the carry of a large payload would reach the sign)
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
@@ -543,9 +544,9 @@ extern "C" int mgnns_sq_mha_pack_weights_bf16(const float* Wk, const float* Wv, 
 }
 
 extern "C" int mgnns_cast_pad_bf16(const float* x, int64_t rows, int D, int ld, void* y, mgnns_stream_t stream) {
-    MG_REQUIRE(x && y, "mgnns_cast_pad_bf16: null pointer");
     MG_REQUIRE(rows >= 0 && D > 0 && ld >= D && ld % 8 == 0, "mgnns_cast_pad_bf16: bad dims D=%d ld=%d", D, ld);
-    if (rows == 0) return 0;
+    if (rows == 0) return 0;               // no rows, no storage: the pointers are null
+    MG_REQUIRE(x && y, "mgnns_cast_pad_bf16: null pointer");
     const size_t total = (size_t)rows * (ld / 8);
     size_t blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
@@ -558,14 +559,14 @@ extern "C" int mgnns_cast_pad_bf16(const float* x, int64_t rows, int D, int ld, 
 extern "C" int mgnns_sq_mha_core_bf16_fwd(const float* qh, const void* bank_bf16, const float* mask, int B, int L, int ld,
                                           int H, int dk, const void* Wp, const float* bk, const float* bv, float* o,
                                           float* attn, mgnns_stream_t stream) {
-    MG_REQUIRE(qh && bank_bf16 && Wp && o, "mgnns_sq_mha_core_bf16_fwd: null pointer");
     MG_REQUIRE(dk == DK, "mgnns_sq_mha_core_bf16_fwd: d_kv=%d unsupported (128 only)", dk);
     MG_REQUIRE(ld == KP, "mgnns_sq_mha_core_bf16_fwd: bank row length %d must be %d (bf16, zero padded)", ld, KP);
     MG_REQUIRE(B >= 0 && H > 0 && L > 0 && L <= LMAX, "mgnns_sq_mha_core_bf16_fwd: L=%d unsupported (1..%d)", L, LMAX);
     MG_REQUIRE((double)H * B * L * 4 < 2147483648.0, "mgnns_sq_mha_core_bf16_fwd: attn output beyond 2 GiB (B=%d)", B);
     MG_REQUIRE(H * DK <= QMAX, "mgnns_sq_mha_core_bf16_fwd: n_head=%d unsupported (<= %d)", H, QMAX / DK);
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(qh && bank_bf16 && Wp && o, "mgnns_sq_mha_core_bf16_fwd: null pointer");
     MG_REQUIRE(mg_aligned16(bank_bf16) && mg_aligned16(Wp), "mgnns_sq_mha_core_bf16_fwd: bank/Wp must be 16-byte aligned");
-    if (B == 0) return 0;
     MG_DYN_LDS(sq_mha_core_bf16_kernel, SMEM_BYTES);
     // one workgroup per sample owns all head pairs when the batch fills the chip; small batches split the pairs
     const int pairs = (H + 1) / 2;

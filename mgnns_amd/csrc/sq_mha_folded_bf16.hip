@@ -263,13 +263,13 @@ extern "C" int mgnns_debug_fold_trace(unsigned long long* out) {
 // attn: fp32 [H*B, L] (the reference's layout, MODEL: submodules.py:76-82) or null.  inv_temp = 1 / sqrt(d_k).
 extern "C" int mgnns_sq_mha_folded_bf16_fwd(const float* U, const void* bank_bf16, const float* mask, int B, int L, int D, int H,
                                             float inv_temp, void* C_bf16, int ldc, float* attn, mgnns_stream_t stream) {
-    MG_REQUIRE(U && bank_bf16 && C_bf16, "mgnns_sq_mha_folded_bf16_fwd: null pointer");
     MG_REQUIRE(B >= 0 && L > 0 && L <= LMAX, "mgnns_sq_mha_folded_bf16_fwd: need 0 < L <= %d (L=%d)", LMAX, L);
     MG_REQUIRE(D > 0 && D <= KP && D % 4 == 0, "mgnns_sq_mha_folded_bf16_fwd: need D <= %d, D %% 4 == 0 (D=%d)", KP, D);
     MG_REQUIRE(H > 0 && H <= MAXH, "mgnns_sq_mha_folded_bf16_fwd: need 0 < H <= %d (H=%d)", MAXH, H);
-    MG_REQUIRE(mg_aligned16(bank_bf16), "mgnns_sq_mha_folded_bf16_fwd: the bank must be 16-byte aligned");
     MG_REQUIRE(ldc >= H * D && ldc % 8 == 0, "mgnns_sq_mha_folded_bf16_fwd: ldc=%d (>= H*D = %d, multiple of 8)", ldc, H * D);
-    if (B == 0) return 0;
+    if (B == 0) return 0;                  // an empty batch has no storage: its pointers are null
+    MG_REQUIRE(U && bank_bf16 && C_bf16, "mgnns_sq_mha_folded_bf16_fwd: null pointer");
+    MG_REQUIRE(mg_aligned16(bank_bf16), "mgnns_sq_mha_folded_bf16_fwd: the bank must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     MG_DYN_LDS(folded_attn_bf16_kernel, SMEM_BYTES);
     hipLaunchKernelGGL(folded_attn_bf16_kernel, dim3(B), dim3(NTHR), SMEM_BYTES, s, U, static_cast<const unsigned short*>(bank_bf16),

@@ -107,8 +107,7 @@ def _d(t):
 def img_bank(feat, weight, bias, rounding=None):
     """feat [B, 2048, P] (or [B, 2048, h, w]) -> (bank [B, P, N] fp64, the stored values; pooled [B, 2048] exact max)."""
     rd = _Rounder(rounding)
-    B = feat.shape[0]
-    f3 = _d(feat).reshape(B, feat.shape[1], -1)
+    f3 = _d(feat).flatten(2)                             # (an empty batch cannot be reshaped through -1)
     x = rd("imgbank_x", f3.permute(0, 2, 1))
     bank = rd("imgbank_out", x @ rd("imgbank_w", weight).t() + _d(bias))
     return bank, f3.max(dim=2).values

@@ -88,3 +88,155 @@ def relerr(a, b):
 
 def maxabs(a, b):
     return float((torch.as_tensor(a).double() - torch.as_tensor(b).double()).abs().max())
+
+
+# ---- numeric helpers of the edge sweeps (tests/test_forward_edges_gpu.py, tests/test_bf16_edges_gpu.py) ------------------------------
+def f64(x):
+    """float tensors / arrays -> float64 torch CPU tensors, through lists, tuples and dicts; everything else unchanged."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    if torch.is_tensor(x):
+        return x.double() if x.is_floating_point() else x
+    if isinstance(x, (list, tuple)):
+        return type(x)(f64(v) for v in x)
+    if isinstance(x, dict):
+        return {k: f64(v) for k, v in x.items()}
+    return x
+
+
+def f32(x):
+    if torch.is_tensor(x):
+        return x.float() if x.is_floating_point() else x
+    if isinstance(x, (list, tuple)):
+        return type(x)(f32(v) for v in x)
+    if isinstance(x, dict):
+        return {k: f32(v) for k, v in x.items()}
+    return x
+
+
+def maxerr(got, ref):
+    got, ref = torch.as_tensor(got).detach().double().cpu(), torch.as_tensor(ref).double()
+    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
+    return float((got - ref).abs().max()) if ref.numel() else 0.0
+
+
+def scale(ref):
+    return float(ref.abs().max()) if ref.numel() else 0.0
+
+
+def fp32_cpu_err(fn, *args):
+    """Largest error of each output of fn evaluated in float32 on the CPU against fn in float64 (args are float64)."""
+    a, b = fn(*f32(args)), fn(*args)
+    if torch.is_tensor(a):
+        a, b = (a,), (b,)
+    return [maxerr(x, y) for x, y in zip(a, b) if x is not None]
+
+
+def close(got, ref, tol, what, rel=False):
+    """|got - ref| <= tol (x the largest |ref| when rel); prints the figure before it asserts."""
+    assert torch.isfinite(torch.as_tensor(got)).all(), "%s: non-finite values" % what
+    err, bound = maxerr(got, ref), tol * (scale(ref) if rel else 1.0)
+    print("%s: max err %.3e, bound %.3e" % (what, err, bound))
+    assert err <= bound, "%s: max err %.3e > %.3e" % (what, err, bound)
+
+
+def make_mask(kind, B, L, rs):
+    """[B, L] float32 (1 = live) or None.  ragged: a random cut-off per sample, sample 0 full; tile: cut-offs on 16-row tile boundaries;
+    holes: position 0 dead, random holes, the last position live, and one sample whose ONLY live position is the last; single: ragged
+    with one sample that has a single live position."""
+    if kind == "none":
+        return None
+    m = np.ones((B, L), np.float32)
+    for b in range(B):
+        if kind in ("ragged", "single") and b:
+            m[b, rs.randint(1, L + 1):] = 0
+        elif kind == "tile":
+            m[b, min(L, 16 * rs.randint(1, L // 16 + 2)):] = 0
+        elif kind == "holes":
+            m[b] = rs.uniform(size=L) > 0.4
+            m[b, 0], m[b, L - 1] = 0 if L > 1 else 1, 1
+    if B and kind == "holes":
+        m[B - 1] = 0
+        m[B - 1, L - 1] = 1
+    if B and kind == "single":
+        m[B - 1] = 0
+        m[B - 1, rs.randint(0, L)] = 1
+    return m
+
+
+def core_case(L, D, H, B, kind, bias, dk=128):
+    rs = np.random.RandomState(L * 1000 + D + 7 * H + B)
+    qh = rs.standard_normal((B, H * dk)).astype(np.float32)
+    bank = (1.2 * rs.standard_normal((B, L, D))).astype(np.float32)
+    wk = (0.05 * rs.standard_normal((H * dk, D))).astype(np.float32)
+    wv = (0.05 * rs.standard_normal((H * dk, D))).astype(np.float32)
+    bk = rs.standard_normal(H * dk).astype(np.float32) if bias else None
+    bv = rs.standard_normal(H * dk).astype(np.float32) if bias else None
+    return [None if a is None else torch.from_numpy(a) for a in (qh, bank, make_mask(kind, B, L, rs), wk, bk, wv, bv)]
+
+
+# ---- bf16 edge sweeps (tests/test_bf16_edges_gpu.py, pinned by tests/test_bf16_edges_ref_cpu.py) ---------------------------------------
+# fp32 bit patterns a bf16 cast must get right: ties between two bf16 neighbours (even and odd upper half, either sign), one bit
+# either side of a tie, +-0, denormals, the largest finite values (the last rounds to inf), +-inf, quiet and signalling NaN with
+# small and all-ones payloads
+BF16_SPECIALS = np.array([0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F807FFF, 0x3F808001, 0x40490FDB,
+                          0x00000000, 0x80000000, 0x00000001, 0x00008000, 0x00018000, 0x007FFFFF, 0x807FFFFF, 0x00800000,
+                          0x7F7F7FFF, 0x7F7F8000, 0xFF7F8000, 0x7F7FFFFF, 0x7F800000, 0xFF800000,
+                          0x7FC00000, 0xFFC00000, 0x7F800001, 0x7FFFFFFF, 0xFFFFFFFF, 0x7FFF8000], dtype=np.uint32)
+
+
+def within_bf16_store(got, want, what):
+    """A value stored as bf16 against its float64 value before the store, ELEMENT BY ELEMENT: |got - want| <= 2^-8 |want| (half a bf16
+    ulp is at most that) + 1e-5 max|want| (fp32 accumulation in another order); prints the worst ratio before it asserts."""
+    got, want = torch.as_tensor(got).detach().double().cpu(), torch.as_tensor(want).double()
+    assert got.shape == want.shape, (tuple(got.shape), tuple(want.shape))
+    if not want.numel():
+        print("%s: empty" % what)
+        return
+    assert torch.isfinite(got).all(), "%s: non-finite values" % what
+    bound = want.abs() * 2.0 ** -8 + 1e-5 * float(want.abs().max())
+    ratio = (got - want).abs() / bound
+    i = int(ratio.argmax())
+    print("%s: worst |err| / bound %.3f (err %.3e, bound %.3e, want %.4e)"
+          % (what, float(ratio.flatten()[i]), float((got - want).abs().flatten()[i]), float(bound.flatten()[i]), float(want.flatten()[i])))
+    assert float(ratio.max()) <= 1.0, "%s: element %d off by %.3f x its bound" % (what, i, float(ratio.max()))
+
+
+def decode_plan(plan, B):
+    """ops.sq_mha_plan's int32 buffer -> ([(first sample, samples, rows)] per group, row offset [B], live rows [B])."""
+    pl = torch.as_tensor(plan).cpu().numpy()
+    ng = int(pl[0])
+    groups = [tuple(int(x) for x in pl[4 + 4 * g: 4 + 4 * g + 3]) for g in range(ng)]
+    off = pl[4 + 4 * B: 4 + 6 * B: 2].astype(int)
+    lv = pl[4 + 4 * B + 1: 4 + 6 * B: 2].astype(int)
+    return groups, off, lv
+
+
+def check_plan(plan, mask, max_rows=128, max_samples=16, align=8):
+    """The invariants of a packing plan of `mask` [B, L]: it names its batch, every sample sits in exactly one group, a group holds
+    1 .. 16 samples and at most 128 rows, a sample's rows start 8-aligned behind its predecessor's (a sample takes its live rows
+    rounded up to 8, at least 8), a group's row count is the sum of its samples', and a sample's live rows are its last unmasked
+    position + 1 (0: no live position).  Raises AssertionError naming the broken one."""
+    m = np.asarray(mask)
+    B = m.shape[0]
+    pl = torch.as_tensor(plan).cpu().numpy()
+    assert pl.shape[0] == 4 + 6 * B, "plan size %d for a batch of %d" % (pl.shape[0], B)
+    assert int(pl[1]) == B, "plan built for a batch of %d, not %d" % (int(pl[1]), B)
+    assert 0 <= int(pl[0]) <= B, "%d groups for %d samples" % (int(pl[0]), B)
+    groups, off, lv = decode_plan(pl, B)
+    want_lv = np.array([0 if not m[b].any() else int(np.nonzero(m[b])[0][-1]) + 1 for b in range(B)], int)
+    assert np.array_equal(lv, want_lv), "live rows differ from the mask's last live position + 1 at samples %s" % np.nonzero(lv != want_lv)[0][:8]
+    seen = np.zeros(B, int)
+    for first, cnt, rows in groups:
+        assert 1 <= cnt <= max_samples, "group at sample %d holds %d samples" % (first, cnt)
+        assert rows <= max_rows, "group at sample %d holds %d rows" % (first, rows)
+        assert 0 <= first and first + cnt <= B, "group at sample %d runs past the batch" % first
+        r = 0
+        for b in range(first, first + cnt):
+            seen[b] += 1
+            assert off[b] % align == 0, "sample %d starts at row %d, not %d-aligned" % (b, off[b], align)
+            assert off[b] == r, "sample %d starts at row %d, its predecessors end at %d" % (b, off[b], r)
+            r += max(align, (lv[b] + align - 1) // align * align)
+        assert r == rows, "group at sample %d says %d rows, its samples take %d" % (first, rows, r)
+    assert (seen == 1).all(), "samples not in exactly one group: %s" % np.nonzero(seen != 1)[0][:8]
+    return groups, off, lv

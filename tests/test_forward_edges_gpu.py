@@ -18,6 +18,7 @@ import torch
 from mgnns_amd import metrics, ops
 from oracle import restatement as R
 from tests import forward_ref as F
+from tests.helpers import close, core_case, f32, f64, fp32_cpu_err, make_mask, maxerr, scale  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -40,91 +41,7 @@ def dev(x):
     return None if x is None else torch.as_tensor(x).to(DEV).contiguous()
 
 
-def f64(x):
-    """float tensors / arrays -> float64 torch CPU tensors, through lists, tuples and dicts; everything else unchanged."""
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(x)
-    if torch.is_tensor(x):
-        return x.double() if x.is_floating_point() else x
-    if isinstance(x, (list, tuple)):
-        return type(x)(f64(v) for v in x)
-    if isinstance(x, dict):
-        return {k: f64(v) for k, v in x.items()}
-    return x
-
-
-def f32(x):
-    if torch.is_tensor(x):
-        return x.float() if x.is_floating_point() else x
-    if isinstance(x, (list, tuple)):
-        return type(x)(f32(v) for v in x)
-    if isinstance(x, dict):
-        return {k: f32(v) for k, v in x.items()}
-    return x
-
-
-def maxerr(got, ref):
-    got, ref = torch.as_tensor(got).detach().double().cpu(), torch.as_tensor(ref).double()
-    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
-    return float((got - ref).abs().max()) if ref.numel() else 0.0
-
-
-def scale(ref):
-    return float(ref.abs().max()) if ref.numel() else 0.0
-
-
-def fp32_cpu_err(fn, *args):
-    """Largest error of each output of fn evaluated in float32 on the CPU against fn in float64 (args are float64)."""
-    a, b = fn(*f32(args)), fn(*args)
-    if torch.is_tensor(a):
-        a, b = (a,), (b,)
-    return [maxerr(x, y) for x, y in zip(a, b) if x is not None]
-
-
-def close(got, ref, tol, what, rel=False):
-    """|got - ref| <= tol (x the largest |ref| when rel); prints the figure before it asserts."""
-    assert torch.isfinite(torch.as_tensor(got)).all(), "%s: non-finite values" % what
-    err, bound = maxerr(got, ref), tol * (scale(ref) if rel else 1.0)
-    print("%s: max err %.3e, bound %.3e" % (what, err, bound))
-    assert err <= bound, "%s: max err %.3e > %.3e" % (what, err, bound)
-
-
 # ---- attention core -----------------------------------------------------------------------------------------------------------
-def make_mask(kind, B, L, rs):
-    """[B, L] float32 (1 = live) or None.  ragged: a random cut-off per sample, sample 0 full; tile: cut-offs on 16-row tile boundaries;
-    holes: position 0 dead, random holes, the last position live, and one sample whose ONLY live position is the last; single: ragged
-    with one sample that has a single live position."""
-    if kind == "none":
-        return None
-    m = np.ones((B, L), np.float32)
-    for b in range(B):
-        if kind in ("ragged", "single") and b:
-            m[b, rs.randint(1, L + 1):] = 0
-        elif kind == "tile":
-            m[b, min(L, 16 * rs.randint(1, L // 16 + 2)):] = 0
-        elif kind == "holes":
-            m[b] = rs.uniform(size=L) > 0.4
-            m[b, 0], m[b, L - 1] = 0 if L > 1 else 1, 1
-    if B and kind == "holes":
-        m[B - 1] = 0
-        m[B - 1, L - 1] = 1
-    if B and kind == "single":
-        m[B - 1] = 0
-        m[B - 1, rs.randint(0, L)] = 1
-    return m
-
-
-def core_case(L, D, H, B, kind, bias, dk=128):
-    rs = np.random.RandomState(L * 1000 + D + 7 * H + B)
-    qh = rs.standard_normal((B, H * dk)).astype(np.float32)
-    bank = (1.2 * rs.standard_normal((B, L, D))).astype(np.float32)
-    wk = (0.05 * rs.standard_normal((H * dk, D))).astype(np.float32)
-    wv = (0.05 * rs.standard_normal((H * dk, D))).astype(np.float32)
-    bk = rs.standard_normal(H * dk).astype(np.float32) if bias else None
-    bv = rs.standard_normal(H * dk).astype(np.float32) if bias else None
-    return [None if a is None else torch.from_numpy(a) for a in (qh, bank, make_mask(kind, B, L, rs), wk, bk, wv, bv)]
-
-
 def check_attention(o, attn, ro, rattn, mask, H, B, L, what):
     assert tuple(attn.shape) == (H * B, 1, L) and tuple(o.shape) == tuple(ro.shape)
     close(attn, rattn, ATTN, what + " attn")                    # the reference is head-major: row h * B + b

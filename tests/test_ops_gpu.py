@@ -942,13 +942,7 @@ def test_a_plan_of_the_other_kind_is_refused_by_the_wrapper_and_by_the_kernel():
     assert H.maxabs(o.cpu(), o1.cpu()) < 5e-6
 
 
-def _decode_plan(plan, B):
-    pl = plan.cpu().numpy()
-    ng = int(pl[0])
-    groups = [tuple(int(x) for x in pl[4 + 4 * g: 4 + 4 * g + 3]) for g in range(ng)]
-    off = pl[4 + 4 * B: 4 + 6 * B: 2].astype(int)
-    lv = pl[4 + 4 * B + 1: 4 + 6 * B: 2].astype(int)
-    return groups, off, lv
+_decode_plan = H.decode_plan
 
 
 @pytest.mark.parametrize("Hn,B,L", [(8, 256, 100), (8, 300, 128), (4, 64, 100), (1, 5, 37), (3, 33, 64), (8, 1, 100), (8, 256, 9)])
