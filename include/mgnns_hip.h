@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 23
+#define MGNNS_ABI_VERSION 24
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -508,6 +508,20 @@ int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int K0, int spl
                         const void* w2a, const void* w2b, int N2, float* G, void* Gp_hi, void* Gp_lo,
                         const float* label_query, int NLQ, const float* wq, const float* bq, int HQ, float* Q,
                         void* scratch, size_t scratch_bytes, int grid, mgnns_stream_t stream);
+/* The same launch with a MEMO: nothing it computes depends on the batch, so while inp (the label embedding table, the same tensor
+ * for every batch of a dataset) and the weights stay what they were, G / Gp / Q of the previous launch are still right.
+ * memo: mgnns_label_gcn_memo_bytes(C, K0) bytes, 256-byte aligned, its first 256 bytes ZERO before the first launch; it holds
+ * three words (int32 [0] valid, [1] hit: the verdict of the last launch, 1 = nothing was computed, [2] internal) and, from
+ * byte 256, a snapshot of the inp the outputs were computed from.  A small check launch compares inp with the snapshot on the
+ * DEVICE, bitwise as integers (NaN equals NaN, -0 differs from +0), and the GCN launch behind it leaves at once on a hit --
+ * correct under hipGraph replay, where no host code sees the inputs.  The caller keeps G, Gp_hi / Gp_lo, Q, scratch and memo
+ * together and passes the SAME buffers every time (a hit writes nothing); one set per concurrently running launch.  The
+ * weights (A, W1, W2, label_query, wq, bq) are NOT compared: after changing one, pass a fresh zeroed memo. */
+size_t mgnns_label_gcn_memo_bytes(int C, int K0);
+int mgnns_label_gcn_memo_fwd(const float* A, int C, const float* inp, int K0, int split, const void* w1a, const void* w1b, int N1,
+                             const void* w2a, const void* w2b, int N2, float* G, void* Gp_hi, void* Gp_lo,
+                             const float* label_query, int NLQ, const float* wq, const float* bq, int HQ, float* Q,
+                             void* scratch, size_t scratch_bytes, void* memo, size_t memo_bytes, int grid, mgnns_stream_t stream);
 
 /* ---- a9: classifier over the four fusion features (Multi_GCN_Multihead_att.py:560-566, eval: dropout is the identity) --
  * logits[b,:] = W [f0[b]; f1[b]; f2[b]; f3[b]] + bias without materialising the concatenation.  f_p [B,D]; W [NL, 4*D];

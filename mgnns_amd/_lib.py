@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _c = ctypes
 _P = _c.c_void_p
@@ -49,6 +49,7 @@ SIGNATURES = {
     "mgnns_label_attn_core_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "mgnns_label_attn_core_masked_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "mgnns_label_gcn_fwd": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _SZ, _I, _P],
+    "mgnns_label_gcn_memo_fwd": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _SZ, _P, _SZ, _I, _P],
     "mgnns_classifier_head_fwd": [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P],
     "mgnns_label_tail_bf16_fwd": [_P, _I, _I, _I, _I, _I, _PP, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P],
     "mgnns_label_tail_fwd": [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P,
@@ -141,6 +142,7 @@ SIZE_GETTERS = {
     "mgnns_bilstm_bf16_table_bytes": [_I, _I],
     "mgnns_bilstm_bf16_fold_workspace_bytes": [_I],
     "mgnns_label_gcn_scratch_bytes": [_I, _I, _I],
+    "mgnns_label_gcn_memo_bytes": [_I, _I],
     "mgnns_mha_tail_c16_scratch_floats": [_I, _I],
     "mgnns_mha_train_bwd_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_wgrad_workspace_bytes": [_I, _I, _I],

@@ -23,6 +23,22 @@
 // counting grid barrier, which hangs as soon as one workgroup of the grid cannot be scheduled.)  The wait is bounded all the
 // same: after ~2^24 polls a workgroup raises the abort word (everybody drains) and the library's status word
 // (mgnns_set_status_word), which the next persistent launch reports through mgnns_last_error().
+//
+// The memo (mgnns_label_gcn_memo_fwd).  Nothing above depends on the batch: until a weight changes, a forward whose label
+// embedding table inp is the one of the forward before it recomputes the same G, Gp and Q.  With a memo buffer the outputs
+// and a snapshot of the inp they were computed from outlive the call, and the DEVICE decides whether to compute (inp is a
+// forward argument; under hipGraph replay no host code runs).  Two launches, ordered by the stream alone:
+//   label_gcn_memo_check   compares inp with the snapshot as 32-bit INTEGERS (a NaN equals itself, -0 differs from +0).
+//                          Every workgroup adds (1 | differs << 16) to one arrival word; the workgroup whose add completes
+//                          the count has every verdict in its hand, writes hit = valid && nothing differs, re-arms the word.
+//   label_gcn_kernel       reads `hit` at entry: set -> every workgroup returns at once, the outputs of the launch that took
+//                          the snapshot stand.  Clear -> the launch computes exactly as without a memo, and the LAST workgroup
+//                          to leave copies inp into the snapshot and sets `valid` (clears it if the launch was aborted).
+// Why a workgroup that starts late sees nothing half-done: `hit` is written by the check launch only, which has completed
+// before the first workgroup of the GCN launch starts and does not run again before its last one has left, so all of them read
+// the same value; the snapshot and `valid` are written only by the workgroup that found every other one gone, and read only
+// by the NEXT check launch, behind a kernel boundary.  No co-residency is needed anywhere.  Weights (A, W1, W2, the label
+// query, w_q) are NOT compared: the host keys the memo on their versions and hands a fresh (valid = 0) one after a change.
 #include "common.hpp"
 #include "tile_bf16.hpp"
 #include "tile_f32.hpp"
@@ -46,6 +62,8 @@ struct LgArgs {
     int* counters;                           // 64 ints (ticket head, done[4], exited, abort: see LG_DONE ...); zero before the first launch, every launch leaves them zero
     int* status;                             // the library's status word (host-pinned, may be null)
     int rows_d, outs_q, pcs3;                // wave-granular work per queue item (multiples of 8: one or more per wave), sized to the grid
+    int* memo;                               // null: no memo.  LGM_VALID / LGM_HIT / LGM_ARRIVE words (256 B), zero before the first launch
+    unsigned* snap;                          // [C*K0]: the inp the outputs standing in G / Gp / Q were computed from
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t lg_rsrc(const void* p, size_t bytes) {
@@ -69,7 +87,11 @@ __device__ __forceinline__ void lg_st4(__amdgpu_buffer_rsrc_t r, int off, f32x4 
 
 // counters (ints, three 64-byte lines so that ticket draws, arrival polls and the exit count do not share one):
 //   [0] ticket head   [16 + p] items of phase p done   [32] workgroups that left   [33] abort
+//   ([32]: + 1 << 16 per workgroup that leaves because the launch was aborted -- the last one then knows without a second word)
 constexpr int LG_DONE = 16, LG_LEFT = 32, LG_ABORT = 33;
+// memo words: the snapshot is complete | the last check launch's verdict | the check launch's arrival word
+constexpr int LGM_VALID = 0, LGM_HIT = 1, LGM_ARRIVE = 2;
+constexpr int LGM_THR = 256;
 constexpr int LG_SPIN_LIMIT = 1 << 24;
 // next work item of this workgroup (wave-uniform), -1 once the queue is empty or the launch is being aborted.  Thread 0 draws
 // the ticket AFTER the next one while the current item is being worked on (`ahead`): the atomic's round trip (~1 us) hides
@@ -182,11 +204,37 @@ __device__ __forceinline__ void lg_gemm_item(unsigned char* smem, __amdgpu_buffe
     __syncthreads();                                   // the tile buffer is restaged by this workgroup's next item
 }
 
+// inp == snapshot, bit for bit?  n4 16-byte words each; see the file comment for the protocol.
+__global__ __launch_bounds__(LGM_THR) void label_gcn_memo_check(const uint4* __restrict__ inp, const uint4* __restrict__ snap, int n4,
+                                                                int* memo) {
+    __shared__ int s_diff;
+    if (threadIdx.x == 0) s_diff = 0;
+    __syncthreads();
+    unsigned diff = 0;
+    for (int i = blockIdx.x * LGM_THR + threadIdx.x; i < n4; i += gridDim.x * LGM_THR) {
+        const uint4 x = inp[i], y = snap[i];
+        diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+    }
+    if (diff) s_diff = 1;                                          // (every writer writes the same value)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int mine = 1 + (s_diff ? 1 << 16 : 0);
+        const int all = __hip_atomic_fetch_add(&memo[LGM_ARRIVE], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine;
+        if ((all & 0xffff) == (int)gridDim.x) {                    // the last verdict in: it carries everybody's
+            const int valid = __hip_atomic_load(&memo[LGM_VALID], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&memo[LGM_HIT], valid != 0 && (all >> 16) == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&memo[LGM_ARRIVE], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 template <bool SPLIT>
 __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // memo hit: the outputs of the launch that took the snapshot stand (the word is the check launch's, constant while this one runs)
+    if (a.memo && __hip_atomic_load(&a.memo[LGM_HIT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
     const int C = a.C, K0 = a.K0, N1 = a.N1, N2 = a.N2;
     const int MT = (C + 15) / 16;
     const size_t tile_bytes = SPLIT ? (size_t)2 * 16 * lg_sc(N1 > K0 ? N1 : K0) * 16 : (size_t)16 * lg_sa(N1 > K0 ? N1 : K0) * 4;
@@ -219,6 +267,7 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
     int ahead = 0;                                             // thread 0: the ticket drawn ahead
     if (tid == 0) ahead = __hip_atomic_fetch_add(&a.counters[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int cur_phase = 0, pending = 0;                            // finished items of cur_phase not yet reported
+    int aborted = 0;                                           // this workgroup leaves because a bounded wait ran out
     for (;;) {
         int it = lg_take(a.counters, total, &s_ticket, ahead);
         const int ph = it < 0 ? 4 : it < n0 ? 0 : it < n0 + n1 ? 1 : it < n0 + n1 + n2 ? 2 : 3;
@@ -229,7 +278,10 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
         }
         if (it < 0) break;
         if (ph > phase_ok) {                                   // the first item of a later phase: everything before it is complete
-            if (!lg_wait_phase(a.counters, ph - 1, ph == 1 ? n0 : ph == 2 ? n1 : n2, a.status, &s_ok)) break;
+            if (!lg_wait_phase(a.counters, ph - 1, ph == 1 ? n0 : ph == 2 ? n1 : n2, a.status, &s_ok)) {
+                aborted = 1;
+                break;
+            }
             phase_ok = ph;
         }
         lg_draw_ahead(a.counters, ahead);
@@ -376,14 +428,30 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
     // ---- re-arm the queue: the last workgroup to leave (nobody holds an item or polls a counter by then) ------------------------------
     __syncthreads();
     if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(&a.counters[LG_LEFT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == (int)gridDim.x - 1) {
-            __hip_atomic_store(&a.counters[0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) __hip_atomic_store(&a.counters[LG_DONE + k], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&a.counters[LG_LEFT], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&a.counters[LG_ABORT], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int mine = 1 + (aborted ? 1 << 16 : 0);
+        const int all = __hip_atomic_fetch_add(&a.counters[LG_LEFT], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + mine;
+        s_ticket = (all & 0xffff) == (int)gridDim.x ? 1 + (all >> 16) : 0;      // 0: not the last; 1: last, complete; > 1: last, aborted
+    }
+    __syncthreads();
+    const int last = __builtin_amdgcn_readfirstlane(s_ticket);
+    if (last == 0) return;
+    if (a.memo) {
+        // every item is done (or the launch was aborted): the outputs now belong to THIS inp.  Snapshot first, `valid` behind it;
+        // both are read by the next check launch only.
+        if (last == 1) {
+            const uint4* src = reinterpret_cast<const uint4*>(a.inp);
+            uint4* dst = reinterpret_cast<uint4*>(a.snap);
+            for (int i = tid; i < C * K0 / 4; i += LG_THR) dst[i] = src[i];
         }
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(&a.memo[LGM_VALID], last == 1 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 0) {
+        __hip_atomic_store(&a.counters[0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) __hip_atomic_store(&a.counters[LG_DONE + k], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.counters[LG_LEFT], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&a.counters[LG_ABORT], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -406,10 +474,16 @@ extern "C" int mgnns_label_gcn_supported(int C, int K0, int N1, int N2, int spli
     return tile + (size_t)8 * LG_MAXC * 8 + 16 <= 160 * 1024 ? 1 : 0;
 }
 
-extern "C" int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int K0, int split, const void* w1a, const void* w1b,
-                                   int N1, const void* w2a, const void* w2b, int N2, float* G, void* Gp_hi, void* Gp_lo,
-                                   const float* label_query, int NLQ, const float* wq, const float* bq, int HQ, float* Q,
-                                   void* scratch, size_t scratch_bytes, int grid, mgnns_stream_t stream) {
+// 256 B of words (valid, hit, arrival) + the snapshot of inp
+extern "C" size_t mgnns_label_gcn_memo_bytes(int C, int K0) {
+    if (C <= 0 || K0 <= 0) return 0;
+    return 256 + ((size_t)C * K0 * 4 + 255) / 256 * 256;
+}
+
+static int lg_launch(const float* A, int C, const float* inp, int K0, int split, const void* w1a, const void* w1b,
+                     int N1, const void* w2a, const void* w2b, int N2, float* G, void* Gp_hi, void* Gp_lo,
+                     const float* label_query, int NLQ, const float* wq, const float* bq, int HQ, float* Q,
+                     void* scratch, size_t scratch_bytes, void* memo, size_t memo_bytes, int grid, mgnns_stream_t stream) {
     MG_REQUIRE(A && inp && w1a && w2a && G && scratch, "mgnns_label_gcn_fwd: null pointer");
     MG_REQUIRE(C > 0 && C <= LG_MAXC, "mgnns_label_gcn_fwd: C=%d unsupported (1..%d)", C, LG_MAXC);
     MG_REQUIRE(K0 > 0 && K0 % 4 == 0 && K0 <= 1024, "mgnns_label_gcn_fwd: in_channel=%d must be a multiple of 4, <= 1024", K0);
@@ -423,6 +497,8 @@ extern "C" int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int 
                scratch_bytes);
     MG_REQUIRE(mg_aligned16(inp) && mg_aligned16(G) && mg_aligned16(w1a) && mg_aligned16(w2a), "mgnns_label_gcn_fwd: inp / G / weights must be 16-byte aligned");
     MG_REQUIRE((size_t)C * N2 * 4 < ((size_t)1 << 31), "mgnns_label_gcn_fwd: C*N2 too large");
+    MG_REQUIRE(!memo || (memo_bytes >= mgnns_label_gcn_memo_bytes(C, K0) && ((uintptr_t)memo & 255) == 0),
+               "mgnns_label_gcn_memo_fwd: memo of %zu B (256-byte aligned) needed, %zu given", mgnns_label_gcn_memo_bytes(C, K0), memo_bytes);
     auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
     unsigned char* p = reinterpret_cast<unsigned char*>(scratch);
     LgArgs a;
@@ -437,6 +513,8 @@ extern "C" int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int 
     a.A = A; a.C = C; a.inp = inp; a.K0 = K0; a.w1a = w1a; a.w1b = w1b; a.N1 = N1; a.w2a = w2a; a.w2b = w2b; a.N2 = N2; a.G = G;
     a.gp_hi = reinterpret_cast<unsigned short*>(Gp_hi); a.gp_lo = reinterpret_cast<unsigned short*>(Gp_lo);
     a.lq = label_query; a.wq = wq; a.bq = bq; a.NLQ = NLQ; a.HQ = HQ; a.Q = Q;
+    a.memo = reinterpret_cast<int*>(memo);
+    a.snap = memo ? reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(memo) + 256) : nullptr;
     const int kmax = N1 > K0 ? N1 : K0;
     const size_t tile = split ? (size_t)2 * 16 * lg_sc(kmax) * 16 : (size_t)16 * lg_sa(kmax) * 4;
     const size_t lds = tile + (size_t)8 * LG_MAXC * 8 + 16;
@@ -457,6 +535,14 @@ extern "C" int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int 
     a.rows_d = per_item(C);
     a.outs_q = per_item(NLQ * HQ > 0 ? NLQ * HQ : 1);
     a.pcs3 = per_item(((C + 15) / 16) * 16 * (N2 / 256));
+    if (memo) {
+        // C * K0 / 4 16-byte words against the snapshot: 1024 per workgroup, at most 32 workgroups (a few microseconds at C = 365)
+        const int n4 = C * K0 / 4;
+        const int cgrid = n4 / 1024 < 1 ? 1 : n4 / 1024 > 32 ? 32 : n4 / 1024;
+        hipLaunchKernelGGL(label_gcn_memo_check, dim3(cgrid), dim3(LGM_THR), 0, (hipStream_t)stream, reinterpret_cast<const uint4*>(inp),
+                           reinterpret_cast<const uint4*>(a.snap), n4, a.memo);
+        MG_CHECK_LAUNCH("mgnns_label_gcn_memo_fwd");
+    }
     if (split) {
         MG_DYN_LDS(label_gcn_kernel<true>, 160 * 1024);
         hipLaunchKernelGGL(label_gcn_kernel<true>, dim3(grid), dim3(LG_THR), lds, (hipStream_t)stream, a);
@@ -466,4 +552,22 @@ extern "C" int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int 
     }
     MG_CHECK_LAUNCH("mgnns_label_gcn_fwd");
     return 0;
+}
+
+extern "C" int mgnns_label_gcn_fwd(const float* A, int C, const float* inp, int K0, int split, const void* w1a, const void* w1b,
+                                   int N1, const void* w2a, const void* w2b, int N2, float* G, void* Gp_hi, void* Gp_lo,
+                                   const float* label_query, int NLQ, const float* wq, const float* bq, int HQ, float* Q,
+                                   void* scratch, size_t scratch_bytes, int grid, mgnns_stream_t stream) {
+    return lg_launch(A, C, inp, K0, split, w1a, w1b, N1, w2a, w2b, N2, G, Gp_hi, Gp_lo, label_query, NLQ, wq, bq, HQ, Q, scratch,
+                     scratch_bytes, nullptr, 0, grid, stream);
+}
+
+extern "C" int mgnns_label_gcn_memo_fwd(const float* A, int C, const float* inp, int K0, int split, const void* w1a, const void* w1b,
+                                        int N1, const void* w2a, const void* w2b, int N2, float* G, void* Gp_hi, void* Gp_lo,
+                                        const float* label_query, int NLQ, const float* wq, const float* bq, int HQ, float* Q,
+                                        void* scratch, size_t scratch_bytes, void* memo, size_t memo_bytes, int grid,
+                                        mgnns_stream_t stream) {
+    MG_REQUIRE(memo, "mgnns_label_gcn_memo_fwd: null memo");
+    return lg_launch(A, C, inp, K0, split, w1a, w1b, N1, w2a, w2b, N2, G, Gp_hi, Gp_lo, label_query, NLQ, wq, bq, HQ, Q, scratch,
+                     scratch_bytes, memo, memo_bytes, grid, stream);
 }

@@ -315,10 +315,21 @@ def label_gcn_pack(w1, w2, split):
 LABEL_GCN_GRID = int(os.environ.get("MGNNS_LGCN_GRID", "0"))
 
 
-def label_gcn(A, inp, packed, want_packed_g=False, query=None, grid=0):
+def label_gcn_memo_flag(memo, want_packed_g=False):
+    """The verdict of the last memo launch on the current stream / scratch epoch: 1 = hit (nothing was computed), 0 = miss.
+    Synchronises (a test's and a tool's question, not the forward's)."""
+    st = memo[_scratch_key() + (bool(want_packed_g),)]
+    return int(st["state"][:12].view(torch.int32)[1].item())
+
+
+def label_gcn(A, inp, packed, want_packed_g=False, query=None, grid=0, memo=None):
     """One channel's whole label GCN in one persistent launch (mgnns_label_gcn_fwd): gen_adj + GraphConvolution x 2 (+ the
     label query projection).  A [C,C]; inp [C,K0]; packed = label_gcn_pack(...) (also carries this channel's scratch);
-    query = (label_query [NLQ,K0], w_q.weight [HQ,K0], w_q.bias or None).  -> (G [C,N2], (Gp_hi, Gp_lo) or None, Q or None)."""
+    query = (label_query [NLQ,K0], w_q.weight [HQ,K0], w_q.bias or None).  -> (G [C,N2], (Gp_hi, Gp_lo) or None, Q or None).
+    memo: a dict the CALLER owns for exactly one set of weights (A, packed, query): the outputs then live in it, per (scratch
+    epoch, launch stream) like the scratch, and a launch whose inp equals -- bit for bit, decided on the device -- the inp they
+    were computed from computes nothing and returns them again (mgnns_label_gcn_memo_fwd).  After changing a weight pass a
+    fresh dict.  None: today's launch into fresh outputs."""
     _chk(A, "A", ndim=2)
     _chk(inp, "inp", ndim=2)
     C = A.shape[0]
@@ -338,12 +349,25 @@ def label_gcn(A, inp, packed, want_packed_g=False, query=None, grid=0):
             packed.setdefault("_retired", []).append(ws)     # a captured hipGraph may still hold its address: never freed
         ws = zeros_bytes(need, A.device)[:need]                           # counters (first 256 B) start at zero
         _scratch_slot_put(slot, key, ws)
-    G = torch.empty(C, N2, device=A.device, dtype=torch.float32)
-    gh = gl = None
-    if want_packed_g:
-        n = L.mgnns_packed_bf16_weight_bytes(C, N2)
-        gh = torch.empty(n, dtype=torch.uint8, device=A.device)
-        gl = torch.empty(n, dtype=torch.uint8, device=A.device)
+    st = None
+    if memo is not None and _TIMER is not None and _TIMER.wants("mgnns_label_gcn_fwd"):
+        memo = None                      # a timed launch is a computing one: a roofline row of the hit path would say nothing
+    if memo is not None:
+        mkey = key + (bool(want_packed_g),)
+        st = memo.get(mkey)
+        if st is None:
+            mneed = L.mgnns_label_gcn_memo_bytes(C, packed["K0"])
+            st = {"state": zeros_bytes(mneed, A.device)[:mneed]}          # valid = 0: the first launch computes
+            _scratch_slot_put(memo, mkey, st)
+    if st is not None and "G" in st:
+        G, gh, gl = st["G"], st["gh"], st["gl"]
+    else:
+        G = torch.empty(C, N2, device=A.device, dtype=torch.float32)
+        gh = gl = None
+        if want_packed_g:
+            n = L.mgnns_packed_bf16_weight_bytes(C, N2)
+            gh = torch.empty(n, dtype=torch.uint8, device=A.device)
+            gl = torch.empty(n, dtype=torch.uint8, device=A.device)
     lq = wq = bq = Q = None
     nlq = hq = 0
     if query is not None:
@@ -355,7 +379,17 @@ def label_gcn(A, inp, packed, want_packed_g=False, query=None, grid=0):
         if bq is not None:
             _chk(bq, "w_q.bias", ndim=1)
         nlq, hq = lq.shape[0], wq.shape[0]
-        Q = torch.empty(nlq, hq, device=A.device, dtype=torch.float32)
+        Q = st["Q"] if st is not None and "G" in st else torch.empty(nlq, hq, device=A.device, dtype=torch.float32)
+    if st is not None:
+        if "G" in st and (Q is None) != (st["Q"] is None):
+            raise ValueError("label_gcn: one memo serves one query (present or absent)")
+        st.update(G=G, gh=gh, gl=gl, Q=Q)
+        mem = st["state"]
+        _launch("mgnns_label_gcn_fwd", ("mgnns_label_gcn_fwd", C, packed["split"]), L.mgnns_label_gcn_memo_fwd, _p(A), C, _p(inp),
+                packed["K0"], 1 if packed["split"] else 0, _p(packed["w1"][0]), _p(packed["w1"][1]), N1, _p(packed["w2"][0]),
+                _p(packed["w2"][1]), N2, _p(G), _p(gh), _p(gl), _p(lq), nlq, _p(wq), _p(bq), hq, _p(Q), _p(ws), ws.numel(), _p(mem),
+                mem.numel(), int(grid) or LABEL_GCN_GRID, _stream())
+        return G, ((gh, gl) if want_packed_g else None), Q
     _launch("mgnns_label_gcn_fwd", ("mgnns_label_gcn_fwd", C, packed["split"]), L.mgnns_label_gcn_fwd, _p(A), C, _p(inp), packed["K0"],
             1 if packed["split"] else 0, _p(packed["w1"][0]), _p(packed["w1"][1]), N1, _p(packed["w2"][0]), _p(packed["w2"][1]), N2,
             _p(G), _p(gh), _p(gl), _p(lq), nlq, _p(wq), _p(bq), hq, _p(Q), _p(ws), ws.numel(), int(grid) or LABEL_GCN_GRID, _stream())
