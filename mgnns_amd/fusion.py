@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .derived import derived
 from . import train as _train
 
 
@@ -182,11 +183,7 @@ class MultiHeadAttention(nn.Module):
         or "split"), rebuilt when either weight changes."""
         form = ops.MHA_CORE if form is None else form
         wk, wv = self.w_ks.weight, self.w_vs.weight
-        key = (wk.data_ptr(), wk._version, wv.data_ptr(), wv._version, str(wk.device))
-        if self._wp is None or self._wp[0] != key:
-            ops.retire(self._wp)                # a live capture may hold the old packs' addresses
-            self._wp = (key, {})
-        packs = self._wp[1]
+        packs = derived(vars(self), "_wp", (wk, wv), dict, park=ops.retire)      # one dict per weight version, filled per form
         if form not in packs:
             if form == "split":
                 packs[form] = ops.pack_kv_weights_split(wk.detach(), wv.detach(), self.n_head, self.d_k)
@@ -242,58 +239,39 @@ class MyMultiHeadAttention(nn.Module):
         return enc_output.squeeze(1), enc_slf_attn
 
 
-def _versions(*params):
-    return tuple((p.data_ptr(), p._version) for p in params) + (str(params[0].device),)
+def _layer_pack(layer, slot, sources, build):
+    """One layer-level derived value, kept on the layer as attribute `slot`; superseded entries go to the park of ops.retire
+    (derived.derived; DESIGN.md, "Derived packs and launch scratch")."""
+    return derived(vars(layer), slot, sources, build, park=ops.retire)
 
 
-def _tail_pack(layer):
-    """Pre-packed weights of one layer's fused tail, rebuilt when any of them changes."""
+def _tail_pack(layer, slot="_tail_cache", pack=ops.pack_weight_f32, suffix="_wp"):
+    """Pre-packed weights of one layer's fused tail: fc, w_1 and w_2 in the fragment-major fp32 layout under "fc_wp", "w1_wp",
+    "w2_wp", biases and LayerNorm parameters as they are."""
     a, f = layer.slf_attn, layer.pos_ffn
     ps = (a.fc.weight, a.fc.bias, a.layer_norm.gamma, a.layer_norm.beta, f.w_1.weight, f.w_1.bias, f.w_2.weight,
           f.w_2.bias, f.layer_norm.gamma, f.layer_norm.beta)
-    key = _versions(*ps)
-    hit = getattr(layer, "_tail_cache", None)
-    if hit is None or hit[0] != key:
-        d = {"fc_wp": ops.pack_weight_f32(a.fc.weight.detach()), "fc_b": a.fc.bias.detach(),
-             "g1": a.layer_norm.gamma.detach(), "be1": a.layer_norm.beta.detach(),
-             "w1_wp": ops.pack_weight_f32(f.w_1.weight.detach().view(f.w_1.out_channels, f.w_1.in_channels)),
-             "b1": f.w_1.bias.detach(),
-             "w2_wp": ops.pack_weight_f32(f.w_2.weight.detach().view(f.w_2.out_channels, f.w_2.in_channels)),
-             "b2": f.w_2.bias.detach(), "g2": f.layer_norm.gamma.detach(), "be2": f.layer_norm.beta.detach()}
-        hit = (key, d)
-        ops.retire(getattr(layer, "_tail_cache", None))      # a live capture may hold the old pack's addresses
-        layer._tail_cache = hit
-    return hit[1]
+    return _layer_pack(layer, slot, ps, lambda: {
+        "fc" + suffix: pack(a.fc.weight.detach()), "fc_b": a.fc.bias.detach(),
+        "g1": a.layer_norm.gamma.detach(), "be1": a.layer_norm.beta.detach(),
+        "w1" + suffix: pack(f.w_1.weight.detach().view(f.w_1.out_channels, f.w_1.in_channels)), "b1": f.w_1.bias.detach(),
+        "w2" + suffix: pack(f.w_2.weight.detach().view(f.w_2.out_channels, f.w_2.in_channels)), "b2": f.w_2.bias.detach(),
+        "g2": f.layer_norm.gamma.detach(), "be2": f.layer_norm.beta.detach()})
 
 
 def _tail_pack_bf16(layer):
-    a, f = layer.slf_attn, layer.pos_ffn
-    ps = (a.fc.weight, a.fc.bias, a.layer_norm.gamma, a.layer_norm.beta, f.w_1.weight, f.w_1.bias, f.w_2.weight,
-          f.w_2.bias, f.layer_norm.gamma, f.layer_norm.beta)
-    key = _versions(*ps)
-    hit = getattr(layer, "_tail_cache_bf16", None)
-    if hit is None or hit[0] != key:
-        d = {"fc": ops.pack_weight_bf16_split(a.fc.weight.detach()), "fc_b": a.fc.bias.detach(),
-             "g1": a.layer_norm.gamma.detach(), "be1": a.layer_norm.beta.detach(),
-             "w1": ops.pack_weight_bf16_split(f.w_1.weight.detach().view(f.w_1.out_channels, f.w_1.in_channels)),
-             "b1": f.w_1.bias.detach(),
-             "w2": ops.pack_weight_bf16_split(f.w_2.weight.detach().view(f.w_2.out_channels, f.w_2.in_channels)),
-             "b2": f.w_2.bias.detach(), "g2": f.layer_norm.gamma.detach(), "be2": f.layer_norm.beta.detach()}
-        hit = (key, d)
-        ops.retire(getattr(layer, "_tail_cache_bf16", None))      # a live capture may hold the old pack's addresses
-        layer._tail_cache_bf16 = hit
-    return hit[1]
+    """The same with split-bf16 (hi, lo) pairs under "fc", "w1", "w2"."""
+    return _tail_pack(layer, "_tail_cache_bf16", ops.pack_weight_bf16_split, "")
+
+
+def _wq_pack(layer, slot="_wq_cache", pack=ops.pack_weight_f32):
+    a = layer.slf_attn
+    return _layer_pack(layer, slot, (a.w_qs.weight, a.w_qs.bias),
+                       lambda: (pack(a.w_qs.weight.detach()), a.w_qs.bias.detach(), a.w_qs.out_features))
 
 
 def _wq_pack_bf16(layer):
-    a = layer.slf_attn
-    key = _versions(a.w_qs.weight, a.w_qs.bias)
-    hit = getattr(layer, "_wq_cache_bf16", None)
-    if hit is None or hit[0] != key:
-        hit = (key, (ops.pack_weight_bf16_split(a.w_qs.weight.detach()), a.w_qs.bias.detach(), a.w_qs.out_features))
-        ops.retire(getattr(layer, "_wq_cache_bf16", None))      # a live capture may hold the old pack's addresses
-        layer._wq_cache_bf16 = hit
-    return hit[1]
+    return _wq_pack(layer, "_wq_cache_bf16", ops.pack_weight_bf16_split)
 
 
 def _use_folded_bf16(a):
@@ -301,14 +279,11 @@ def _use_folded_bf16(a):
     return a.attention == 'folded' and a.precision == 'bf16' and not a.is_regu
 
 
-def composed_query_map(layer):
-    """((hi, lo), bias, H*D) of u_h = (W_k,h^T W_q,h) x + W_k,h^T b_q,h for every head h, stacked [H*D, D]: what a producer of x
-    (the previous layer's tail, a channel tail) applies instead of w_qs so that the folded attention starts from u.  Built in
-    fp32 (ops.matmul) once per weight version (submodules.py:64-72: q = w_qs(x), k = w_ks(bank))."""
+def _composed_query(layer):
+    """(composed_query_map(layer), the fp32 matrix it was packed from), built in fp32 (ops.matmul) once per weight version."""
     a = layer.slf_attn
-    key = _versions(a.w_qs.weight, a.w_qs.bias, a.w_ks.weight)
-    hit = getattr(layer, "_uq_cache", None)
-    if hit is None or hit[0] != key:
+
+    def build():
         H, dk = a.n_head, a.d_k
         wq, bq, wk = a.w_qs.weight.detach(), a.w_qs.bias.detach(), a.w_ks.weight.detach()
         rows, bias = [], []
@@ -317,15 +292,19 @@ def composed_query_map(layer):
             rows.append(ops.matmul(wkt, wq[h * dk:(h + 1) * dk].contiguous()))               # [D, D]
             bias.append(ops.matmul(wkt, bq[h * dk:(h + 1) * dk].reshape(dk, 1).contiguous()).reshape(-1))
         m = torch.cat(rows, 0).contiguous()
-        hit = (key, (ops.pack_weight_bf16_split(m), torch.cat(bias).contiguous(), m.shape[0]), m)
-        ops.retire(getattr(layer, "_uq_cache", None))      # a live capture may hold the old pack's addresses
-        layer._uq_cache = hit
-    return hit[1]
+        return (ops.pack_weight_bf16_split(m), torch.cat(bias).contiguous(), m.shape[0]), m
+    return _layer_pack(layer, "_uq_cache", (a.w_qs.weight, a.w_qs.bias, a.w_ks.weight), build)
+
+
+def composed_query_map(layer):
+    """((hi, lo), bias, H*D) of u_h = (W_k,h^T W_q,h) x + W_k,h^T b_q,h for every head h, stacked [H*D, D]: what a producer of x
+    (the previous layer's tail, a channel tail) applies instead of w_qs so that the folded attention starts from u
+    (submodules.py:64-72: q = w_qs(x), k = w_ks(bank))."""
+    return _composed_query(layer)[0]
 
 
 def _composed_query_weight(layer):
-    composed_query_map(layer)
-    return layer._uq_cache[2]
+    return _composed_query(layer)[1]
 
 
 def _tail_pack_folded(layer):
@@ -334,9 +313,8 @@ def _tail_pack_folded(layer):
     a, f = layer.slf_attn, layer.pos_ffn
     ps = (a.fc.weight, a.fc.bias, a.w_vs.weight, a.w_vs.bias, a.layer_norm.gamma, a.layer_norm.beta, f.w_1.weight, f.w_1.bias,
           f.w_2.weight, f.w_2.bias, f.layer_norm.gamma, f.layer_norm.beta)
-    key = _versions(*ps)
-    hit = getattr(layer, "_tail_cache_folded", None)
-    if hit is None or hit[0] != key:
+
+    def build():
         H, dv = a.n_head, a.d_v
         fc, wv = a.fc.weight.detach(), a.w_vs.weight.detach()
         cols = [ops.matmul(fc[:, h * dv:(h + 1) * dv].contiguous(), wv[h * dv:(h + 1) * dv].contiguous()) for h in range(H)]
@@ -345,21 +323,8 @@ def _tail_pack_folded(layer):
         d = dict(_tail_pack_bf16(layer))
         d["fc"] = ops.pack_weight_bf16_split(n)
         d["fc_b"] = nb
-        hit = (key, d)
-        ops.retire(getattr(layer, "_tail_cache_folded", None))      # a live capture may hold the old pack's addresses
-        layer._tail_cache_folded = hit
-    return hit[1]
-
-
-def _wq_pack(layer):
-    a = layer.slf_attn
-    key = _versions(a.w_qs.weight, a.w_qs.bias)
-    hit = getattr(layer, "_wq_cache", None)
-    if hit is None or hit[0] != key:
-        hit = (key, (ops.pack_weight_f32(a.w_qs.weight.detach()), a.w_qs.bias.detach(), a.w_qs.out_features))
-        ops.retire(getattr(layer, "_wq_cache", None))
-        layer._wq_cache = hit
-    return hit[1]
+        return d
+    return _layer_pack(layer, "_tail_cache_folded", ps, build)
 
 
 def first_query_pack(layers):

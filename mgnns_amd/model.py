@@ -19,6 +19,7 @@ from torch.nn import Parameter
 from . import _lib, ops
 from . import train as _train
 from .adjacency import gen_A, gen_adj_csr
+from .derived import derived
 from .fusion import (MemoryBank, MultiHeadAttention, MyAnotherMultiHeadAttention, MyMultiHeadAttention, first_query, make_mask_plan,
                      mask_plan_applies,
                      first_query_pack, first_query_pack_bf16, run_stack)
@@ -366,35 +367,33 @@ class Multi_GCN_Multihead_Att(nn.Module):
         # reference order: cat(enc_final_state[-1] (reverse), enc_final_state[-2] (forward)) (MODEL:392)
         return memory_bank, torch.cat((bwd_last, fwd_last), 1)
 
-    def _wt(self, lin):
-        """Linear(2048, 300).weight transposed + padded for the bank kernel, cached per weight version."""
+    def _derived(self, slot, sources, build, extra=()):
+        """self._wt_cache[slot], rebuilt when a source changes (derived.derived; DESIGN.md, "Derived packs and launch scratch")."""
+        return derived(self._wt_cache, slot, sources, build, extra, self._park)
+
+    def _park(self, old):
+        """The model-level park: a superseded entry of _wt_cache is kept while a captured hipGraph of this model exists
+        (GraphedForward counts itself in _live_graphs and empties the park when the last one goes)."""
+        if getattr(self, "_live_graphs", 0) > 0:
+            if not hasattr(self, "_wt_retired"):
+                self._wt_retired = []
+            self._wt_retired.append(old)
+
+    def _lin_pack(self, lin, slot, pack):
         w = lin.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        hit = self._wt_cache.get(id(lin))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.transpose_pad(w.detach().contiguous(), ops.IMGBANK_LDW))
-            self._cache_put(id(lin), hit)
-        return hit[1]
+        return self._derived(slot, (w,), lambda: pack(w.detach().contiguous()))
+
+    def _wt(self, lin):
+        """Linear(2048, 300).weight transposed + padded for the bank kernel."""
+        return self._lin_pack(lin, id(lin), lambda w: ops.transpose_pad(w, ops.IMGBANK_LDW))
 
     def _wp(self, lin):
         """The same weight in the MFMA-fragment-major bf16 layout of the bf16 bank kernel."""
-        w = lin.weight
-        key = (w.data_ptr(), w._version, str(w.device), 'bf16')
-        hit = self._wt_cache.get((id(lin), 'bf16'))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.pack_imgbank_weights_bf16(w.detach().contiguous()))
-            self._cache_put((id(lin), 'bf16'), hit)
-        return hit[1]
+        return self._lin_pack(lin, (id(lin), 'bf16'), ops.pack_imgbank_weights_bf16)
 
     def _wp_split(self, lin):
         """The same weight as split-bf16 (hi, lo) fragment-major buffers for the bf16x3 bank kernel."""
-        w = lin.weight
-        key = (w.data_ptr(), w._version, str(w.device), 'split')
-        hit = self._wt_cache.get((id(lin), 'split'))
-        if hit is None or hit[0] != key:
-            hit = (key, ops.pack_weight_bf16_split(w.detach().contiguous()))
-            self._cache_put((id(lin), 'split'), hit)
-        return hit[1]
+        return self._lin_pack(lin, (id(lin), 'split'), ops.pack_weight_bf16_split)
 
     def _img_bank_and_pool(self, feats, lin):
         """-> (MemoryBank, pooled [B,2048]); one pass over the feature map."""
@@ -437,102 +436,56 @@ class Multi_GCN_Multihead_Att(nn.Module):
         ops.stamp("  label GCN end")
         return G
 
-    def _cache_put(self, key, value):
-        """Replace a derived-weights cache entry.  While a captured hipGraph of this model exists (GraphedForward counts
-        itself in _live_graphs) the superseded entry is parked, not freed: the graph holds raw addresses of its buffers --
-        packed weights, the persistent launches' scratch with their queue counters -- and a replay after set_precision() /
-        load_state_dict() must not read recycled memory.  The park empties when the last graph goes."""
-        old = self._wt_cache.get(key)
-        if old is not None and getattr(self, "_live_graphs", 0) > 0:
-            if not hasattr(self, "_wt_retired"):
-                self._wt_retired = []
-            self._wt_retired.append(old)
-        self._wt_cache[key] = value
-
-    def _tail_pack(self, attention, linear_5, x_linear):
-        """Packed weights of one channel's fused label-attention tail, rebuilt when any of them changes:
-        w_k / w_v / x_linear in the fragment-major fp32 layout, fc and linear_5 composed into one map (no non-linearity
-        between them, MODEL:131 -> 477): Wc = W5 . Wfc, bc = W5 . b_fc + b5."""
+    def _tail_pack(self, attention, linear_5, x_linear, kind='tail', pack=ops.pack_weight_f32):
+        """Packed weights of one channel's fused label-attention tail: w_k / w_v / x_linear in the fragment-major fp32 layout,
+        fc and linear_5 composed into one map (no non-linearity between them, MODEL:131 -> 477): Wc = W5 . Wfc,
+        bc = W5 . b_fc + b5."""
         ps = (attention.w_k.weight, attention.w_k.bias, attention.w_v.weight, attention.w_v.bias, attention.fc.weight,
               attention.fc.bias, linear_5.weight, linear_5.bias, x_linear.weight, x_linear.bias)
-        key = tuple((p_.data_ptr(), p_._version) for p_ in ps) + (str(ps[0].device),)
-        hit = self._wt_cache.get((id(attention), 'tail'))
-        if hit is None or hit[0] != key:
+
+        def build():
             w5 = linear_5.weight.detach()
             wc = ops.matmul(w5.contiguous(), attention.fc.weight.detach().contiguous())               # [N5, hid]
             bc = ops.linear(attention.fc.bias.detach()[None, :].contiguous(), w5, linear_5.bias.detach())[0]
-            d = {"wk": ops.pack_weight_f32(attention.w_k.weight.detach()), "bk": attention.w_k.bias.detach(),
-                 "wv": ops.pack_weight_f32(attention.w_v.weight.detach()), "bv": attention.w_v.bias.detach(),
-                 "wc": ops.pack_weight_f32(wc), "bc": bc.contiguous(), "n5": linear_5.out_features,
-                 "xl": ops.pack_weight_f32(x_linear.weight.detach()), "bxl": x_linear.bias.detach(),
-                 "n_out": x_linear.out_features, "C": attention.w_k.in_features, "_src": ps}
-            hit = (key, d)
-            self._cache_put((id(attention), 'tail'), hit)
-        return hit[1]
+            return {"wk": pack(attention.w_k.weight.detach()), "bk": attention.w_k.bias.detach(),
+                    "wv": pack(attention.w_v.weight.detach()), "bv": attention.w_v.bias.detach(),
+                    "wc": pack(wc), "bc": bc.contiguous(), "n5": linear_5.out_features,
+                    "xl": pack(x_linear.weight.detach()), "bxl": x_linear.bias.detach(),
+                    "n_out": x_linear.out_features, "C": attention.w_k.in_features}
+        return self._derived((id(attention), kind), ps, build)
+
+    def _tail_pack_bf16(self, attention, linear_5, x_linear):
+        """The same weights as split-bf16 fragment-major (hi, lo) buffers for the bf16-mode fused tail."""
+        return self._tail_pack(attention, linear_5, x_linear, 'tail_bf16', lambda w: ops.pack_weight_bf16_split(w.contiguous()))
 
     def _lgcn_pack(self, tag):
         """Packed GraphConvolution weights of one channel for the persistent label-GCN launch (exact fp32 fragments in fp32
         mode, split-bf16 pairs in bf16 mode), rebuilt when a weight or the precision changes; carries the launch's scratch."""
-        gc1, gc2 = (self.gc1, self.gc2)
-        ps = (gc1.weight, gc2.weight)
+        w1, w2 = self.gc1.weight, self.gc2.weight
         split = self.precision in ('bf16', 'bf16x3')
-        key = tuple((p_.data_ptr(), p_._version) for p_ in ps) + (str(ps[0].device), split)
-        hit = self._wt_cache.get(('lgcn', tag))
-        if hit is None or hit[0] != key:
-            d = ops.label_gcn_pack(gc1.weight.detach(), gc2.weight.detach(), split)
-            d["_src"] = ps
-            hit = (key, d)
-            self._cache_put(('lgcn', tag), hit)
-        return hit[1]
+        return self._derived(('lgcn', tag), (w1, w2), lambda: ops.label_gcn_pack(w1.detach(), w2.detach(), split), (split,))
 
     def _lgcn_memo(self, tag, attention, A, pack):
         """The memo of one channel's persistent label-GCN launch (ops.label_gcn(memo=...)): nothing that launch computes depends
         on the batch, so its outputs (G, the packed image of G, the projected label query) are kept, per scratch epoch and launch
         stream, and a forward recomputes them only when the DEVICE finds inp[0] changed bit for bit -- inp is a forward argument,
-        and a replayed hipGraph runs no host code.  The weights are validated HERE like every derived pack: the memo is keyed on
-        the versions of A, gc1 / gc2 (through their pack), label_query and w_q, and a change hands the launch an empty memo.  A
-        captured graph holds its memo by address, so it freezes these exactly as it freezes the weight packs."""
+        and a replayed hipGraph runs no host code.  The weights are validated HERE like every derived pack: the memo derives
+        from A, gc1 / gc2 (through their pack, which it holds so that id(pack) stays that pack's), label_query and w_q, and a
+        change hands the launch an empty memo.  A captured graph holds its memo by address, so it freezes these exactly as it
+        freezes the weight packs."""
         ps = (A, self.label_query, attention.w_q.weight, attention.w_q.bias)
-        key = tuple((p_.data_ptr(), p_._version) for p_ in ps if p_ is not None) + (id(pack), str(A.device))
-        hit = self._wt_cache.get(('lgcn_memo', tag))
-        if hit is None or hit[0] != key:
-            hit = (key, {"_src": ps + (pack,)})
-            self._cache_put(('lgcn_memo', tag), hit)
-        return hit[1]
+        return self._derived(('lgcn_memo', tag), ps, lambda: {"_pack": pack}, (id(pack),))
 
     def _head_pack(self):
         """multi_linear_2 . multi_linear_1 as one [num_labels, 1200] map (MODEL:563-566: only dropout between them, the
-        identity in eval), rebuilt when either changes: Wc = W2 . W1, bc = W2 . b1 + b2."""
+        identity in eval): Wc = W2 . W1, bc = W2 . b1 + b2."""
         l1, l2 = self.multi_linear_1, self.multi_linear_2
-        ps = (l1.weight, l1.bias, l2.weight, l2.bias)
-        key = tuple((p_.data_ptr(), p_._version) for p_ in ps) + (str(ps[0].device),)
-        hit = self._wt_cache.get('head')
-        if hit is None or hit[0] != key:
+
+        def build():
             wc = ops.matmul(l2.weight.detach().contiguous(), l1.weight.detach().contiguous())                # [NL, 1200]
             bc = ops.linear(l1.bias.detach()[None, :].contiguous(), l2.weight.detach(), l2.bias.detach())[0]
-            hit = (key, (wc.contiguous(), bc.contiguous(), ps))
-            self._cache_put('head', hit)
-        return hit[1][0], hit[1][1]
-
-    def _tail_pack_bf16(self, attention, linear_5, x_linear):
-        """The same weights as split-bf16 fragment-major (hi, lo) buffers for the bf16-mode fused tail."""
-        ps = (attention.w_k.weight, attention.w_k.bias, attention.w_v.weight, attention.w_v.bias, attention.fc.weight,
-              attention.fc.bias, linear_5.weight, linear_5.bias, x_linear.weight, x_linear.bias)
-        key = tuple((p_.data_ptr(), p_._version) for p_ in ps) + (str(ps[0].device),)
-        hit = self._wt_cache.get((id(attention), 'tail_bf16'))
-        if hit is None or hit[0] != key:
-            w5 = linear_5.weight.detach()
-            wc = ops.matmul(w5.contiguous(), attention.fc.weight.detach().contiguous())
-            bc = ops.linear(attention.fc.bias.detach()[None, :].contiguous(), w5, linear_5.bias.detach())[0]
-            sp = lambda w: ops.pack_weight_bf16_split(w.contiguous())
-            d = {"wk": sp(attention.w_k.weight.detach()), "bk": attention.w_k.bias.detach(),
-                 "wv": sp(attention.w_v.weight.detach()), "bv": attention.w_v.bias.detach(),
-                 "wc": sp(wc), "bc": bc.contiguous(), "n5": linear_5.out_features,
-                 "xl": sp(x_linear.weight.detach()), "bxl": x_linear.bias.detach(),
-                 "n_out": x_linear.out_features, "C": attention.w_k.in_features, "_src": ps}
-            hit = (key, d)
-            self._cache_put((id(attention), 'tail_bf16'), hit)
-        return hit[1]
+            return wc.contiguous(), bc.contiguous()
+        return self._derived('head', (l1.weight, l1.bias, l2.weight, l2.bias), build)
 
     def _lgcn_fused_ok(self, C, K0):
         """Does the persistent label-GCN launch take this channel?  (mgnns_label_gcn_supported: the launcher's own limits)"""
@@ -660,14 +613,11 @@ class Multi_GCN_Multihead_Att(nn.Module):
         return x
 
     def _adj_pair(self, A):
-        """(CSR of gen_adj(A), CSR of its transpose), built once per adjacency version."""
-        key = (A.data_ptr(), A._version, str(A.device))
-        hit = self._adj_cache.get(id(A))
-        if hit is None or hit[0] != key:
+        """(CSR of gen_adj(A), CSR of its transpose), built once per adjacency version (training only, never captured: no park)."""
+        def build():
             adj, csr = ops.gen_adj(A.detach().float().contiguous(), want_csr=True)
-            hit = (key, (csr, ops.dense_to_csr(ops.transpose_pad(adj, adj.shape[0]))))
-            self._adj_cache[id(A)] = hit
-        return hit[1]
+            return csr, ops.dense_to_csr(ops.transpose_pad(adj, adj.shape[0]))
+        return derived(self._adj_cache, id(A), (A,), build)
 
     def _forward_train(self, text, text_lens, text_mask, object_feature, place_feature, object_inp, place_inp):
         """The reference's training forward (MODEL:431-567) as one chain of autograd Functions over HIP kernels on the current

@@ -8,6 +8,7 @@ import os
 import torch
 
 from . import _lib
+from .derived import derived
 
 ACT_NONE, ACT_RELU, ACT_LRELU2 = 0, 1, 2
 BANK_LD = 320      # bf16 memory banks are [B, L, 320]: model dim 300 zero padded to 10 MFMA k-steps of 32
@@ -56,10 +57,8 @@ def release_scratch_epoch(epoch):
         slot.pop(key, None)
 
 
-# Derived weight packs / scratch that a captured hipGraph may hold by raw address: while any capture is alive, a superseded
-# pack is parked here instead of being freed (load_state_dict / set_precision with a live GraphedForward must not let a replay
-# read recycled memory); the park empties when the last capture goes.  model._cache_put keeps its own per-model list; the
-# layer-level caches of fusion.py (no back-pointer to the model) use this one.
+# The layer-level park ("Derived packs and launch scratch"): while any capture is alive, a superseded entry of a
+# fusion.py layer cache or an LstmCache is kept here instead of being freed; it empties when the last capture goes.
 _LIVE_CAPTURES = 0
 _RETIRED = []
 
@@ -122,6 +121,29 @@ def zeros_bytes(nbytes, device):
 
 def zeros_i32(n, device):
     return zeros_bytes(4 * n, device).view(torch.int32)[:n]
+
+
+def _scratch_slot(packed, name, fits, make):
+    """The scratch of one persistent / cluster launch: packed[name][_scratch_key()], made by make() when there is none or when
+    fits(it) -- big enough, on the launch's device -- says no.  make() takes counters from the zero pool (zeros_bytes /
+    zeros_i32; a torch.zeros would be a fill node inside a capture).  A superseded buffer goes to packed["_retired"] and
+    is never freed while the pack lives: a captured hipGraph may still hold its address.  -> (key, scratch)"""
+    slot = packed.setdefault(name, {})
+    key = _scratch_key()
+    ws = slot.get(key)
+    if ws is None or not fits(ws):
+        if ws is not None:
+            packed.setdefault("_retired", []).append(ws)
+        ws = make()
+        _scratch_slot_put(slot, key, ws)
+    return key, ws
+
+
+def _cluster_scratch(packed, name, device, tiles, floats):
+    """(tiles, exchange scratch of floats(tiles) fp32, 2 counters per tile) for a cluster launch over `tiles` 16-sample tiles."""
+    return _scratch_slot(packed, name, lambda ws: ws[0] >= tiles and ws[1].device == device,
+                         lambda: (tiles, torch.empty(floats(tiles), device=device, dtype=torch.float32),
+                                  zeros_i32(2 * tiles, device)))[1]
 
 
 class KernelTimer:
@@ -341,14 +363,8 @@ def label_gcn(A, inp, packed, want_packed_g=False, query=None, grid=0, memo=None
     need = L.mgnns_label_gcn_scratch_bytes(C, N1, N2)
     # the launch's scratch holds its intermediates and its item queue: one per (capture epoch, launch stream), so that two
     # forwards of one model in flight at once -- two streams, two captured graphs -- never share one
-    slot = packed.setdefault("_scratch", {})
-    key = _scratch_key()
-    ws = slot.get(key)
-    if ws is None or ws.numel() < need or ws.device != A.device:
-        if ws is not None:
-            packed.setdefault("_retired", []).append(ws)     # a captured hipGraph may still hold its address: never freed
-        ws = zeros_bytes(need, A.device)[:need]                           # counters (first 256 B) start at zero
-        _scratch_slot_put(slot, key, ws)
+    key, ws = _scratch_slot(packed, "_scratch", lambda ws: ws.numel() >= need and ws.device == A.device,
+                            lambda: zeros_bytes(need, A.device)[:need])               # counters (first 256 B) start at zero
     st = None
     if memo is not None and _TIMER is not None and _TIMER.wants("mgnns_label_gcn_fwd"):
         memo = None                      # a timed launch is a computing one: a roofline row of the hit path would say nothing
@@ -587,36 +603,26 @@ def embedding(idx, table):
 # ---- text memory bank: embedding + packed BiLSTM -----------------------------------------------------
 class LstmCache:
     """Derived forms of one nn.LSTM's weights (per-layer [W_ih ; W_ih_reverse], the packed bf16 layouts), owned by the
-    module that owns the weights so their lifetime is the module's (a captured hipGraph bakes these pointers in).
-    An entry keeps strong REFERENCES to the tensors it was derived from, so their storage cannot be freed and handed
-    to another model's weights while the entry lives: a (data_ptr, version) match therefore means the same weights."""
+    module that owns the weights so their lifetime is the module's (a captured hipGraph bakes these pointers in).  Each
+    field is one entry of derived.derived (value at index 2), stored in this object's __dict__."""
 
     def __init__(self):
-        self.cat = None        # (sources, versions, value)
+        self.cat = None
         self.prepack = None
         self.table = None      # the layer-0 input projection folded into the embedding table
 
-    @staticmethod
-    def _hit(entry, sources):
-        return (entry is not None and len(entry[0]) == len(sources)
-                and all(a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.device == b.device
-                        for a, b in zip(entry[0], sources))
-                and entry[1] == tuple(t._version for t in sources))
+
+def _lstm_derived(cache, slot, sources, build):
+    """cache.<slot>, rebuilt when a source changes and parked by retire(); cache None: built per call, nothing stored."""
+    return build() if cache is None else derived(vars(cache), slot, sources, build, park=retire)
 
 
 def _lstm_cat(weights, num_layers, cache):
     """Per layer [W_ih ; W_ih_reverse] and [b_ih ; b_ih_reverse], rebuilt when a weight changes (one input-projection
     GEMM per layer instead of two)."""
-    src = [t for tup in weights for t in (tup[0], tup[2])]
-    if cache is not None and LstmCache._hit(cache.cat, src):
-        return cache.cat[2]
-    val = [(torch.cat([weights[2 * l][0], weights[2 * l + 1][0]], 0).contiguous(),
-            torch.cat([weights[2 * l][2], weights[2 * l + 1][2]], 0).contiguous()) for l in range(num_layers)]
-    if cache is not None:
-        if cache.cat is not None:
-            retire(cache.cat[2])                # a live capture holds the old concatenations' addresses (projection weights / biases)
-        cache.cat = (src, tuple(t._version for t in src), val)
-    return val
+    return _lstm_derived(cache, "cat", [t for tup in weights for t in (tup[0], tup[2])], lambda: [
+        (torch.cat([weights[2 * l][0], weights[2 * l + 1][0]], 0).contiguous(),
+         torch.cat([weights[2 * l][2], weights[2 * l + 1][2]], 0).contiguous()) for l in range(num_layers)])
 
 
 # bf16 recurrence: the layer-0 input projection folded into the embedding table once per weight version (mgnns_bilstm_bf16_fold_embedding:
@@ -627,21 +633,16 @@ LSTM_FOLD_EMBEDDING = os.environ.get("MGNNS_LSTM_FOLD", "1") != "0"
 def _lstm_table(emb_table, cat0, hidden, cache):
     """table[v] = bf16(emb[v]) . bf16(W_ih0)^T + b_ih0 for every vocabulary entry; rebuilt when the embedding or layer 0's input
     weights change.  Superseded tables go to the retirement list (a captured graph may still read them)."""
-    src = [emb_table, cat0[0], cat0[1]]
-    if cache is not None and LstmCache._hit(cache.table, src):
-        return cache.table[2]
-    L = _lib.lib()
-    V, E = emb_table.shape
-    table = torch.empty(V, 8 * hidden, device=emb_table.device, dtype=torch.float32)
-    assert table.numel() * 4 == L.mgnns_bilstm_bf16_table_bytes(V, hidden)
-    ws = torch.empty(L.mgnns_bilstm_bf16_fold_workspace_bytes(V), dtype=torch.uint8, device=emb_table.device)
-    _lib.check(L.mgnns_bilstm_bf16_fold_embedding(_p(emb_table), V, E, hidden, _p(cat0[0]), _p(cat0[1]), _p(ws), ws.numel(), _p(table),
-                                                  _stream()), "mgnns_bilstm_bf16_fold_embedding")
-    if cache is not None:
-        if cache.table is not None:
-            retire(cache.table[2])
-        cache.table = (src, tuple(t._version for t in src), table)
-    return table
+    def build():
+        L = _lib.lib()
+        V, E = emb_table.shape
+        table = torch.empty(V, 8 * hidden, device=emb_table.device, dtype=torch.float32)
+        assert table.numel() * 4 == L.mgnns_bilstm_bf16_table_bytes(V, hidden)
+        ws = torch.empty(L.mgnns_bilstm_bf16_fold_workspace_bytes(V), dtype=torch.uint8, device=emb_table.device)
+        _lib.check(L.mgnns_bilstm_bf16_fold_embedding(_p(emb_table), V, E, hidden, _p(cat0[0]), _p(cat0[1]), _p(ws), ws.numel(),
+                                                      _p(table), _stream()), "mgnns_bilstm_bf16_fold_embedding")
+        return table
+    return _lstm_derived(cache, "table", [emb_table, cat0[0], cat0[1]], build)
 
 
 def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, recurrence="f32", cache=None, fold=None):
@@ -690,17 +691,12 @@ def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, r
                 _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _stream())
     else:
         # weight layouts of the bf16 kernels: packed once per weight version, off the per-forward path
-        src = [t for tup in weights for t in (tup[0], tup[1])]
-        if cache is not None and LstmCache._hit(cache.prepack, src):
-            pre = cache.prepack[2]
-        else:
+        def prepack():
             pre = torch.empty(L.mgnns_bilstm_bf16_prepack_bytes(hidden, num_layers), dtype=torch.uint8, device=tok.device)
             _lib.check(L.mgnns_bilstm_bf16_prepack(c_wih, c_whh, emb_table.shape[1], hidden, num_layers, _p(pre), _stream()),
                        "mgnns_bilstm_bf16_prepack")
-            if cache is not None:
-                if cache.prepack is not None:
-                    retire(cache.prepack[2])
-                cache.prepack = (src, tuple(t._version for t in src), pre)
+            return pre
+        pre = _lstm_derived(cache, "prepack", [t for tup in weights for t in (tup[0], tup[1])], prepack)
         if fold is None:
             fold = LSTM_FOLD_EMBEDDING and cache is not None
         if fold and B <= 1024 and T <= 1024 and emb_table.shape[1] % 4 == 0 and emb_table.shape[1] <= 320:
@@ -945,16 +941,7 @@ def label_tail_bf16(pooled, g_pair, Q, n_heads, packed, next_q=None, terms=3, cl
         cluster = LABEL_TAIL_CLUSTER
     scratch = counters = None
     if cluster and int(terms) == 3 and B > 0:
-        tiles = (B + 15) // 16
-        slot = packed.setdefault("_cluster_ws", {})
-        key = _scratch_key()                                     # per (capture epoch, launch stream), like the label GCN's
-        ws = slot.get(key)
-        if ws is None or ws[0] < tiles or ws[1].device != Q.device:
-            if ws is not None:
-                packed.setdefault("_retired", []).append(ws)     # a captured hipGraph may still hold its address: never freed
-            ws = (tiles, torch.empty(tiles * 4 * 6144, device=Q.device, dtype=torch.float32),
-                  zeros_i32(2 * tiles, Q.device))
-            _scratch_slot_put(slot, key, ws)
+        ws = _cluster_scratch(packed, "_cluster_ws", Q.device, (B + 15) // 16, lambda tiles: tiles * 4 * 6144)
         scratch, counters = ws[1], ws[2]
     L = _lib.lib()
     _launch("mgnns_label_tail_bf16_fwd", ("mgnns_label_tail_bf16_fwd", packed["C"]), L.mgnns_label_tail_bf16_fwd, _p(pooled), B,
@@ -1288,16 +1275,8 @@ def mha_tail_bf16(o, q, packed, eps, next_packed=None, terms=3, cluster=0, kspli
     L = _lib.lib()
     scratch = counters = None
     if use_ks and int(terms) in (1, 3):
-        tiles = (B + 15) // 16
-        slot = packed.setdefault("_cluster_ws_ks", {})
-        key = _scratch_key()                                     # per (capture epoch, launch stream), like the c16 tail's
-        ws = slot.get(key)
-        if ws is None or ws[0] < tiles or ws[1].device != o.device:
-            if ws is not None:
-                packed.setdefault("_retired", []).append(ws)     # a captured hipGraph may still hold its address: never freed
-            ws = (tiles, torch.empty(L.mgnns_mha_tail_c16_scratch_floats(16 * tiles, 8), device=o.device, dtype=torch.float32),
-                  zeros_i32(2 * tiles, o.device))
-            _scratch_slot_put(slot, key, ws)
+        ws = _cluster_scratch(packed, "_cluster_ws_ks", o.device, (B + 15) // 16,
+                              lambda tiles: L.mgnns_mha_tail_c16_scratch_floats(16 * tiles, 8))
         scratch, counters = ws[1], ws[2]
     _launch("mgnns_mha_tail_bf16_fwd", ("mgnns_mha_tail_bf16_fwd",), L.mgnns_mha_tail_bf16_fwd, _p(o), HK, _p(q), B, 300,
             int(terms), arr, _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]), _p(packed["b1"]), _p(packed["b2"]),
@@ -1331,16 +1310,8 @@ def mha_tail_c16(c, q, packed, eps, next_packed=None, cluster=0, ksplit=True):
     L = _lib.lib()
     scratch = counters = None
     if ksplit and B > 0 and cluster != 1:
-        tiles = (B + 15) // 16
-        slot = packed.setdefault("_cluster_ws", {})
-        key = _scratch_key()                                     # per (capture epoch, launch stream), like the channel tail's
-        ws = slot.get(key)
-        if ws is None or ws[0] < tiles or ws[1].device != c.device:
-            if ws is not None:
-                packed.setdefault("_retired", []).append(ws)     # a captured hipGraph may still hold its address: never freed
-            ws = (tiles, torch.empty(L.mgnns_mha_tail_c16_scratch_floats(16 * tiles, 8), device=c.device, dtype=torch.float32),
-                  zeros_i32(2 * tiles, c.device))
-            _scratch_slot_put(slot, key, ws)
+        ws = _cluster_scratch(packed, "_cluster_ws", c.device, (B + 15) // 16,
+                              lambda tiles: L.mgnns_mha_tail_c16_scratch_floats(16 * tiles, 8))
         scratch, counters = ws[1], ws[2]
     _launch("mgnns_mha_tail_c16_fwd", ("mgnns_mha_tail_c16_fwd",), L.mgnns_mha_tail_c16_fwd, _p(c), HC, _p(q), B, 300,
             arr, _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]), _p(packed["b1"]), _p(packed["b2"]),
