@@ -80,7 +80,7 @@ class GraphedForward:
             self.mode = "single"                    # one stream: the forward is one linear chain anyway
         elif self.mode in ("single", "auto") and hasattr(model, "resolve_schedule") and not _probe_child:
             # hipStreamEndCapture SEGFAULTS inside the runtime (ROCm 7.0 / 7.2) on the single-graph form of every schedule
-            # tried but 'channels' (lgcn_side, banks_first, channels2: python -X faulthandler points at capture_end) -- not
+            # tried but 'channels' (channels2 and other topologies, NOTES_r03: python -X faulthandler points at capture_end) -- not
             # an exception this process could survive: the one-graph form of a topology is first captured in a child process
             sched = model.resolve_schedule(example_args[0].shape[0])
             prec, att = getattr(model, "precision", "fp32"), getattr(model, "attention", "faithful")

@@ -229,20 +229,20 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self._lstm_cache = ops.LstmCache()     # derived LSTM weight forms live and die with this module
         self._streams = None
         self.use_streams = bool(opt.get('use_streams', True))
-        # 'auto': 'place_bank_first' for batches of at least 128 samples, 'channels2' below (resolve_schedule)
+        # 'auto': default_schedule() by batch size and precision (resolve_schedule)
         self.schedule = opt.get('schedule', os.environ.get('MGNNS_SCHEDULE', 'auto'))
         # the classifier as four shares behind the four stacks instead of a segment of its own (forward_plan)
-        self.split_head = os.environ.get('MGNNS_SPLIT_HEAD', '1') == '1'
+        self.split_head = True
+        # the channel tails and the label GCN as fused / persistent launches.  Their workgroups wait on each other, so two
+        # processes on ONE GPU switch them off (tools/dev/two_proc_model.py): the only two with an env read
         self.fused_label_tail = os.environ.get('MGNNS_FUSED_LABEL_TAIL', '1') == '1'
-        self.fused_label_tail_min_batch = int(os.environ.get('MGNNS_FUSED_TAIL_MIN_BATCH', '96'))      # fp32 fused tail (16 CUs per 256 samples)
-        # the bf16 fused tail runs as 4-workgroup clusters: it wins at every batch size (B=32: 0.471 -> 0.431 ms, B=16: 0.438 -> 0.419)
-        self.fused_label_tail_bf16_min_batch = int(os.environ.get('MGNNS_FUSED_TAIL_BF16_MIN_BATCH', '1'))
-        self.fused_label_tail_bf16 = os.environ.get('MGNNS_FUSED_LABEL_TAIL_BF16', '1') == '1'
-        self.fused_head = os.environ.get('MGNNS_FUSED_HEAD', '1') == '1'      # classifier as one launch (composed maps)
-        self.fused_label_gcn = os.environ.get('MGNNS_FUSED_LABEL_GCN', '1') == '1'      # label GCN as one persistent launch
+        self.fused_label_gcn = os.environ.get('MGNNS_FUSED_LABEL_GCN', '1') == '1'
+        # fp32 fused tail (16 CUs per 256 samples): from this batch on (_channel_tail).  The bf16 fused tail runs as 4-workgroup
+        # clusters and wins at every batch size (B=32: 0.471 -> 0.431 ms, B=16: 0.438 -> 0.419)
+        self.fused_label_tail_min_batch = 96
         # the persistent label-GCN launch keeps its outputs and computes only when inp[0] or a weight changed (_lgcn_memo)
         self.label_gcn_memo = True
-        self.label_tail_terms = int(os.environ.get('MGNNS_LABEL_TAIL_TERMS', '3'))
+        self.label_tail_terms = 3              # split-bf16 products of the bf16 tail (1: plain bf16)
         self.precision = 'fp32'
         self.attention_choice = 'faithful'
         self.attention = 'faithful'
@@ -401,7 +401,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         f3 = feats.float().contiguous().view(B, feats.shape[1], -1)
         if self.precision == 'bf16' and 16 <= f3.shape[2] <= 208 and f3.shape[2] % 4 == 0 and f3.shape[1] % 64 == 0 \
                 and lin.out_features <= 304:        # (the bf16 bank kernels' limits; other shapes take the fp32 kernel)
-            keep_halves = (self.fused_label_tail and self.fused_label_tail_bf16 and B >= self.fused_label_tail_bf16_min_batch)
+            keep_halves = self.fused_label_tail and B >= 1
             bank, pooled = ops.imgbank_pool_bf16(f3, self._wp(lin), lin.bias.detach(), lin.out_features, combine=not keep_halves)
             return MemoryBank(bf16=bank), pooled
         if self.precision == 'bf16x3' and f3.shape[2] % 4 == 0 and f3.shape[2] <= 224 and f3.shape[1] % 64 == 0 \
@@ -515,7 +515,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         bf16_ok = (Gp is not None and flat_ok and pooled.dim() == 3 and
                    L.mgnns_label_tail_bf16_supported(C, NLQ, nh, dh, N5, n_out, pooled.shape[-1], int(self.label_tail_terms), n_next))
         f32_ok = flat_ok and L.mgnns_label_tail_supported(C, NLQ, nh, dh, N5, n_out, 0, n_next)
-        if bf16_ok and self.fused_label_tail and B >= self.fused_label_tail_bf16_min_batch:
+        if bf16_ok and self.fused_label_tail and B >= 1:
             # bf16 precision mode: the whole chain, read-out included, as ONE launch on the bf16 MFMA
             pk = self._tail_pack_bf16(attention, linear_5, x_linear)
             nq = first_query_pack_bf16(next_stack) if next_stack is not None and len(next_stack) else None
@@ -685,8 +685,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
         "head": ("tio", "tip", "iot", "ipt"),
     }
     # schedules: enqueue order and stream of every segment ('main' = the caller's stream, 's1'..'s3' side streams, all of
-    # default priority on hardware queues of their own, mgnns_amd/streams.py).  Decided by bench.py measurements
-    # (DESIGN.md section 6).
+    # default priority on hardware queues of their own, mgnns_amd/streams.py).  Decided by bench.py measurements; the schedules
+    # that lost their A/Bs are retired, their numbers are in DESIGN.md section 6 and profiles/NOTES_r03 / r04 / r05.
     SCHEDULES = {
         # one stream per channel, stacks where their producer ran (the round-1 schedule)
         # (the BiLSTM chain is the longest of the forward: it is enqueued FIRST -- at B=32 the single-graph runtime started
@@ -694,70 +694,23 @@ class Multi_GCN_Multihead_Att(nn.Module):
         "channels": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"),
                      ("bank_place", "s2"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio", "main"), ("tip", "s3"),
                      ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
-        # the same, but a text->image stack also waits for its channel's label-attention tail: the tail's two small
-        # launches then run BEFORE the chip-filling attention cores start instead of queueing for CUs behind them
-        "tails_first": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"), ("bank_place", "s2"),
-                        ("tail_obj", "s1"), ("tail_place", "s2"), ("tio+tail_obj", "main"),
-                        ("tip+tail_place", "s3"), ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
-        # memory banks first on their streams (they start at ~20 us instead of behind their label GCN); both label GCNs on
-        # the text-GCN stream, which is otherwise idle until the place bank is done
-        "banks_first": [("text_bank", "main"), ("bank_obj", "s1"), ("bank_place", "s2"), ("text_gcn", "s3"), ("lgcn_obj", "s3"),
-                        ("lgcn_place", "s3"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio", "main"), ("tip", "s3"),
-                        ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
         # 'channels' with the object-side stacks re-homed: the text->object stack right behind the object bank (not behind the
         # BiLSTM chain on the caller's stream, which ends later than the bank at small batches), the image->text stack behind the
         # BiLSTM it needs, the object tail on the text-GCN stream
         "channels2": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"),
                       ("bank_place", "s2"), ("tio", "s1"), ("tail_obj", "s3"), ("tail_place", "s2"), ("tip", "s3"),
                       ("iot", "main"), ("ipt", "s2"), ("head", "main")],
-        # 'channels' with the two HBM-bound memory-bank kernels one after the other instead of side by side: together they
-        # take as long either way, but the first one -- and the stack and the label tail behind it -- is done in half the time
-        "banks_serial": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"),
-                         ("bank_place+bank_obj", "s2"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio", "main"), ("tip", "s3"),
-                         ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
         # 'channels' with the place channel's memory bank in FRONT of its label GCN (the longer one, C = 365: 105-123 us): the bank
         # starts at t = 0 instead of behind it
         "place_bank_first": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("bank_place", "s2"),
                              ("lgcn_place", "s2"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio", "main"), ("tip", "s3"),
                              ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
-        # ('place_bank_first' with the object bank WAITING for the place bank -- the two HBM-bound kernels one after the other,
-        #  place first -- loses: 0.644-0.647 / 0.715-0.721 ms against 0.613-0.621 / 0.678-0.682, three alternating runs, round 5)
-        # the same with the place label GCN on the text-GCN stream (idle until the place bank is done)
-        "place_bank_first_lgcn_s3": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("bank_place", "s2"),
-                                     ("lgcn_place", "s3"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio", "main"), ("tip", "s3"),
-                                     ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
-        "tails_first_obj": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"),
-                            ("bank_place", "s2"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio+tail_obj", "main"), ("tip", "s3"),
-                            ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
-        "tails_first_place": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"),
-                              ("bank_place", "s2"), ("tail_obj", "s1"), ("tail_place", "s2"), ("tio", "main"), ("tip+tail_place", "s3"),
-                              ("iot", "s1"), ("ipt", "s2"), ("head", "main")],
-        # chip-filling kernels in two chains, every small launch on a stream of its own:
-        #   main: BiLSTM -> head;  s1: both image banks, then the two masked stacks;  s2: the two text->image stacks;
-        #   s3: text GCN, label GCNs, label-attention tails
-        # (round 5: a six-stream schedule -- BiLSTM, text GCN, two label GCNs and two memory banks each at the head of a stream of
-        #  its own -- lost at every batch: 0.536 against 0.388 ms at B = 32 on the runtime's four hardware queues, where the extra
-        #  streams share a queue, and GPU_MAX_HW_QUEUES=8 slows EVERY schedule down, 0.54-0.72 ms at B = 32 and 0.93 at B = 256:
-        #  NOTES_r05 section 5)
-        # small batches (round 5; default below 64 samples): the memory banks in FRONT of the two shorter heads -- object label
-        # GCN, text GCN -- instead of behind the label GCNs ('channels2': label GCN 75 / 105 us, THEN the bank 59 / 54 us, then the
-        # tail); the place label GCN (the longest head, C = 365) and the BiLSTM start at t = 0 on streams of their own; the
-        # text->object stack behind the BiLSTM, the object->text stack behind the object tail.  B = 32: 0.305-0.325 ms two in
-        # flight / 0.369-0.370 one at a time against 0.348-0.352 / 0.387-0.390 ('channels2', same box); B = 16: 0.310 / 0.361
-        # against 0.340 / 0.378; B = 48: 0.330 / 0.396 against 0.357 / 0.396; at B = 64 it loses (0.42 against 0.37)
+        # small batches: the memory banks in FRONT of the two shorter heads -- object label GCN, text GCN -- instead of behind the
+        # label GCNs; the place label GCN (the longest head, C = 365) and the BiLSTM start at t = 0 on streams of their own; the
+        # text->object stack behind the BiLSTM, the object->text stack behind the object tail
         "small": [("text_bank", "main"), ("lgcn_place", "s2"), ("bank_obj", "s1"), ("bank_place", "s3"), ("lgcn_obj", "s1"),
                   ("text_gcn", "s3"), ("tail_place", "s2"), ("tail_obj", "s1"), ("tip", "s3"), ("tio", "main"), ("ipt", "s2"),
                   ("iot", "s1"), ("head", "main")],
-        # mid-size batches (found by tools/dev/sched_search.py from 'channels2' at B = 64; NOT the default): both memory banks behind
-        # the object label GCN on ONE stream, the place label GCN (the longest head) alone on its own.  Throughput for latency: B = 64:
-        # 0.348-0.352 ms two in flight / 0.456-0.457 one at a time against 0.369-0.370 / 0.418-0.419 ('channels2'); B = 96: 0.402-0.404 /
-        # 0.486-0.492 against 0.425-0.439 / 0.470; B = 48: 0.310-0.317 / 0.453-0.455 against 0.326 / 0.397-0.405 ('small'); B = 128: loses
-        "mid": [("text_bank", "main"), ("text_gcn", "s3"), ("lgcn_obj", "s1"), ("bank_obj", "s1"), ("lgcn_place", "s2"),
-                ("bank_place", "s1"), ("tio", "s1"), ("tail_place", "s2"), ("tail_obj", "s3"), ("iot", "main"), ("tip", "s3"),
-                ("ipt", "s2"), ("head", "main")],
-        "bigsmall": [("text_gcn", "s3"), ("bank_obj", "s1"), ("text_bank", "main"), ("lgcn_obj", "s3"), ("bank_place", "s1"),
-                     ("lgcn_place", "s3"), ("tio", "s2"), ("tail_obj", "s3"), ("tail_place", "s3"), ("tip", "s2"),
-                     ("iot", "s1"), ("ipt", "s1"), ("head", "main")],
     }
 
     def resolve_schedule(self, batch, schedule=None):
@@ -767,7 +720,9 @@ class Multi_GCN_Multihead_Att(nn.Module):
         one box, B = 256): 0.647-0.654 against 0.665-0.673 ms with two forwards in flight, 0.690-0.703 against 0.717-0.721 one at a
         time; equal at B = 128 (0.502 / 0.503).  Below 128 the BiLSTM chain on the caller's stream is the longest segment and
         'channels2' (no text->image stack queued behind it) wins: 0.381 vs 0.390 / 0.394 ms at B = 32, 0.412 vs 0.413 / 0.424 at
-        B = 64 ('channels' / 'place_bank_first').  Below 64 (round 5): 'small' -- the memory banks in front of the shorter heads."""
+        B = 64 ('channels' / 'place_bank_first').  Below 64 (round 5): 'small' -- the memory banks in front of the shorter heads:
+        B = 32: 0.305-0.325 ms two in flight / 0.369-0.370 one at a time against 0.348-0.352 / 0.387-0.390 ('channels2', same box);
+        at B = 64 it loses (0.42 against 0.37).  All of it, B = 16 / 48 included: NOTES_r04 section 11, NOTES_r05 sections 4 and 5."""
         name = schedule or self.schedule
         if name == 'auto':
             # 'bf16x3' (three times the matrix work in the chip-filling kernels, the fp32 recurrence): 'channels2' at every batch --
@@ -790,8 +745,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         if not self.bidirectional:
             raise NotImplementedError("the HIP text bank implements the bidirectional LSTM the reference configures")
         ctx = _PlanCtx()
-        fused_bf16 = (self.precision in ('bf16', 'bf16x3') and self.fused_label_tail and self.fused_label_tail_bf16
-                      and text.shape[0] >= self.fused_label_tail_bf16_min_batch)
+        fused_bf16 = self.precision in ('bf16', 'bf16x3') and self.fused_label_tail and text.shape[0] >= 1
         plan_kind = mask_plan_applies(text_mask, self.precision, self.attention)        # False | 'packed' | 'grouped'
 
         def text_gcn():
@@ -874,7 +828,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         # captured behind the head (the sharded forward's all-gather): that needs the head as a segment.
         if split_head is None:
             split_head = self.split_head
-        split_head = bool(split_head and self.fused_head)
+        split_head = bool(split_head)
         if split_head:
             # building the plan launches nothing: the executor calls ctx.prepare() on the caller's stream before it forks
             def prepare():
@@ -896,15 +850,9 @@ class Multi_GCN_Multihead_Att(nn.Module):
             return run
 
         def head():
-            if self.fused_head:      # one launch: multi_linear_2 . multi_linear_1 composed (eval: nothing between them)
-                wc, bc = self._head_pack()
-                ctx['logits'] = ops.classifier_head([ctx['tio'], ctx['tip'], ctx['iot'], ctx['ipt']], wc, bc)
-                ops.stamp("logits")
-                return
-            multi_feature = torch.cat([ctx['tio'], ctx['tip'], ctx['iot'], ctx['ipt']], dim=1)
-            multi_feature = ops.linear(multi_feature, self.multi_linear_1.weight.detach(),
-                                       self.multi_linear_1.bias.detach())
-            ctx['logits'] = ops.linear(multi_feature, self.multi_linear_2.weight.detach(), self.multi_linear_2.bias.detach())
+            # one launch: multi_linear_2 . multi_linear_1 composed (eval: nothing between them)
+            wc, bc = self._head_pack()
+            ctx['logits'] = ops.classifier_head([ctx['tio'], ctx['tip'], ctx['iot'], ctx['ipt']], wc, bc)
             ops.stamp("logits")
 
         fns = {
@@ -927,9 +875,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
         }
         sched = self.SCHEDULES[self.resolve_schedule(text.shape[0], schedule)]
         where, plan = {}, []
-        for entry, skey in sched:
-            name, *extra = entry.split("+")          # "seg+other": also wait for `other` (ordering only, no data)
-            deps = tuple(self.SEGMENT_DEPS[name]) + tuple(extra)
+        for name, skey in sched:
+            deps = tuple(self.SEGMENT_DEPS[name])
             if name in ("iot", "ipt") and plan_kind and "text_gcn" not in deps:
                 deps += ("text_gcn",)                # the mask's packing plan is built at the end of that segment
             for d in deps:

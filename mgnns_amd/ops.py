@@ -334,7 +334,7 @@ def label_gcn_pack(w1, w2, split):
     return d
 
 
-LABEL_GCN_GRID = int(os.environ.get("MGNNS_LGCN_GRID", "0"))
+LABEL_GCN_GRID = 0            # workgroups of the persistent label-GCN launch; 0: by batch size (model.forward_plan)
 
 
 def label_gcn_memo_flag(memo, want_packed_g=False):
@@ -904,14 +904,14 @@ def label_tail(x, Q, n_heads, packed, pooled=None, g_wp=None, next_q=None):
     return out if next_q is None else (out, qh)
 
 
-LABEL_TAIL_CLUSTER = os.environ.get("MGNNS_LABEL_TAIL_CLUSTER", "1") != "0"
+LABEL_TAIL_CLUSTER = True
 
 
 def label_tail_bf16(pooled, g_pair, Q, n_heads, packed, next_q=None, terms=3, cluster=None):
     """bf16-mode fused channel tail (mgnns_label_tail_bf16_fwd): pooled [B,parts,K] fp32, g_pair = pack_weight_bf16_split(G
     [C,K]); packed = dict(wk, wv, wc, xl = (hi, lo) pairs of pack_weight_bf16_split, bk, bv, bc, bxl, n5, n_out, C);
     next_q = ((hi, lo), bq, HK).  terms = 1 plain bf16 | 3 split-bf16.  cluster: four workgroups per 16-sample tile
-    (terms = 3; default on, MGNNS_LABEL_TAIL_CLUSTER=0 turns it off); the exchange scratch lives in `packed`, one per
+    (terms = 3; default on, ops.LABEL_TAIL_CLUSTER = False turns it off); the exchange scratch lives in `packed`, one per
     channel, so the two channels' launches never share one.  -> out [B,n_out] (or (out, qh))."""
     import ctypes
     _chk(pooled, "pooled", ndim=3)
@@ -1346,7 +1346,7 @@ def transpose_cast_bf16(x):
     return y
 
 
-GEMM_BF16_KSPLIT = os.environ.get("MGNNS_GEMM_BF16_KSPLIT", "1") == "1"
+GEMM_BF16_KSPLIT = True       # K splits with partial sums in a workspace
 _gemm_bf16_ws = {}
 
 

@@ -7,7 +7,7 @@ kernel and this emulation is fp32 summation order (~1e-6 relative) and the occas
 of a bf16 rounding boundary, so the kernels can be held far tighter than against the fp32 answer.
 
 Stages that stay fp32-class in bf16 mode come from restatement.py unchanged (model.set_precision docstring): the text GCN, the
-label GCN (split-bf16 in the persistent launch), the label attention + its tail at MGNNS_LABEL_TAIL_TERMS=3 (split-bf16,
+label GCN (split-bf16 in the persistent launch), the label attention + its tail at model.label_tail_terms = 3 (split-bf16,
 csrc/label_tail.hip), softmax, LayerNorms, residuals; the classifier head (fp32).
 
 Rounding points (names = the keys of POINTS; `rounding` selects which are on, default all):
@@ -41,7 +41,7 @@ Rounding points (names = the keys of POINTS; `rounding` selects which are on, de
     tail_h       relu(w_1 y + b_1) as w_2's A operand              mha_tail_body.hpp:306
     tail_q       the layer output as the next projection's A operand  mha_tail_body.hpp:92 via :350; mha_tail.hip:352
                  (mha_proj_c16_kernel, the K-split forms' projection)
-  label tail at terms=1 (MGNNS_LABEL_TAIL_TERMS=1, csrc/label_tail.hip label_tail_bf16_kernel<1, 1>), label_tail() below:
+  label tail at terms=1 (model.label_tail_terms = 1, csrc/label_tail.hip label_tail_bf16_kernel<1, 1>), label_tail() below:
     weights (G, w_k, w_v, the composed linear_5 . fc, x_linear, w_q) and every product's A operand: pooled
     (label_tail.hip:425), x (:440-498), o (:558), the flatten buffer (:580), out (:605).
 
@@ -294,7 +294,7 @@ def label_tail(p, chan, pooled, G, Q, n_heads=5, next_w=None, next_b=None, terms
 # ---------------------------------------------------------------------------------------------------------------------------
 def forward(p, inputs, pmi, n_head, d_kv, stack_num, ngram, label_query=None, attention="faithful", rounding=None,
             hidden=150, num_layers=2, return_parts=False):
-    """Multi_GCN_Multihead_Att.forward in bf16 mode (identity trunks, MGNNS_LABEL_TAIL_TERMS=3, the bf16 LSTM recurrence).
+    """Multi_GCN_Multihead_Att.forward in bf16 mode (identity trunks, model.label_tail_terms = 3, the bf16 LSTM recurrence).
     Arguments as restatement.forward; attention 'faithful' | 'folded'; rounding: the POINTS switched on (None: all; () gives
     the fp32 network in fp64 arithmetic).  -> logits [B, NL] fp64 (, parts)."""
     if attention not in ("faithful", "folded"):

@@ -182,7 +182,7 @@ def test_mha_tail_c16_matches_emulation(Hn, B):
 
 
 def test_label_tail_bf16_terms1_matches_emulation():
-    """ops.label_tail_bf16(terms=1) (MGNNS_LABEL_TAIL_TERMS=1) on the cases of test_fused_label_tail_bf16_vs_oracle, against
+    """ops.label_tail_bf16(terms=1) (model.label_tail_terms = 1) on the cases of test_fused_label_tail_bf16_vs_oracle, against
     oracle/bf16_path.label_tail (every product's operands rounded)."""
     g = H.load_golden("label_attention.npz")
     lq = dev(g["label_query"])

@@ -146,6 +146,70 @@ def test_every_schedule_is_a_valid_plan_without_a_gpu():
         m.forward_plan(*args, schedule="no-such-schedule")
 
 
+def test_kept_schedules_plan_exactly_as_before():
+    """[(segment, stream key, cross-stream waits)] of forward_plan for the four schedules the model keeps, in fp32 mode (no mask plan)
+    and in bf16 mode with the faithful attention (the masked stacks also wait for text_gcn, where the mask's plan is built).  The table
+    was dumped from the commit BEFORE the retired schedules and the "seg+other" ordering syntax were removed, on this model and these
+    B = 2 inputs -- not from the code under test: a plan of a kept schedule that changes is a behaviour change."""
+    cfg = synth.CONFIGS["mvsa_single_b8"]
+    pmi, count = synth.synth_pmi(cfg.V, seed=3)
+    adj = H.load_golden("adjacency.npz")
+    m = build_model(cfg, pmi, count, adj["object_t04_A"], adj["place_t03_A"], np.zeros((7, 300), np.float32))
+    inp = synth.make_inputs(cfg, B=2, pmi=pmi)
+    t = {k: torch.from_numpy(v) for k, v in inp.items()}
+    args = (t["text"], t["text_lens"], t["text_mask"], t["object_feature"], t["place_feature"], t["object_inp"], t["place_inp"])
+    table = {
+        ("fp32", "channels"): [
+            ("text_bank", "main", ()), ("text_gcn", "s3", ()), ("lgcn_obj", "s1", ()), ("bank_obj", "s1", ()), ("lgcn_place", "s2", ()),
+            ("bank_place", "s2", ()), ("tail_obj", "s1", ()), ("tail_place", "s2", ()), ("tio", "main", ("bank_obj", "text_gcn")),
+            ("tip", "s3", ("bank_place",)), ("iot", "s1", ("text_bank",)), ("ipt", "s2", ("text_bank",)), ("head", "main", ("tip", "iot", "ipt"))],
+        ("fp32", "channels2"): [
+            ("text_bank", "main", ()), ("text_gcn", "s3", ()), ("lgcn_obj", "s1", ()), ("bank_obj", "s1", ()), ("lgcn_place", "s2", ()),
+            ("bank_place", "s2", ()), ("tio", "s1", ("text_gcn",)), ("tail_obj", "s3", ("lgcn_obj", "bank_obj")), ("tail_place", "s2", ()),
+            ("tip", "s3", ("bank_place",)), ("iot", "main", ("tail_obj",)), ("ipt", "s2", ("text_bank",)), ("head", "main", ("tio", "tip", "ipt"))],
+        ("fp32", "place_bank_first"): [
+            ("text_bank", "main", ()), ("text_gcn", "s3", ()), ("lgcn_obj", "s1", ()), ("bank_obj", "s1", ()), ("bank_place", "s2", ()),
+            ("lgcn_place", "s2", ()), ("tail_obj", "s1", ()), ("tail_place", "s2", ()), ("tio", "main", ("bank_obj", "text_gcn")),
+            ("tip", "s3", ("bank_place",)), ("iot", "s1", ("text_bank",)), ("ipt", "s2", ("text_bank",)), ("head", "main", ("tip", "iot", "ipt"))],
+        ("fp32", "small"): [
+            ("text_bank", "main", ()), ("lgcn_place", "s2", ()), ("bank_obj", "s1", ()), ("bank_place", "s3", ()), ("lgcn_obj", "s1", ()),
+            ("text_gcn", "s3", ()), ("tail_place", "s2", ("bank_place",)), ("tail_obj", "s1", ()), ("tip", "s3", ()),
+            ("tio", "main", ("bank_obj", "text_gcn")), ("ipt", "s2", ("text_bank",)), ("iot", "s1", ("text_bank",)),
+            ("head", "main", ("tip", "iot", "ipt"))],
+        ("bf16", "channels"): [
+            ("text_bank", "main", ()), ("text_gcn", "s3", ()), ("lgcn_obj", "s1", ()), ("bank_obj", "s1", ()), ("lgcn_place", "s2", ()),
+            ("bank_place", "s2", ()), ("tail_obj", "s1", ()), ("tail_place", "s2", ()), ("tio", "main", ("bank_obj", "text_gcn")),
+            ("tip", "s3", ("bank_place",)), ("iot", "s1", ("text_bank", "text_gcn")), ("ipt", "s2", ("text_bank", "text_gcn")),
+            ("head", "main", ("tip", "iot", "ipt"))],
+        ("bf16", "channels2"): [
+            ("text_bank", "main", ()), ("text_gcn", "s3", ()), ("lgcn_obj", "s1", ()), ("bank_obj", "s1", ()), ("lgcn_place", "s2", ()),
+            ("bank_place", "s2", ()), ("tio", "s1", ("text_gcn",)), ("tail_obj", "s3", ("lgcn_obj", "bank_obj")), ("tail_place", "s2", ()),
+            ("tip", "s3", ("bank_place",)), ("iot", "main", ("tail_obj", "text_gcn")), ("ipt", "s2", ("text_bank", "text_gcn")),
+            ("head", "main", ("tio", "tip", "ipt"))],
+        ("bf16", "place_bank_first"): [
+            ("text_bank", "main", ()), ("text_gcn", "s3", ()), ("lgcn_obj", "s1", ()), ("bank_obj", "s1", ()), ("bank_place", "s2", ()),
+            ("lgcn_place", "s2", ()), ("tail_obj", "s1", ()), ("tail_place", "s2", ()), ("tio", "main", ("bank_obj", "text_gcn")),
+            ("tip", "s3", ("bank_place",)), ("iot", "s1", ("text_bank", "text_gcn")), ("ipt", "s2", ("text_bank", "text_gcn")),
+            ("head", "main", ("tip", "iot", "ipt"))],
+        ("bf16", "small"): [
+            ("text_bank", "main", ()), ("lgcn_place", "s2", ()), ("bank_obj", "s1", ()), ("bank_place", "s3", ()), ("lgcn_obj", "s1", ()),
+            ("text_gcn", "s3", ()), ("tail_place", "s2", ("bank_place",)), ("tail_obj", "s1", ()), ("tip", "s3", ()),
+            ("tio", "main", ("bank_obj", "text_gcn")), ("ipt", "s2", ("text_bank", "text_gcn")), ("iot", "s1", ("text_bank", "text_gcn")),
+            ("head", "main", ("tip", "iot", "ipt"))],
+    }
+    assert set(m.SCHEDULES) == {"channels", "channels2", "place_bank_first", "small"}
+    for prec in ("fp32", "bf16"):
+        m.set_precision(prec)
+        assert m.attention == "faithful"
+        for name in m.SCHEDULES:
+            plan, _ = m.forward_plan(*args, schedule=name)
+            assert [(seg, skey, cross) for seg, skey, cross, _ in plan] == table[(prec, name)], (prec, name)
+            assert plan[-1][0] == "head" and plan[-1][3] is None                       # the default: the four stacks carry the head
+            plan, _ = m.forward_plan(*args, schedule=name, split_head=False)
+            assert [(seg, skey, cross) for seg, skey, cross, _ in plan] == table[(prec, name)], (prec, name)
+            assert plan[-1][0] == "head" and callable(plan[-1][3])                     # (what graph.py asks for with a `post` step)
+
+
 def test_default_schedules_are_pinned():
     """resolve_schedule('auto') for B in {16, 32, 64, 128, 256} x the precision modes: the defaults were chosen from alternating-run
     A/Bs on one box (NOTES_r04 / r05, +-1.5 % noise) -- changing one is a measured decision that edits this table, not a side effect."""

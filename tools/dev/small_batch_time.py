@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """ms per forward (one hipGraph replay at a time) of small shards of the bench workload under different schedules:
-    python tools/dev/small_batch_time.py [schedule ...]      (default: auto small small2)"""
+    python tools/dev/small_batch_time.py [schedule ...]      (default: auto small)"""
 import os
 import statistics
 import sys
@@ -19,7 +19,7 @@ A_obj, A_place = harness.synthetic_adjacencies(cfg)
 inp = synth.make_inputs(cfg, B=256, seed=cfg.seed, pmi=pmi)
 model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], dev)
 model.set_precision("bf16").set_attention("faithful")
-scheds = sys.argv[1:] or ["auto", "small", "small2"]
+scheds = sys.argv[1:] or ["auto", "small"]
 ref = {}
 with torch.no_grad():
     for bs in (32, 64, 128):
