@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 24
+#define MGNNS_ABI_VERSION 25
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -609,6 +609,13 @@ int mgnns_train_eltwise(int op, const float* a, const float* b, int64_t n, float
  * [0, P) add nothing).  dpooled and arg are both NULL (no pooled term) or both given; dbank may be NULL (the pooled term alone; W
  * is then not read), but not dbank and dpooled both.  N <= 320.  Exact-f32 MFMA; the o reduction runs inside one workgroup in a
  * fixed order, no workspace.  B = 0: nothing is launched, the tensors may be NULL.
+ * mgnns_imgbank_wgrad_split / mgnns_imgbank_dgrad_split: the same two gradients on the bf16 matrix pipe at fp32-class accuracy
+ * (split-bf16: every fp32 operand as hi = bf16(x), lo = bf16(x - hi), a product as hi*lo + lo*hi + hi*hi with fp32 accumulation,
+ * ~2^-16 relative per product; db is summed from the unrounded dbank).  Same operands (plain fp32, same layouts), shapes, NULL
+ * rules and determinism as the two entries above.  The wgrad's workspace: mgnns_imgbank_wgrad_split_workspace_bytes(B, K, P, N)
+ * bytes (slab partials).  The dgrad's workspace, mgnns_imgbank_dgrad_split_workspace_bytes(B, K, P, N) bytes and 16-byte aligned,
+ * receives the split, transposed image of W, written by a small launch of the same call (no state is kept between calls); with
+ * dbank NULL (the pooled term alone) the call is mgnns_imgbank_dgrad's and the workspace is not touched.
  * mgnns_label_attn_train_fwd: the label attention between its projections with dropout: Q [NLQ, H*dh], K = w_k(x), V = w_v(x)
  * [B, H*dh] -> x [B, NLQ, H*dh] = dropout(softmax_dh(Q K / sqrt(dh))) V, and for the backward P (softmax before dropout) and
  * keep (bytes), both [B, NLQ, H*dh].  dh <= 64.
@@ -626,6 +633,12 @@ int mgnns_imgbank_wgrad(const float* X, const float* dbank, int B, int K, int P,
 int mgnns_map_argmax(const float* X, int B, int K, int P, int32_t* arg, mgnns_stream_t stream);
 int mgnns_imgbank_dgrad(const float* dbank, const float* W, const float* dpooled, const int32_t* arg, int B, int K, int P, int N,
                         float* dX, mgnns_stream_t stream);
+size_t mgnns_imgbank_wgrad_split_workspace_bytes(int B, int K, int P, int N);
+int mgnns_imgbank_wgrad_split(const float* X, const float* dbank, int B, int K, int P, int N, float* dW, float* db,
+                              void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
+size_t mgnns_imgbank_dgrad_split_workspace_bytes(int B, int K, int P, int N);
+int mgnns_imgbank_dgrad_split(const float* dbank, const float* W, const float* dpooled, const int32_t* arg, int B, int K, int P,
+                              int N, float* dX, void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
 int mgnns_label_attn_train_fwd(const float* Q, const float* K, const float* V, int B, int NLQ, int H, int dh, uint64_t seed,
                                float rate, float* x, float* P, uint8_t* keep, mgnns_stream_t stream);
 size_t mgnns_label_attn_train_bwd_workspace_bytes(int B, int NLQ, int H, int dh);

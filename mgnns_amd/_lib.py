@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _c = ctypes
 _P = _c.c_void_p
@@ -101,6 +101,8 @@ SIGNATURES = {
     "mgnns_imgbank_wgrad": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
     "mgnns_map_argmax": [_P, _I, _I, _I, _P, _P],
     "mgnns_imgbank_dgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "mgnns_imgbank_wgrad_split": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_imgbank_dgrad_split": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P],
     "mgnns_label_attn_train_fwd": [_P, _P, _P, _I, _I, _I, _I, _U64, _F, _P, _P, _P, _P],
     "mgnns_label_attn_train_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _SZ, _P],
     "mgnns_dropout_fwd": [_P, _L, _U64, _I, _F, _P, _P, _P],
@@ -147,6 +149,8 @@ SIZE_GETTERS = {
     "mgnns_mha_train_bwd_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_wgrad_workspace_bytes": [_I, _I, _I],
     "mgnns_imgbank_wgrad_workspace_bytes": [_I, _I, _I, _I],
+    "mgnns_imgbank_wgrad_split_workspace_bytes": [_I, _I, _I, _I],
+    "mgnns_imgbank_dgrad_split_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_label_attn_train_bwd_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_bilstm_train_workspace_bytes": [_I, _I, _I],
 }

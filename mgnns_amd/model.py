@@ -244,6 +244,9 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self.label_gcn_memo = True
         self.label_tail_terms = 3              # split-bf16 products of the bf16 tail (1: plain bf16)
         self.precision = 'fp32'
+        self.train_bank_precision = 'fp32'
+        self.train_bank_split_forward = False  # 'bf16x3' training: the bank's forward too as split-bf16 (set_train_bank_precision)
+        self.set_train_bank_precision(opt.get('train_bank_precision', 'fp32'))
         self.attention_choice = 'faithful'
         self.attention = 'faithful'
         self.set_precision(opt.get('precision', 'fp32'))
@@ -272,6 +275,21 @@ class Multi_GCN_Multihead_Att(nn.Module):
             if isinstance(m, MultiHeadAttention):
                 m.precision = precision
         return self.set_attention(self.attention_choice)
+
+    def set_train_bank_precision(self, mode):
+        """How the TRAINING step runs the two image memory banks' products.  'fp32' (default): the exact-f32 MFMA.  'bf16x3':
+        the weight gradient and the map gradient of each bank as split-bf16 on the bf16 matrix pipe (three MFMAs per product,
+        fp32 accumulation, ~2^-16 relative; csrc/bank_grad_split.hip), at every shape.  The bank's forward stays the fp32
+        kernel: so the logits and every other gradient are bit for bit those of 'fp32' mode, and the step stays inside the
+        1e-4 training gate.  `train_bank_split_forward = True` also runs the forward as split-bf16 (ops.imgbank_pool_split,
+        where K % 64 == 0, P % 4 == 0, P <= 224, N <= 304) and saves another ~1.1 ms per step at B = 256, but the bank's
+        ~5e-6 error is amplified by the fusion attention's backward to 1.4e-4 of a key-projection gradient's largest magnitude
+        (measured, DESIGN.md section 11): outside that gate, hence off.  `precision` must still be 'fp32' in training mode;
+        eval, captured graphs, schedules and the state_dict do not depend on this switch."""
+        if mode not in _train.BANK_PRECISIONS:
+            raise ValueError("train_bank_precision must be 'fp32' or 'bf16x3'")
+        self.train_bank_precision = mode
+        return self
 
     def set_attention(self, attention):
         """'faithful' (default): the fusion attention projects K and V from the memory bank as the reference does
@@ -644,7 +662,12 @@ class Multi_GCN_Multihead_Att(nn.Module):
             maps = self._train_maps(trunk_in, 'object_feature' if tag == 'obj' else 'place_feature')
             setattr(self, 'object_feature' if tag == 'obj' else 'place_feature', maps)      # MODEL:450,482 keep them
             f3 = (maps if maps.requires_grad else maps.detach()).float().contiguous().view(B, maps.shape[1], -1)
-            bank[tag], pooled = _train.ImgBankFunction.apply(f3, lin.weight, lin.bias, self._wt(lin))
+            if self.train_bank_precision == 'fp32':
+                bank[tag], pooled = _train.ImgBankFunction.apply(f3, lin.weight, lin.bias, self._wt(lin))
+            else:
+                fits = self.train_bank_split_forward and _train.split_forward_fits(f3.shape[1], f3.shape[2], lin.out_features)
+                bank[tag], pooled = _train.ImgBankFunction.apply(f3, lin.weight, lin.bias, None if fits else self._wt(lin),
+                                                                 self.train_bank_precision, self._wp_split(lin) if fits else None)
             pair = self._adj_pair(A)
             G = self.gc2(self.gc1(inp[0].float().contiguous(), pair, act=ops.ACT_LRELU2), pair)       # [C, 2048]
             x = _train.linear(pooled, G)                                  # pooled @ G^T -> [B, C]

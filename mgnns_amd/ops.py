@@ -1687,9 +1687,10 @@ def train_eltwise(op, a, b):
 
 
 # ---- training mode of the model around the fusion stacks (csrc/model_train.hip) -----------------------------------------
-def imgbank_wgrad(feat, dbank):
+def imgbank_wgrad(feat, dbank, split=False):
     """Weight gradient of an image memory bank bank[b,p,:] = W feat[b,:,p] + c (mgnns_imgbank_wgrad): feat [B, K, P] in its
-    native layout, dbank [B, P, N] -> (dW [N, K], db [N]).  Exact-f32 MFMA, samples reduced in a fixed order."""
+    native layout, dbank [B, P, N] -> (dW [N, K], db [N]).  Exact-f32 MFMA, samples reduced in a fixed order.  split: the
+    split-bf16 kernel (mgnns_imgbank_wgrad_split: three bf16 MFMAs per product, fp32-class, same contract)."""
     _chk(feat, "feature map", ndim=3)
     _chk(dbank, "dbank", ndim=3)
     B, K, P = feat.shape
@@ -1699,10 +1700,10 @@ def imgbank_wgrad(feat, dbank):
     dW = torch.empty(N, K, device=feat.device, dtype=torch.float32)
     db = torch.empty(N, device=feat.device, dtype=torch.float32)
     L = _lib.lib()
-    nbytes = L.mgnns_imgbank_wgrad_workspace_bytes(B, K, P, N)
+    name = "mgnns_imgbank_wgrad_split" if split else "mgnns_imgbank_wgrad"
+    nbytes = getattr(L, name + "_workspace_bytes")(B, K, P, N)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
-    _launch("mgnns_imgbank_wgrad", ("mgnns_imgbank_wgrad", B, P), L.mgnns_imgbank_wgrad, _p(feat), _p(dbank), B, K, P, N, _p(dW),
-            _p(db), _p(ws), nbytes, _stream())
+    _launch(name, (name, B, P), getattr(L, name), _p(feat), _p(dbank), B, K, P, N, _p(dW), _p(db), _p(ws), nbytes, _stream())
     return dW, db
 
 
@@ -1718,11 +1719,13 @@ def map_argmax(feat):
     return arg
 
 
-def imgbank_dgrad(dbank, weight, dpooled=None, arg=None, positions=None, out=None):
+def imgbank_dgrad(dbank, weight, dpooled=None, arg=None, positions=None, out=None, split=False):
     """Gradient with respect to the feature map of an image memory bank and its max-pool (mgnns_imgbank_dgrad):
     dX[b,k,p] = sum_o weight[o,k] dbank[b,p,o] + (p == arg[b,k]) dpooled[b,k] -> dX [B, K, P].  dbank [B, P, N], or None for the
     pooled term alone (then `positions` = P); weight [N, K] (the nn.Linear's); dpooled [B, K] with arg [B, K] int32 (map_argmax),
-    or both None; out: a [B, K, P] tensor to write instead of a new one.  Exact-f32 MFMA, bit-identical from call to call."""
+    or both None; out: a [B, K, P] tensor to write instead of a new one.  Exact-f32 MFMA, bit-identical from call to call.
+    split: the split-bf16 kernel (mgnns_imgbank_dgrad_split: three bf16 MFMAs per product, fp32-class, same contract; the
+    pooled term alone has no product and runs today's kernel)."""
     _chk(weight, "weight", ndim=2)
     N, K = weight.shape
     if (dpooled is None) != (arg is None):
@@ -1751,7 +1754,14 @@ def imgbank_dgrad(dbank, weight, dpooled=None, arg=None, positions=None, out=Non
         dX = _chk(out, "out", ndim=3)
         if tuple(dX.shape) != (B, K, P):
             raise ValueError("out %s is not [%d, %d, %d]" % (tuple(dX.shape), B, K, P))
-    _launch("mgnns_imgbank_dgrad", ("mgnns_imgbank_dgrad", B, P), _lib.lib().mgnns_imgbank_dgrad, _p(dbank), _p(weight), _p(dpooled),
+    L = _lib.lib()
+    if split and dbank is not None:
+        nbytes = L.mgnns_imgbank_dgrad_split_workspace_bytes(B, K, P, N)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        _launch("mgnns_imgbank_dgrad_split", ("mgnns_imgbank_dgrad_split", B, P), L.mgnns_imgbank_dgrad_split, _p(dbank), _p(weight),
+                _p(dpooled), _p(arg), B, K, P, N, _p(dX), _p(ws), nbytes, _stream())
+        return dX
+    _launch("mgnns_imgbank_dgrad", ("mgnns_imgbank_dgrad", B, P), L.mgnns_imgbank_dgrad, _p(dbank), _p(weight), _p(dpooled),
             _p(arg), B, K, P, N, _p(dX), _stream())
     return dX
 

@@ -147,16 +147,38 @@ def linear(x, lin_or_w, b=None):
     return y.view(*shp[:-1], y.shape[-1])
 
 
+BANK_PRECISIONS = ('fp32', 'bf16x3')
+
+
+def split_forward_fits(K, P, N):
+    """The shapes the split-bf16 bank kernel (ops.imgbank_pool_split) takes; any other map runs the fp32 forward."""
+    return K % 64 == 0 and P % 4 == 0 and 0 < P <= 224 and 0 < N <= 304
+
+
 class ImgBankFunction(torch.autograd.Function):
     """(bank [B, P, N], pooled [B, K]) = the fp32 memory bank and max-pool of a feature map f [B, K, P] (ops.imgbank_pool; wt =
     the bank kernel's transposed weight).  The weight and bias get gradients from ops.imgbank_wgrad (skipped when neither requires
     one).  A map that requires a gradient gets dX = W^T dbank + the max-pool's gradient at each row's first maximum
     (ops.imgbank_dgrad over ops.map_argmax of the saved map, both in the backward only); either incoming gradient may be absent.
-    For a map that requires none, pooled is a constant and neither kernel is launched."""
+    For a map that requires none, pooled is a constant and neither kernel is launched.
+    Two optional trailing arguments: mode ('fp32', the default, or 'bf16x3') and w_split (ops.pack_weight_bf16_split of the
+    weight, or None).  'bf16x3' runs the three products on the bf16 matrix pipe at fp32-class accuracy: both gradients through
+    the split-bf16 kernels at every shape, the forward through ops.imgbank_pool_split where w_split is given and the shape fits
+    (split_forward_fits; wt may then be None), else through the fp32 kernel.  pooled is exact in either mode."""
 
     @staticmethod
-    def forward(ctx, f, weight, bias, wt):
-        bank, pooled = ops.imgbank_pool(f, wt, bias.detach(), weight.shape[0])
+    def forward(ctx, f, weight, bias, wt, *mode):
+        split = bool(mode) and mode[0] == 'bf16x3'
+        if mode and mode[0] not in BANK_PRECISIONS:
+            raise ValueError("ImgBankFunction: mode must be one of %s, got %r" % (BANK_PRECISIONS, mode[0]))
+        w_split = mode[1] if len(mode) > 1 else None
+        N = weight.shape[0]
+        if split and w_split is not None and split_forward_fits(f.shape[1], f.shape[2], N):
+            bank, halves = ops.imgbank_pool_split(f, w_split, bias.detach(), N, want_pool=True, want_f32=True)
+            pooled = halves.amax(dim=1)            # the exact maxima of the two region halves
+        else:
+            bank, pooled = ops.imgbank_pool(f, wt, bias.detach(), N)
+        ctx.split, ctx.extra = split, len(mode)
         ctx.map_grad = ctx.needs_input_grad[0]
         if ctx.map_grad:
             ctx.save_for_backward(f, weight)
@@ -169,22 +191,25 @@ class ImgBankFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dbank, dpooled):
         want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        rest = (None,) * (1 + ctx.extra)
+        sp = (True,) if ctx.split else ()          # (positional: fp32 mode makes today's calls, argument for argument)
         if not ctx.map_grad:
             if not want_w:
-                return None, None, None, None
+                return (None, None, None) + rest
             f, = ctx.saved_tensors
-            dw, db = ops.imgbank_wgrad(f, dbank.contiguous())
-            return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
+            dw, db = ops.imgbank_wgrad(f, dbank.contiguous(), *sp)
+            return (None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None) + rest
         f, weight = ctx.saved_tensors
         dbank = None if dbank is None else dbank.contiguous()
         dw = db = dx = None
         if want_w and dbank is not None:
-            dw, db = ops.imgbank_wgrad(f, dbank)
+            dw, db = ops.imgbank_wgrad(f, dbank, *sp)
+        kw = {"split": True} if ctx.split else {}
         if dpooled is not None:
-            dx = ops.imgbank_dgrad(dbank, weight, dpooled.contiguous(), ops.map_argmax(f), positions=f.shape[2])
+            dx = ops.imgbank_dgrad(dbank, weight, dpooled.contiguous(), ops.map_argmax(f), positions=f.shape[2], **kw)
         elif dbank is not None:
-            dx = ops.imgbank_dgrad(dbank, weight)
-        return dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
+            dx = ops.imgbank_dgrad(dbank, weight, **kw)
+        return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None) + rest
 
 
 class GCNFunction(torch.autograd.Function):

@@ -12,7 +12,12 @@ formulation (nn.LSTM on packed sequences, a scatter-max text GCN).
 map gradients, imgbank_dgrad alone (dense, and with the max-pool scatter) with its % of the fp32 matrix peak next to imgbank_wgrad
 at the same shape, map_argmax alone with its GB/s next to a torch copy of the same bytes, and torch autograd's F.linear
 backward-to-input at the same shape.
-Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps]"""
+--bank-precision fp32|bf16x3 (with --model-only or --maps): the model's set_train_bank_precision for the step timings; with
+bf16x3, --maps also times the three image-bank products (forward, wgrad, dgrad) in both forms and the whole step in both modes,
+alternately in one process, three rounds each, best and all rounds reported (csrc/bank_grad_split.hip).
+--steps-only K: nothing but K whole-model training steps with map gradients in the chosen bank precision -- the run a kernel
+trace is taken of (rocprofv3 --kernel-trace --stats, as tools/prof.sh does for bench.py; table by tools/rocpd_stats.py).
+Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps | --steps-only K] [--bank-precision fp32|bf16x3]"""
 import json
 import math
 import os
@@ -181,6 +186,13 @@ def torch_model(model, tf, tbank, tmask, maps, inps, lq):
     return model.multi_linear_2(F.dropout(model.multi_linear_1(multi), model.dropout.p))
 
 
+def bank_precision():
+    mode = sys.argv[sys.argv.index("--bank-precision") + 1] if "--bank-precision" in sys.argv else "fp32"
+    if mode not in ("fp32", "bf16x3"):
+        raise SystemExit("bench_train: --bank-precision fp32|bf16x3")
+    return mode
+
+
 def model_case(n):
     from mgnns_amd import harness, synth
     cfg = synth.CONFIGS["mvsa_multiple_b256"]
@@ -188,10 +200,11 @@ def model_case(n):
     A_obj, A_place = harness.synthetic_adjacencies(cfg)
     inp = synth.make_inputs(cfg, B=cfg.B, seed=7, pmi=pmi)
     model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV).train().freeze_text_encoders()
+    model.set_train_bank_precision(bank_precision())
     args = harness.call_args(inp, DEV)
     B = args[0].shape[0]
     G = torch.randn(B, cfg.NL, device=DEV)
-    res = {"case": "model_%s_fp32" % cfg.name, "B": B}
+    res = {"case": "model_%s_fp32" % cfg.name, "B": B, "bank_precision": model.train_bank_precision}
 
     def step():
         model.zero_grad(set_to_none=True)
@@ -325,10 +338,13 @@ def maps_case(n):
     A_obj, A_place = harness.synthetic_adjacencies(cfg)
     inp = synth.make_inputs(cfg, B=cfg.B, seed=7, pmi=pmi)
     model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV).train().freeze_text_encoders()
+    mode = bank_precision()
+    model.set_train_bank_precision(mode)
     args = list(harness.call_args(inp, DEV))
+    plain = list(args)
     B = args[0].shape[0]
     G = torch.randn(B, cfg.NL, device=DEV)
-    res = {"case": "maps_%s_fp32" % cfg.name, "B": B}
+    res = {"case": "maps_%s_fp32" % cfg.name, "B": B, "bank_precision": mode}
 
     def step():
         model.zero_grad(set_to_none=True)
@@ -379,13 +395,77 @@ def maps_case(n):
     t_all = timeit(torch_dgrad, n)
     t_fwd = timeit(lambda: F.linear(xt.detach(), W), n)
     res["torch_linear_bwd_to_input_us"] = round(t_all - t_fwd, 1)
+    if mode == "bf16x3":
+        res["split_vs_fp32"] = split_case(model, args, plain, step, f3, W, dbank, dpooled, arg, n)
     return res
+
+
+def split_case(model, args, plain, step, f3, W, dbank, dpooled, arg, n):
+    """The image bank's three products in both forms, and the whole step in both modes: alternately, three rounds each."""
+    lin = model.liner_img_object
+    N = W.shape[0]
+    wt, wp, bias = model._wt(lin), model._wp_split(lin), lin.bias.detach()
+    pairs = {
+        "bank_fwd": (lambda: ops.imgbank_pool(f3, wt, bias, N), lambda: ops.imgbank_pool_split(f3, wp, bias, N)),
+        "bank_wgrad": (lambda: ops.imgbank_wgrad(f3, dbank), lambda: ops.imgbank_wgrad(f3, dbank, split=True)),
+        "bank_dgrad": (lambda: ops.imgbank_dgrad(dbank, W), lambda: ops.imgbank_dgrad(dbank, W, split=True)),
+        "bank_dgrad_with_scatter": (lambda: ops.imgbank_dgrad(dbank, W, dpooled, arg),
+                                    lambda: ops.imgbank_dgrad(dbank, W, dpooled, arg, split=True)),
+    }
+    out = {}
+    for name, (f32, spl) in pairs.items():
+        ta, tb = [], []
+        for _ in range(3):
+            ta.append(timeit(f32, n))
+            tb.append(timeit(spl, n))
+        out[name] = {"fp32_us": round(min(ta), 1), "bf16x3_us": round(min(tb), 1), "ratio": round(min(tb) / min(ta), 3),
+                     "fp32_runs_us": [round(t, 1) for t in ta], "bf16x3_runs_us": [round(t, 1) for t in tb]}
+    leaves = list(args)
+    for key, use in (("step_map_grads", leaves), ("step", plain)):
+        args[:] = use
+        ta, tb, tc = [], [], []
+        for _ in range(3):
+            model.set_train_bank_precision("fp32")
+            ta.append(timeit(step, n))
+            model.set_train_bank_precision("bf16x3")
+            tb.append(timeit(step, n))
+            model.train_bank_split_forward = True
+            tc.append(timeit(step, n))
+            model.train_bank_split_forward = False
+        out[key] = {"fp32_us": round(min(ta), 1), "bf16x3_us": round(min(tb), 1), "ratio": round(min(tb) / min(ta), 3),
+                    "bf16x3_split_forward_us": round(min(tc), 1), "fp32_runs_us": [round(t, 1) for t in ta],
+                    "bf16x3_runs_us": [round(t, 1) for t in tb], "bf16x3_split_forward_runs_us": [round(t, 1) for t in tc]}
+    args[:] = leaves
+    return out
+
+
+def steps_only(k):
+    from mgnns_amd import harness, synth
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=cfg.B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV).train().freeze_text_encoders()
+    model.set_train_bank_precision(bank_precision())
+    args = list(harness.call_args(inp, DEV))
+    for i in (3, 4):
+        args[i] = args[i].detach().clone().requires_grad_(True)
+    G = torch.randn(args[0].shape[0], cfg.NL, device=DEV)
+    for _ in range(k):
+        model.zero_grad(set_to_none=True)
+        args[3].grad = args[4].grad = None
+        torch.autograd.backward(model(*args), G)
+    torch.cuda.synchronize()
+    return {"case": "steps_%s" % cfg.name, "steps": k, "bank_precision": model.train_bank_precision}
 
 
 def main():
     n = int(sys.argv[sys.argv.index("--iters") + 1]) if "--iters" in sys.argv else 20
     if not torch.cuda.is_available():
         raise SystemExit("bench_train: no GPU")
+    if "--steps-only" in sys.argv:
+        print(json.dumps(steps_only(int(sys.argv[sys.argv.index("--steps-only") + 1]))), flush=True)
+        return
     if "--maps" in sys.argv:
         print(json.dumps(maps_case(n)), flush=True)
         return
