@@ -2,7 +2,7 @@
 // and imgbank_dgrad_kernel (map_grad.hip) on the bf16 matrix pipe, with those kernels' contracts:
 //     dW[o,c]   = sum_{b,p} dBank[b,p,o] X[b,c,p],   db[o] = sum_{b,p} dBank[b,p,o]
 //     dX[b,k,p] = sum_o W[o,k] dBank[b,p,o]  +  [p == arg[b,k]] dPooled[b,k]
-// Every fp32 operand x is carried as hi = bf16(x), lo = bf16(x - hi) (round to nearest even, v_cvt_pk_bf16_f32) and a product
+// Every fp32 operand x is carried as hi = bf16(x), lo = bf16(x - hi) (round to nearest even, bf16.hpp) and a product
 // is a_hi b_lo + a_lo b_hi + a_hi b_hi on v_mfma_f32_16x16x32_bf16 into one fp32 accumulator: ~2^-16 relative per product.
 // All inputs are plain fp32 in HBM in today's layouts; the split happens while a stage is written to LDS.  An operand fragment
 // of the 16x16x32 MFMA is 8 consecutive reduction indices of one row per lane (16 bytes): LDS holds 16-byte chunks as
@@ -11,28 +11,10 @@
 // from call to call.  DESIGN.md section 11.
 #include <type_traits>
 #include "common.hpp"
+#include "bf16.hpp"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
-
-__device__ __forceinline__ unsigned bs_pack2(float a, float b) {       // bf16(a) | bf16(b) << 16, RNE
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// 8 fp32 values -> the hi and lo chunks (8 bf16 each)
-__device__ __forceinline__ void bs_split8(const float (&x)[8], uint4& hi, uint4& lo) {
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        h[q] = bs_pack2(x[2 * q], x[2 * q + 1]);
-        l[q] = bs_pack2(x[2 * q] - __builtin_bit_cast(float, h[q] << 16), x[2 * q + 1] - __builtin_bit_cast(float, h[q] & 0xFFFF0000u));
-    }
-    hi = uint4{h[0], h[1], h[2], h[3]};
-    lo = uint4{l[0], l[1], l[2], l[3]};
-}
 
 __device__ __forceinline__ f32x4 bs_mfma(uint4 a, uint4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -151,13 +133,13 @@ __global__ __launch_bounds__(WS_NT) void imgbank_wgrad_split_kernel(const float*
             if (t < WS_A_TASKS) {
                 if (do_db) dbacc[i] += ((ra[i][0] + ra[i][1]) + (ra[i][2] + ra[i][3])) + ((ra[i][4] + ra[i][5]) + (ra[i][6] + ra[i][7]));
                 uint4 h, l;
-                bs_split8(ra[i], h, l);
+                mg_split8(ra[i], h, l);
                 hi[t] = h;                                          // [kc][o] = kc * 320 + o = t
                 lo[t] = l;
             }
         }
         uint4 h, l;
-        bs_split8(rb, h, l);
+        mg_split8(rb, h, l);
         hi[4 * WS_O + bkc * WS_C + bc] = h;
         lo[4 * WS_O + bkc * WS_C + bc] = l;
     };
@@ -287,7 +269,7 @@ __global__ void imgbank_wsplit_kernel(const float* __restrict__ W, int N, int K,
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = (k < K && 8 * oc + j < N) ? W[(size_t)(8 * oc + j) * K + k] : 0.f;
         uint4 h, l;
-        bs_split8(x, h, l);
+        mg_split8(x, h, l);
         Wh[i] = h;
         Wl[i] = l;
     }
@@ -352,7 +334,7 @@ __global__ __launch_bounds__(DS_NT) void imgbank_dgrad_split_kernel(const float*
             const int u = tid + DS_NT * i;
             if (u < DS_TASKS) {
                 uint4 h, l;
-                bs_split8(rb[i], h, l);
+                mg_split8(rb[i], h, l);
                 const int at = ((u >> 3) & 3) * DS_PR + 8 * (u >> 5) + (u & 7);
                 hi[at] = h;
                 lo[at] = l;

@@ -9,6 +9,8 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));              // what the raw_buffer_{load,store}_b128 builtins carry
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));         // an MFMA operand fragment (conversions: bf16.hpp)
 
 void mgnns_set_error(const char* fmt, ...);
 int mg_ensure_dyn_lds(const void* fn, int bytes);   // api.hip; 0 or MGNNS_ERR_LAUNCH (error text set)
@@ -43,6 +45,16 @@ __device__ __forceinline__ float mg_act(float v, int act) {
     if (act == MGNNS_ACT_RELU) return fmaxf(v, 0.0f);
     if (act == MGNNS_ACT_LRELU2) return v > 0.0f ? v : 0.2f * v;
     return v;
+}
+
+// Buffer resource over [p, p + bytes): a wave-uniform base in four SGPRs, addressed by 32-bit per-lane byte offsets.  Raw
+// (stride 0) and range checked in bytes: a load beyond `bytes` returns 0 and a store there is dropped.  The fourth word,
+// 0x00027000, is DATA_FORMAT = 32 (bits 18:15 = 4) with NUM_FORMAT = float (bits 14:12 = 7) -- the raw_buffer_* builtins
+// ignore the format but the hardware wants a valid one -- and every other field 0: no swizzle, no index stride, no
+// ADD_TID.  A typed pointer to mutable memory gives the same resource as a const void* one: only the address is kept.  `bytes`
+// is narrowed to the resource's 32-bit NUM_RECORDS here, whatever width the caller computed it in (0x7fffffff: "no bound").
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mg_buffer(const void* p, size_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00027000);
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope fence, which the compiler

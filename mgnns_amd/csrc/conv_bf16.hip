@@ -16,26 +16,11 @@
 // Narrow layers (C_out = 64) use a 256 x 64 tile (NJ = 2).  The last convolution of a trunk writes the
 // [B, 2048, 14, 14] fp32 NCHW map the fusion path reads (out_nchw = 1).
 #include "common.hpp"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16.hpp"
 
 namespace {
 
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-__device__ __forceinline__ unsigned int f2bf(float f) {       // round to nearest even; inputs are finite
-    unsigned int u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ float bf2f(unsigned int h) { return __uint_as_float(h << 16); }
-// two fp32 -> packed bf16x2 (round to nearest even) in ONE instruction (no builtin for it on gfx950); the shift / add form
-// above costs five VALU operations per value, which made the convolution epilogue VALU-bound
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv_fold_bn_kernel(const float* __restrict__ w, const float* __restrict__ cbias,
@@ -55,7 +40,7 @@ __global__ __launch_bounds__(256) void conv_fold_bn_kernel(const float* __restri
             else { kh = k / (KW * Cin); kw = (k / Cin) % KW; c = k % Cin; }          // k = (kh, kw, c): NHWC implicit GEMM
             v = w[(((size_t)o * Cin + c) * KH + kh) * KW + kw] * scale;
         }
-        wt[(size_t)o * ld + k] = (unsigned short)f2bf(v);
+        wt[(size_t)o * ld + k] = (unsigned short)mg_bf16_rne_finite(v);
     }
     if (threadIdx.x == 0) {
         const float cb = cbias ? cbias[o] : 0.f;
@@ -92,7 +77,7 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(const float* __restrict
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
         const int e = tid + 256 * i;
-        if (e < NE) patch[e] = (unsigned short)pack2(pv[i], 0.f);
+        if (e < NE) patch[e] = (unsigned short)mg_bf16x2(pv[i], 0.f);
     }
     const int fr = lane & 15, fg = lane >> 4;
     // weights: lane (n = fr, k-group fg) of column tile jt, k-step s
@@ -143,8 +128,8 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(const float* __restrict
                 const int n = jt * 16 + fg * 4;
                 const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + n);
                 uint2 o;
-                o.x = pack2(fmaxf(acc[jt][0] + bv[0], 0.f), fmaxf(acc[jt][1] + bv[1], 0.f));
-                o.y = pack2(fmaxf(acc[jt][2] + bv[2], 0.f), fmaxf(acc[jt][3] + bv[3], 0.f));
+                o.x = mg_bf16x2(fmaxf(acc[jt][0] + bv[0], 0.f), fmaxf(acc[jt][1] + bv[1], 0.f));
+                o.y = mg_bf16x2(fmaxf(acc[jt][2] + bv[2], 0.f), fmaxf(acc[jt][3] + bv[3], 0.f));
                 *reinterpret_cast<uint2*>(dst + n) = o;
             }
         }
@@ -178,8 +163,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const unsigned short*
                 const unsigned int u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    m[2 * j] = fmaxf(m[2 * j], bf2f(u[j] & 0xFFFFu));
-                    m[2 * j + 1] = fmaxf(m[2 * j + 1], bf2f(u[j] >> 16));
+                    m[2 * j] = fmaxf(m[2 * j], mg_bf16_f32(u[j] & 0xFFFFu));
+                    m[2 * j + 1] = fmaxf(m[2 * j + 1], mg_bf16_f32(u[j] >> 16));
                 }
             }
         }
@@ -204,11 +189,10 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const unsigned short*
 // History (all measured): one tile per workgroup with the DMA issue inside the eight compute waves: 6.96 ms per
 // 32 ResNet-101 images; 16-byte epilogue 6.12; persistent stream + inline-asm LDS reads 5.19 (a compute wave still stalled
 // ~1.2-1.4 k cycles per slice in the issue of its six DMA pieces -- the vector-memory path was backed up -- against ~0.7 k
-// cycles of its own MFMA work, in-kernel timer); v_cvt_pk_bf16_f32 epilogue 4.96; producer waves 4.73.
+// cycles of its own MFMA work, in-kernel timer); mg_bf16x2 epilogue 4.96; producer waves 4.73.
 constexpr int TM = 256, BK = 64, NSTAGE = 3;
 constexpr int A_BYTES = TM * BK * 2, A_PIECES = A_BYTES / 1024;      // 32 KB = 32 DMA pieces of 8 rows x 128 B
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs {
     const unsigned short* x;      // [B, H, W, Cin] bf16
@@ -374,7 +358,7 @@ __global__ __launch_bounds__(NTHR_WS) void conv_igemm_ws_kernel(const ConvArgs a
     };
     int cm0 = 0, cn0 = 0, ckt = 0;
     int cj = next_valid(jj0, cm0, cn0);
-    const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.ybytes, 0x00027000);
+    const __amdgpu_buffer_rsrc_t y_rsrc = mg_buffer(a.y, a.ybytes);
     const int ncl = wc * 16 * NJ + (fg & 1) * 16 + (fg >> 1) * 8;
     u32x4 rv[NJ / 2][4];
     f32x4 bs[NJ / 2][2];
@@ -473,10 +457,10 @@ __global__ __launch_bounds__(NTHR_WS) void conv_igemm_ws_kernel(const ConvArgs a
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o[r]), y_rsrc, ok ? off + (unsigned)(r * ohw * 4) : off, 0, 0);
                 } else {
                     i32x4 ov;
-                    ov[0] = (int)pack2(o[0], o[1]);
-                    ov[1] = (int)pack2(o[2], o[3]);
-                    ov[2] = (int)pack2(o[4], o[5]);
-                    ov[3] = (int)pack2(o[6], o[7]);
+                    ov[0] = (int)mg_bf16x2(o[0], o[1]);
+                    ov[1] = (int)mg_bf16x2(o[2], o[3]);
+                    ov[2] = (int)mg_bf16x2(o[4], o[5]);
+                    ov[3] = (int)mg_bf16x2(o[6], o[7]);
                     const unsigned int off = ok ? (unsigned int)(((size_t)m * a.Cout + n) * 2) : 0xFFFFFFF0u;
                     __builtin_amdgcn_raw_buffer_store_b128(ov, y_rsrc, off, 0, 0);
                 }

@@ -16,8 +16,7 @@
 // fetched from HBM once per XCD and a Bt byte once per super row (for M = K = 10 000, N = 1024: ~0.4 GB instead of
 // 1.6 GB + 1.6 GB with a row-major tile order).
 #include "common.hpp"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "bf16.hpp"
 
 namespace {
 
@@ -39,9 +38,7 @@ __global__ __launch_bounds__(256) void transpose_cast_bf16_kernel(const float* _
     for (int i = ty; i < 32; i += 8) {
         const int c = c0 + i, r = r0 + tx;                      // out row = c, out col = r
         if (c < cols && r < ld) {
-            unsigned int u = __float_as_uint(tile[tx][i]);
-            u += 0x7FFFu + ((u >> 16) & 1u);
-            y[(size_t)c * ld + r] = (unsigned short)(u >> 16);
+            y[(size_t)c * ld + r] = (unsigned short)mg_bf16_rne_finite(tile[tx][i]);
         }
     }
 }
@@ -314,9 +311,7 @@ __global__ __launch_bounds__(NTHR_WS) void gemm_bf16_nt_kernel(const unsigned sh
                 acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (m < M && n < N) {
                     if (c_bf16) {                                  // C is a bf16 matrix (ldc in elements): the operand of the next product
-                        unsigned lo, hi;
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(o[0]), "v"(o[1]));
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(o[2]), "v"(o[3]));
+                        const unsigned lo = mg_bf16x2(o[0], o[1]), hi = mg_bf16x2(o[2], o[3]);
                         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
                         *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned short*>(C) + (size_t)m * ldc + n) = u32x2_t{lo, hi};
                     } else {
@@ -368,9 +363,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_fixup_kernel(const float* __res
             for (int q = 0; q < 4; ++q) o[q] = mg_act(sum[q] + bv[q], act);
             if (m < M && n < N) {
                 if (c_bf16) {
-                    unsigned lo, hi;
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(o[0]), "v"(o[1]));
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(o[2]), "v"(o[3]));
+                    const unsigned lo = mg_bf16x2(o[0], o[1]), hi = mg_bf16x2(o[2], o[3]);
                     typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned short*>(C) + (size_t)m * ldc + n) = u32x2_t{lo, hi};
                 } else {
@@ -426,9 +419,7 @@ __device__ __forceinline__ void gemm256_store(f32x4 (&acc)[4][8], int cm0, int c
             for (int r = 0; r < 4; ++r) o[r] = mg_act(acc[i][jj][r] + bv[r], act);
             if (m < M && n < N) {
                 if (c_bf16) {                                      // C is a bf16 matrix (ldc in elements): the operand of the next product
-                    unsigned lo, hi;
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(o[0]), "v"(o[1]));
-                    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(o[2]), "v"(o[3]));
+                    const unsigned lo = mg_bf16x2(o[0], o[1]), hi = mg_bf16x2(o[2], o[3]);
                     typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
                     *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned short*>(C) + (size_t)m * ldc + n) = u32x2_t{lo, hi};
                 } else {
@@ -496,8 +487,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_256_kernel(const unsigned sh
     auto open_tile = [&](int j) {
         const int m0 = (rb0 + j / nct) * TM2, n0 = (j % nct) * TN2;
         const int mr = M - m0 < TM2 ? M - m0 : TM2, nr = N - n0 < TN2 ? N - n0 : TN2;
-        ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(A + (size_t)m0 * Kp), 0, mr * Kp * 2, 0x00027000);
-        rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Bt + (size_t)n0 * Kp), 0, nr * Kp * 2, 0x00027000);
+        ra = mg_buffer(A + (size_t)m0 * Kp, mr * Kp * 2);
+        rb = mg_buffer(Bt + (size_t)n0 * Kp, nr * Kp * 2);
     };
     open_tile(it);
     auto issue_one = [&](int g, int i) {                           // request i (0..3) of slice g
@@ -806,18 +797,15 @@ __global__ __launch_bounds__(NTHR160) void gemm_bf16_nt_160x256_kernel(const uns
                     for (int r = 0; r < 4; ++r) {
                         if (n + r >= N) continue;
                         if (c_bf16 & 1) {
-                            unsigned pk;
-                            asm("v_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(pk) : "v"(o[r]));
-                            reinterpret_cast<unsigned short*>(C)[(size_t)(n + r) * ldc + m] = (unsigned short)(pk & 0xFFFFu);
+                            const unsigned short h = mg_bf16(o[r]);
+                            reinterpret_cast<unsigned short*>(C)[(size_t)(n + r) * ldc + m] = h;
                         } else {
                             C[(size_t)(n + r) * ldc + m] = o[r];
                         }
                     }
                 } else if (!(c_bf16 & 2) && m < M && m < cm0 + TM160 && n < N) {
                     if (c_bf16 & 1) {
-                        unsigned lo, hi;
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(o[0]), "v"(o[1]));
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(o[2]), "v"(o[3]));
+                        const unsigned lo = mg_bf16x2(o[0], o[1]), hi = mg_bf16x2(o[2], o[3]);
                         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
                         *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned short*>(C) + (size_t)m * ldc + n) = u32x2_t{lo, hi};
                     } else {
@@ -880,8 +868,8 @@ __global__ __launch_bounds__(NTHR320) void gemm_bf16_nt_320x256_kernel(const uns
         const int j = jj0 + i * W;
         const int m0 = (rb0 + j / nct) * TM320, n0 = (j % nct) * TN320;
         const int mr = M - m0 < TM320 ? M - m0 : TM320, nr = N - n0 < TN320 ? N - n0 : TN320;
-        ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(A + (size_t)m0 * Kp), 0, mr * Kp * 2, 0x00027000);
-        rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Bt + (size_t)n0 * Kp), 0, nr * Kp * 2, 0x00027000);
+        ra = mg_buffer(A + (size_t)m0 * Kp, mr * Kp * 2);
+        rb = mg_buffer(Bt + (size_t)n0 * Kp, nr * Kp * 2);
     };
     open_tile(0);
     auto issue_one = [&](int g, int i) {                           // request i (0..5) of slice g, k slice ik of the open tile
@@ -974,9 +962,7 @@ __global__ __launch_bounds__(NTHR320) void gemm_bf16_nt_320x256_kernel(const uns
                 acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (m < M && n < N) {
                     if (c_bf16) {
-                        unsigned lo, hi;
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(lo) : "v"(o[0]), "v"(o[1]));
-                        asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(hi) : "v"(o[2]), "v"(o[3]));
+                        const unsigned lo = mg_bf16x2(o[0], o[1]), hi = mg_bf16x2(o[2], o[3]);
                         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
                         *reinterpret_cast<u32x2_t*>(reinterpret_cast<unsigned short*>(C) + (size_t)m * ldc + n) = u32x2_t{lo, hi};
                     } else {

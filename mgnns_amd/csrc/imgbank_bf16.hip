@@ -12,14 +12,15 @@
 // against 3.5 TB/s for rounds 1-2's register path (two workgroups per sample, each reading 448-B half rows: 1.19x sector
 // over-fetch; producer waves whose every computing cycle was a cycle the memory pipe was not refilled).
 // Per k-step all eight waves (a) turn the landed fp32 slot into the bf16 MFMA operand image [p][32 k] (LDS -> registers ->
-// v_cvt_pk_bf16_f32 -> LDS, 16-B chunks swizzled so that both sides are conflict-free), (b) take the max-pool of its 32 rows,
+// mg_bf16x2 -> LDS, 16-B chunks swizzled so that both sides are conflict-free), (b) take the max-pool of its 32 rows,
 // (c) after ONE barrier run the k-step's MFMAs: wave (rg, cg) owns row tiles 7 rg .. and column tiles 5 cg .. (7 x 5 tiles,
 // v_mfma_f32_16x16x32_bf16, W fragments fragment-major from L2, two k-steps ahead).  Epilogue through LDS: bank rows leave
 // as 16-B lanes.
 #include "common.hpp"
+#include "bf16.hpp"
+#include "sq_mha_util.hpp"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #ifdef MG_IMG_TRACE
@@ -42,13 +43,6 @@ constexpr int OCH = OUT_LD / 8;         // 40 chunks per output row
 constexpr int OSTR = OUT_LD * 2 + 16;   // epilogue LDS row stride in bytes (656: rows land on distinct banks)
 constexpr int NTHR = 512;
 
-// two fp32 -> packed bf16x2 (round to nearest even) in ONE instruction; there is no builtin for it on gfx950
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
 // Wp[nt][ks][lane][8] = W[nt*16 + (lane&15)][ks*32 + (lane>>4)*8 + j]   (0 for rows >= N)
 __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ W, int N, int K, unsigned short* __restrict__ Wp) {
     const int KS = K / 32;
@@ -63,10 +57,10 @@ __global__ __launch_bounds__(256) void pack_w_kernel(const float* __restrict__ W
         uint4 o = make_uint4(0u, 0u, 0u, 0u);
         if (row < N) {
             const float* w = W + (size_t)row * K + k0;
-            o.x = pack2(w[0], w[1]);
-            o.y = pack2(w[2], w[3]);
-            o.z = pack2(w[4], w[5]);
-            o.w = pack2(w[6], w[7]);
+            o.x = mg_bf16x2(w[0], w[1]);
+            o.y = mg_bf16x2(w[2], w[3]);
+            o.z = mg_bf16x2(w[4], w[5]);
+            o.w = mg_bf16x2(w[6], w[7]);
         }
         reinterpret_cast<uint4*>(Wp)[i] = o;
     }
@@ -92,19 +86,12 @@ static_assert((size_t)PMAX * OSTR <= SMEM_BYTES, "the epilogue stages the bank r
 constexpr int NRW = MG_IMG_NRW, NRM = MT - NRW;          // row tiles of a W wave (it also requests the W fragments) / of the others
 
 // LDS accesses of the main loop are inline asm: hipcc puts s_waitcnt vmcnt(0) in front of every LDS access it can see while an
-// LDS-DMA may be in flight, which would drain the ring at every step.  The caller orders them (lgkmcnt / barriers).
-template <int N> struct ICI { static constexpr int v = N; };
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for_img(F&& f) {
-    if constexpr (I < N) {
-        f(ICI<I>{});
-        static_for_img<I + 1, N>(f);
-    }
-}
+// LDS-DMA may be in flight, which would drain the ring at every step.  The caller orders them (lgkmcnt / barriers); their
+// immediate offsets and counts come from the compile-time loops of sq_mha_util.hpp.
 
 // (v_max_f32 through asm: fmaxf costs a canonicalising v_max_f32 v, v, v per operand in front of the real one)
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// Max over the four 16-lane rows of the wave for FOUR values at once (a transposing reduction, sq_mha_bf16.hip::rows4_sum4 with
+// Max over the four 16-lane rows of the wave for FOUR values at once (a transposing reduction, sq_mha_util.hpp::rows4_sum4 with
 // max): on return the rows of the result hold [a, c, b, d] folded over the rows.
 __device__ __forceinline__ float rows4_max4(float a, float b, float c, float d) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\ts_nop 1"
@@ -144,10 +131,8 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
     const int RB = P * 4;                                // bytes of a map row
     const unsigned lds0 = mg_lds_addr(smem), abuf = lds0 + (unsigned)OFF_A, wbuf = lds0 + (unsigned)OFF_W;
     const unsigned myring = lds0 + (unsigned)(wave * WRING);
-    const __amdgpu_buffer_rsrc_t f_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(feat + (size_t)b * K * P), 0, K * P * (int)sizeof(float), 0x00027000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(Wp), 0, NT * nks * 1024, 0x00027000);
+    const __amdgpu_buffer_rsrc_t f_rsrc = mg_buffer(feat + (size_t)b * K * P, K * P * (int)sizeof(float));
+    const __amdgpu_buffer_rsrc_t w_rsrc = mg_buffer(Wp, NT * nks * 1024);
     const int nquad = P >> 2;
 
     // ---- the map stream: unit j of this wave = rows 8 oct + 4 half .. + 3 of k-step j -> unit slot j % 3; one row (P / 4 lanes
@@ -226,7 +211,7 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
         constexpr int k = decltype(kc)::v;
         if constexpr (k < 4) {                           // half chunk of region 4 pq + k
             u32x2 c;
-            c[0] = pack2(v[0][k], v[1][k]); c[1] = pack2(v[2][k], v[3][k]);
+            c[0] = mg_bf16x2(v[0][k], v[1][k]); c[1] = mg_bf16x2(v[2][k], v[3][k]);
             asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(cv_ab), "v"(c), "n"(k * 64) : "memory");
         } else if constexpr (k < 8) {                    // maximum of row k - 4 over this lane's four regions
             constexpr int j = k - 4;
@@ -269,7 +254,7 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
         for (int t = 0; t < NW; ++t) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[t]) : "v"(w_rd + wb), "n"(t * 1024) : "memory");
 #pragma unroll
         for (int i = 0; i < NR; ++i) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bf[i]) : "v"(a_rd + ab), "n"(i * 1024) : "memory");
-        static_for_img<0, NR>([&](auto ic) {
+        mg_mha::static_for<0, NR>([&](auto ic) {
             constexpr int i = decltype(ic)::v;
             // row tile i's MFMAs wait for the W fragments and map fragments 0 .. i only: younger are the other fragments and the
             // image writes of the conversion pieces issued so far (pieces 0-3 sit behind MFMAs Q0 .. Q0 + 3)
@@ -277,13 +262,13 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
             asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NR - 1 - i + wr) : "memory");
             __builtin_amdgcn_sched_barrier(0);
             const bf16x8 bv = __builtin_bit_cast(bf16x8, bf[i]);
-            static_for_img<0, NW>([&](auto tc) {
+            mg_mha::static_for<0, NW>([&](auto tc) {
                 constexpr int t = decltype(tc)::v, q = i * NW + t;
                 acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[t]), bv, acc[i][t], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (WS && q < 5) dma_w(s + 1, q);
                 else if constexpr (q < Q0) dma_rows(s + NUS, (q - (Q0 - ND)) * (UROWS / ND), UROWS / ND);
-                else if constexpr (q - Q0 < NCV) { if (cv) cv_piece(ICI<q - Q0>{}, s + 1); }
+                else if constexpr (q - Q0 < NCV) { if (cv) cv_piece(mg_mha::IC<q - Q0>{}, s + 1); }
                 __builtin_amdgcn_sched_barrier(0);
             });
         });
@@ -301,7 +286,7 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
     cv_reads(0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    static_for_img<0, NCV>([&](auto kc) { cv_piece(kc, 0); });
+    mg_mha::static_for<0, NCV>([&](auto kc) { cv_piece(kc, 0); });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 #ifdef MG_IMG_TRACE
@@ -332,8 +317,8 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
         __builtin_amdgcn_sched_barrier(0);
         MG_TT(4, t0);
     };
-    for (int s = 0; s + 1 < nks; ++s) step(s, ICI<1>{});
-    step(nks - 1, ICI<0>{});                             // (nothing left to convert)
+    for (int s = 0; s + 1 < nks; ++s) step(s, mg_mha::IC<1>{});
+    step(nks - 1, mg_mha::IC<0>{});                             // (nothing left to convert)
 #ifdef MG_IMG_TRACE
     if (lane == 0 && (wave == 0 || wave == 4) && (blockIdx.x == 0 || blockIdx.x == 129)) {
         unsigned long long* g = g_img_trace[(blockIdx.x ? 2 : 0) + (wave >> 2)];
@@ -359,8 +344,8 @@ __device__ __forceinline__ void img_wave(unsigned char* smem, const float* __res
         for (int i = 0; i < NR; ++i) {
             const int row = (tile0 + i) * 16 + (lane & 15);
             uint2 o;
-            o.x = pack2(n + 0 < N ? acc[i][t][0] + bvv[0] : 0.f, n + 1 < N ? acc[i][t][1] + bvv[1] : 0.f);
-            o.y = pack2(n + 2 < N ? acc[i][t][2] + bvv[2] : 0.f, n + 3 < N ? acc[i][t][3] + bvv[3] : 0.f);
+            o.x = mg_bf16x2(n + 0 < N ? acc[i][t][0] + bvv[0] : 0.f, n + 1 < N ? acc[i][t][1] + bvv[1] : 0.f);
+            o.y = mg_bf16x2(n + 2 < N ? acc[i][t][2] + bvv[2] : 0.f, n + 3 < N ? acc[i][t][3] + bvv[3] : 0.f);
             *reinterpret_cast<uint2*>(osb + (size_t)row * OSTR + n * 2) = o;
         }
     }

@@ -4,9 +4,9 @@
 // idle, this one is faster (B = 32: 0.43 vs 0.47 ms per forward).  At chip-filling batches it loses: 448-B half rows
 // (1.19x sector over-fetch), map rows through registers (3.5 TB/s against 4.3).  Same operands, same results.
 #include "common.hpp"
+#include "bf16.hpp"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #ifdef MG_IMG_TRACE
 // profiling aid (off by default): per-phase cycle sums of wave 0 / wave 7 of two workgroups
@@ -30,13 +30,6 @@ constexpr int OCH = OUT_LD / 8;         // 40 chunks per output row
 constexpr int OSTR = OUT_LD * 2 + 16;   // epilogue LDS row stride in bytes (656: rows land on distinct banks)
 constexpr int NTHR = 512;
 constexpr int P_SPLIT = 104;            // half 0: regions [0,104) (tiles 0..6), half 1: [104,196) (tiles 0..5)
-
-// two fp32 -> packed bf16x2 (round to nearest even) in ONE instruction; there is no builtin for it on gfx950
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // ---- roles ------------------------------------------------------------------------------------------------------------
 // Waves 4-7 are PRODUCERS: they own the HBM stream.  Each keeps THREE k-slices of its share of the map in flight in
@@ -68,8 +61,7 @@ __device__ __forceinline__ void imgbank_producer(uint4* __restrict__ Fs, float* 
     // branch the compiler no longer knows how many are outstanding and every wait becomes vmcnt(0)
     const int pqc = pq < npq ? pq : npq - 1;
     const int loff = (int)((16 * hw * gm.P + gm.p0 + 4 * pqc) * sizeof(float));
-    const __amdgpu_buffer_rsrc_t frsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(feat + (size_t)gm.b * gm.K * gm.P), 0, gm.K * gm.P * (int)sizeof(float), 0x00027000);
+    const __amdgpu_buffer_rsrc_t frsrc = mg_buffer(feat + (size_t)gm.b * gm.K * gm.P, gm.K * gm.P * (int)sizeof(float));
     const int urow0 = 32 * pw;                                           // first feature row of this wave inside a slice
     const int P = gm.P, nchunk = gm.nchunk;
 
@@ -102,10 +94,10 @@ __device__ __forceinline__ void imgbank_producer(uint4* __restrict__ Fs, float* 
                 for (int j = 0; j < 4; ++j) {
                     // lanes past the half's last region quad hold a copy of the last quad: their LDS rows are never stored
                     uint4 pk;
-                    pk.x = pack2(s[8 * g + 0][j], s[8 * g + 1][j]);
-                    pk.y = pack2(s[8 * g + 2][j], s[8 * g + 3][j]);
-                    pk.z = pack2(s[8 * g + 4][j], s[8 * g + 5][j]);
-                    pk.w = pack2(s[8 * g + 6][j], s[8 * g + 7][j]);
+                    pk.x = mg_bf16x2(s[8 * g + 0][j], s[8 * g + 1][j]);
+                    pk.y = mg_bf16x2(s[8 * g + 2][j], s[8 * g + 3][j]);
+                    pk.z = mg_bf16x2(s[8 * g + 4][j], s[8 * g + 5][j]);
+                    pk.w = mg_bf16x2(s[8 * g + 6][j], s[8 * g + 7][j]);
                     Fs[(buf * ROWS + 4 * pq + j) * FSTR + ((kc0 + g) ^ (pq & 7))] = pk;
                 }
         }
@@ -300,8 +292,8 @@ __device__ __forceinline__ void imgbank_consumer(unsigned char* smem, const ImgG
         for (int i = 0; i < MTH; ++i) {
             const int row = i * 16 + (lane & 15);
             uint2 o;
-            o.x = pack2(n + 0 < N ? acc[i][j][0] + bv[0] : 0.f, n + 1 < N ? acc[i][j][1] + bv[1] : 0.f);
-            o.y = pack2(n + 2 < N ? acc[i][j][2] + bv[2] : 0.f, n + 3 < N ? acc[i][j][3] + bv[3] : 0.f);
+            o.x = mg_bf16x2(n + 0 < N ? acc[i][j][0] + bv[0] : 0.f, n + 1 < N ? acc[i][j][1] + bv[1] : 0.f);
+            o.y = mg_bf16x2(n + 2 < N ? acc[i][j][2] + bv[2] : 0.f, n + 3 < N ? acc[i][j][3] + bv[3] : 0.f);
             *reinterpret_cast<uint2*>(osb + (size_t)row * OSTR + n * 2) = o;
         }
     }

@@ -18,9 +18,9 @@
 // Outputs (round 5): the fp32 bank and / or its split-bf16 images hi = bf16(x), lo = bf16(x - hi) as [B, P, 320] bf16 each (zero
 // padded) -- the operand of the split-bf16 attention core (sq_mha_split_bf16.hip), written here instead of by a conversion pass.
 #include "common.hpp"
+#include "bf16.hpp"
 #include "sq_mha_util.hpp"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #ifdef MG_IS_TRACE
 // profiling aid (off by default; tools/dev/is_trace.py): s_memtime sums of a slice's phases, waves 0 (converts first) and 4
@@ -41,12 +41,6 @@ constexpr int IS_NT = 19;                // column tiles (N <= 304)
 constexpr int IS_TPW = 3;                // column tiles per wave (w, w + 8, w + 16)
 constexpr int IS_THR = 512;
 constexpr int IS_PSPLIT = 112;           // half 0: regions [0, 112), half 1: [112, P)
-
-__device__ __forceinline__ unsigned is_pack2(float a, float b) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 constexpr int IS_WD = 3;                 // W-fragment ring: two k-steps in flight + the one being multiplied (four: 21 spilled registers)
 constexpr int IS_LD = 320;               // row length of the split-bf16 bank images
@@ -149,11 +143,11 @@ __global__ __launch_bounds__(IS_THR) void imgbank_split_kernel(const float* __re
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float x = sl[i][j];
-                h[i] = __builtin_bit_cast(float, (is_pack2(x, 0.f) << 16));              // bf16(x) as fp32
+                h[i] = mg_bf16_f32(mg_bf16x2(x, 0.f));                                   // bf16(x) as fp32
                 l[i] = x - h[i];
             }
-            ch[j][0] = is_pack2(h[0], h[1]); ch[j][1] = is_pack2(h[2], h[3]);
-            cl[j][0] = is_pack2(l[0], l[1]); cl[j][1] = is_pack2(l[2], l[3]);
+            ch[j][0] = mg_bf16x2(h[0], h[1]); ch[j][1] = mg_bf16x2(h[2], h[3]);
+            cl[j][0] = mg_bf16x2(l[0], l[1]); cl[j][1] = mg_bf16x2(l[2], l[3]);
         }
         // v_permlane32_swap a, b: a = [a.lo, b.lo], b = [a.hi, b.hi].  With a = region row j, b = region row j + 2: the lower half
         // ends with (its own k 0-3, the upper half's k 4-7) of row j, the upper half with (the lower half's k 0-3, its own k 4-7) of
@@ -365,8 +359,8 @@ __global__ __launch_bounds__(IS_THR) void imgbank_split_kernel(const float* __re
                     const int p = i * 16 + fg * 4 + r;
                     const float v = acc[i][t][r] + bv;
                     const float vn = MG_DPP(v, 0xF5);
-                    const unsigned h2 = is_pack2(v, vn);
-                    const unsigned l2 = is_pack2(v - __builtin_bit_cast(float, h2 << 16), vn - __builtin_bit_cast(float, h2 & 0xFFFF0000u));
+                    unsigned h2, l2;
+                    mg_split2(v, vn, h2, l2);
                     if (on && !(fr & 1) && p < rows) {
                         oh[((size_t)p * IS_LD + n) >> 1] = h2;
                         ol[((size_t)p * IS_LD + n) >> 1] = l2;

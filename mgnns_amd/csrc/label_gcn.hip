@@ -47,7 +47,6 @@ namespace {
 
 constexpr int LG_THR = 512;
 constexpr int LG_MAXC = 512;                 // label classes (ELL row list of a wave lives in LDS)
-typedef int lg_i32x4 __attribute__((ext_vector_type(4)));
 
 struct LgArgs {
     const float* A; int C;
@@ -66,9 +65,6 @@ struct LgArgs {
     unsigned* snap;                          // [C*K0]: the inp the outputs standing in G / Gp / Q were computed from
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t lg_rsrc(const void* p, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00027000);
-}
 // COH: the buffer was written by other workgroups of THIS launch -> system-scope (cache-bypassing) access
 template <bool COH> __device__ __forceinline__ f32x4 lg_ld4(__amdgpu_buffer_rsrc_t r, int off) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, COH ? 17 : 0));
@@ -82,7 +78,7 @@ __device__ __forceinline__ void lg_st1(__amdgpu_buffer_rsrc_t r, int off, float 
 }
 __device__ __forceinline__ void lg_st1i(__amdgpu_buffer_rsrc_t r, int off, int v) { __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, 17); }
 __device__ __forceinline__ void lg_st4(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lg_i32x4, v), r, off, 0, 17);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, off, 0, 17);
 }
 
 // counters (ints, three 64-byte lines so that ticket draws, arrival polls and the exit count do not share one):
@@ -180,11 +176,7 @@ __device__ __forceinline__ void lg_gemm_item(unsigned char* smem, __amdgpu_buffe
             }
             unsigned short h[8], l[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float x = j < 4 ? u[j] : v[j - 4];
-                h[j] = f2bf_t(x);
-                l[j] = f2bf_t(x - bf2f_t(h[j]));
-            }
+            for (int j = 0; j < 8; ++j) mg_split(j < 4 ? u[j] : v[j - 4], h[j], l[j]);
             Ah[r * sc + c8] = make_uint4(h[0] | (unsigned)h[1] << 16, h[2] | (unsigned)h[3] << 16, h[4] | (unsigned)h[5] << 16, h[6] | (unsigned)h[7] << 16);
             Al[r * sc + c8] = make_uint4(l[0] | (unsigned)l[1] << 16, l[2] | (unsigned)l[3] << 16, l[4] | (unsigned)l[5] << 16, l[6] | (unsigned)l[7] << 16);
         }
@@ -242,10 +234,10 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
     float* s_val = reinterpret_cast<float*>(smem + tile_bytes + 8 * LG_MAXC * sizeof(int)) + wave * LG_MAXC;
 
     // buffer resources are built where a phase uses them: eight of them live across the item loop spilled ~90 SGPRs
-#define LG_RSRC_D const __amdgpu_buffer_rsrc_t r_d = lg_rsrc(a.d, (size_t)C * 4)
+#define LG_RSRC_D const __amdgpu_buffer_rsrc_t r_d = mg_buffer(a.d, (size_t)C * 4)
 #define LG_RSRC_ELL                                                                                          \
-    const __amdgpu_buffer_rsrc_t r_nnz = lg_rsrc(a.nnz, (size_t)C * 4), r_ec = lg_rsrc(a.ell_col, (size_t)C * C * 4), \
-                                 r_ev = lg_rsrc(a.ell_val, (size_t)C * C * 4)
+    const __amdgpu_buffer_rsrc_t r_nnz = mg_buffer(a.nnz, (size_t)C * 4), r_ec = mg_buffer(a.ell_col, (size_t)C * C * 4), \
+                                 r_ev = mg_buffer(a.ell_val, (size_t)C * C * 4)
 
     // ---- the item queue: phase order, the long items of a phase first ------------------------------------------------------
     //   P0  [0, nG1)           S1 = inp @ W1, 16-row x 256-column MFMA items
@@ -288,7 +280,7 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
         if (it < n0) {
             // ---- P0 ------------------------------------------------------------------------------------------------------------
             if (it < nG1) {
-                const __amdgpu_buffer_rsrc_t r_inp = lg_rsrc(a.inp, (size_t)C * K0 * 4), r_s1 = lg_rsrc(a.S1, (size_t)C * N1 * 4);
+                const __amdgpu_buffer_rsrc_t r_inp = mg_buffer(a.inp, (size_t)C * K0 * 4), r_s1 = mg_buffer(a.S1, (size_t)C * N1 * 4);
                 lg_gemm_item<SPLIT, false>(smem, r_inp, C, K0, it / (N1 / 256), it % (N1 / 256), a.w1a, a.w1b, N1, r_s1, tid, wave, lane);
             } else if (it < nG1 + nD) {
                 LG_RSRC_D;
@@ -319,7 +311,7 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
             if (i < C) {
                 LG_RSRC_D;
                 LG_RSRC_ELL;
-                const __amdgpu_buffer_rsrc_t r_s1 = lg_rsrc(a.S1, (size_t)C * N1 * 4), r_x1 = lg_rsrc(a.X1, (size_t)C * N1 * 4);
+                const __amdgpu_buffer_rsrc_t r_s1 = mg_buffer(a.S1, (size_t)C * N1 * 4), r_x1 = mg_buffer(a.X1, (size_t)C * N1 * 4);
                 const float di = lg_ld1(r_d, i * 4);
                 int cnt = 0;
                 for (int j0 = 0; j0 < C; j0 += 64) {
@@ -372,7 +364,7 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
         if (it < n2) {
             // ---- P2: S2 = X1 @ W2 ----------------------------------------------------------------------------------------------
             {
-                const __amdgpu_buffer_rsrc_t r_x1 = lg_rsrc(a.X1, (size_t)C * N1 * 4), r_s2 = lg_rsrc(a.S2, (size_t)C * N2 * 4);
+                const __amdgpu_buffer_rsrc_t r_x1 = mg_buffer(a.X1, (size_t)C * N1 * 4), r_s2 = mg_buffer(a.S2, (size_t)C * N2 * 4);
                 lg_gemm_item<SPLIT, true>(smem, r_x1, C, N1, it / NC2, it % NC2, a.w2a, a.w2b, N2, r_s2, tid, wave, lane);
             }
             ++pending;
@@ -381,7 +373,7 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
         it -= n2;
         // ---- P3: G = adj @ S2 (+ its split-bf16 fragment-major image; rows C..16*MT of the image are zero) ---------------------------
         LG_RSRC_ELL;
-        const __amdgpu_buffer_rsrc_t r_s2 = lg_rsrc(a.S2, (size_t)C * N2 * 4);
+        const __amdgpu_buffer_rsrc_t r_s2 = mg_buffer(a.S2, (size_t)C * N2 * 4);
         for (int pc = it * P3 + wave; pc < min(MT * 16 * NC2, (it + 1) * P3); pc += 8) {
             const int i = pc / NC2, c0 = (pc - i * NC2) * 256;
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -412,10 +404,7 @@ __global__ __launch_bounds__(LG_THR) void label_gcn_kernel(LgArgs a) {
                 const size_t e = ((((size_t)(i >> 4) * KS2 + (k >> 5)) * 64 + (i & 15) + 16 * ((k & 31) >> 3)) * 8) + (k & 7);
                 unsigned short h[4], l[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    h[q] = f2bf_t(acc[q]);
-                    l[q] = f2bf_t(acc[q] - bf2f_t(h[q]));
-                }
+                for (int q = 0; q < 4; ++q) mg_split(acc[q], h[q], l[q]);
                 *reinterpret_cast<uint2*>(a.gp_hi + e) = make_uint2(h[0] | (unsigned)h[1] << 16, h[2] | (unsigned)h[3] << 16);
                 *reinterpret_cast<uint2*>(a.gp_lo + e) = make_uint2(l[0] | (unsigned)l[1] << 16, l[2] | (unsigned)l[3] << 16);
             }

@@ -299,9 +299,8 @@ struct LabelW {             // packed hi / lo buffers (lo unused with TERMS == 1
     const float *bk, *bv, *bc, *bxl, *bq;
 };
 
-typedef int lt_i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pk2(float a, float b) { return f2bf_t(a) | (unsigned)f2bf_t(b) << 16; }
+// (two single conversions and a merge, not mg_bf16x2: the form the kernel was measured with)
+__device__ __forceinline__ unsigned pk2(float a, float b) { return mg_bf16(a) | (unsigned)mg_bf16(b) << 16; }
 
 // TERMS = 1: plain bf16 operands (+1e-2 on the logits of the B=256 batch: the label-attention feature is the QUERY of two
 // fusion stacks, every bf16 stage of this chain costs ~1e-2 there).  TERMS = 3 (default): split-bf16 operands, three MFMAs
@@ -351,7 +350,7 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
     unsigned short* fh16 = reinterpret_cast<unsigned short*>(s_fh);
     unsigned short* fl16 = reinterpret_cast<unsigned short*>(s_fl);
     auto put = [&](unsigned short* h, unsigned short* l, int idx, float v) {
-        if (LO) split_store(h, l, idx, v); else h[idx] = f2bf_t(v);
+        if (LO) mg_split_store(h, l, idx, v); else h[idx] = mg_bf16(v);
     };
 
     // split-bf16 streams twice the bytes per k-step: six k-steps in flight instead of the tail kernel's three (this kernel has
@@ -429,7 +428,7 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
             }
             s_ph[r * sp + c8] = make_uint4(pk2(a.x, a.y), pk2(a.z, a.w), pk2(b.x, b.y), pk2(b.z, b.w));
             if (LO) {
-                auto lo = [](float x) { return x - bf2f_t(f2bf_t(x)); };
+                auto lo = [](float x) { return x - mg_bf16_f32(mg_bf16(x)); };
                 s_pl[r * sp + c8] = make_uint4(pk2(lo(a.x), lo(a.y)), pk2(lo(a.z), lo(a.w)), pk2(lo(b.x), lo(b.y)), pk2(lo(b.z), lo(b.w)));
             }
         }
@@ -442,13 +441,12 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
     ring_prime(ring, KSx, w.wk_h, w.wk_l, NTh, wave, lane, 0);           // w_k flies through the conversion / exchange of x
     if (CL > 1) {
         // partial [tile][rank][wave][t][lane] x 16 B: a lane writes and reads exactly the accumulator slots it owns
-        const __amdgpu_buffer_rsrc_t xp = __builtin_amdgcn_make_buffer_rsrc(xpart + (size_t)tile * CL * (8 * 3 * 64 * 4), 0,
-                                                                            CL * 8 * 3 * 64 * 16, 0x00027000);
+        const __amdgpu_buffer_rsrc_t xp = mg_buffer(xpart + (size_t)tile * CL * (8 * 3 * 64 * 4), CL * 8 * 3 * 64 * 16);
         const int slot = (wave * 3 * 64 + lane) * 16;
 #pragma unroll
         for (int t = 0; t < 3; ++t)
             if (wave + 8 * t < NTc)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lt_i32x4, acc[t]), xp, slot + t * 64 * 16, crank * (8 * 3 * 64 * 16), 17);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, acc[t]), xp, slot + t * 64 * 16, crank * (8 * 3 * 64 * 16), 17);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's write-through stores are acknowledged
         __syncthreads();
         if (tid == 0) {

@@ -16,6 +16,7 @@
 //      zero-filled by the same workgroup (pad_packed_sequence(total_length=T)).
 // Gate order i, f, g, o (PyTorch).  All arithmetic fp32; the k-loop is a sequential fmaf chain.
 #include "common.hpp"
+#include "bf16.hpp"
 
 int mg_launch_linear(const float* X, int M, int K, const float* W, const float* bias, int N, float* Y, int ldy,
                      const int32_t* gather_idx, const int32_t* m_dev, hipStream_t stream);
@@ -134,11 +135,6 @@ __global__ __launch_bounds__(128) void lstm_fill_kernel(const int64_t* __restric
     }
 }
 
-__device__ __forceinline__ unsigned short f2bf_rne(float x) {
-    unsigned int u = __float_as_uint(x);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // tanh(x) = 2*sigmoid(2x) - 1: one exp instead of libm's tanhf polynomial/branch mix (abs err < 2e-7)
 __device__ __forceinline__ float tanhf_(float x) { return 2.0f / (1.0f + expf(-2.0f * x)) - 1.0f; }
@@ -162,7 +158,7 @@ __device__ __forceinline__ void flush_rows(const float* s_out, int och, int s0, 
         const int t = dir ? len - 1 - s : s;
         const float hh = s_out[(s % och) * HPAD + j];
         out[((size_t)b * T + t) * (2 * HID) + dir * HID + j] = hh;
-        if (out_bf16) out_bf16[((size_t)b * T + t) * ld_bf16 + dir * HID + j] = f2bf_rne(hh);
+        if (out_bf16) out_bf16[((size_t)b * T + t) * ld_bf16 + dir * HID + j] = mg_bf16_rne_finite(hh);
     }
     mg_lds_barrier();                                                    // the rows may be overwritten by the next steps
 }
@@ -303,11 +299,6 @@ constexpr int MTHR = MW * 64;
 constexpr int MKS = 38;               // k-steps of 4 (150 -> 152)
 constexpr int MH = 192;               // h row in LDS (bf16), zero padded to 3 x 16 chunks of 4
 
-__device__ __forceinline__ unsigned int pack2_bf16(float a, float b) {
-    unsigned int r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 #define MG_QUAD_BCAST(v, q) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (q) * 0x55, 0xF, 0xF, true))
 
 // bf16-mode input projection, A side: Xb[r, 0:Kp] = bf16(X[gidx[r], 0:K]) (zero padded to Kp) for the r < *m_dev packed
@@ -331,7 +322,7 @@ __global__ __launch_bounds__(256) void lstm_gather_cast_kernel(const float* __re
         v[4 * h] = q[0]; v[4 * h + 1] = q[1]; v[4 * h + 2] = q[2]; v[4 * h + 3] = q[3];
     }
     *reinterpret_cast<uint4*>(Xb + (size_t)r * XKP + c) =
-        uint4{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])};
+        uint4{mg_bf16x2(v[0], v[1]), mg_bf16x2(v[2], v[3]), mg_bf16x2(v[4], v[5]), mg_bf16x2(v[6], v[7])};
 }
 
 // bf16 mode, B <= 1024: pack + fill + gather as ONE launch.  lstm_pack_kernel is a single workgroup that every other
@@ -413,8 +404,8 @@ __global__ __launch_bounds__(PREP_THR) void lstm_prep_kernel(const int64_t* __re
         for (int u = 0; u < 4; ++u)
             if (i0 + u * PREP_THR < items)
                 *reinterpret_cast<uint4*>(Xb + (size_t)(off + rr[u]) * XKP + cc[u]) =
-                    uint4{pack2_bf16(q[u][0][0], q[u][0][1]), pack2_bf16(q[u][0][2], q[u][0][3]), pack2_bf16(q[u][1][0], q[u][1][1]),
-                          pack2_bf16(q[u][1][2], q[u][1][3])};
+                    uint4{mg_bf16x2(q[u][0][0], q[u][0][1]), mg_bf16x2(q[u][0][2], q[u][0][3]), mg_bf16x2(q[u][1][0], q[u][1][1]),
+                          mg_bf16x2(q[u][1][2], q[u][1][3])};
     }
 }
 
@@ -431,7 +422,7 @@ __global__ __launch_bounds__(MTHR) void lstm_pack_whh_kernel(const float* __rest
     float v[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = (row_on && 4 * ks + e < HID) ? wrow[4 * ks + e] : 0.f;
-    packed[((size_t)(dir * MW + wave) * MKS + ks) * 64 + lane] = uint2{pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3])};
+    packed[((size_t)(dir * MW + wave) * MKS + ks) * 64 + lane] = uint2{mg_bf16x2(v[0], v[1]), mg_bf16x2(v[2], v[3])};
 }
 
 #ifndef MG_LSTM_KM
@@ -617,7 +608,7 @@ __global__ __launch_bounds__(MTHR) void lstm_rec_bf16_kernel(const float* __rest
             c = fgt * c + ig * gg;
             const float hh = og * (2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * c)) - 1.0f);
             if (gate == 0 && row_on) {
-                s_h[cur ^ 1][unit] = (unsigned short)(pack2_bf16(hh, 0.f) & 0xFFFFu);
+                s_h[cur ^ 1][unit] = (unsigned short)(mg_bf16x2(hh, 0.f) & 0xFFFFu);
                 s_out[sm * HPAD + unit] = hh;
             }
             LSTM_T(2)                                              // activations, cell update, h to LDS
@@ -633,7 +624,7 @@ __global__ __launch_bounds__(MTHR) void lstm_rec_bf16_kernel(const float* __rest
                     // bf16 A operand ([packed row, 320], this direction's 150 columns; direction 0 also zeroes the padding)
                     for (int e = tid; e < (s + 1 - s0) * HID; e += MTHR) {
                         const int ss = s0 + e / HID, j = e % HID;
-                        next_x[(size_t)(off + (dir ? len - 1 - ss : ss)) * XKP + dir * HID + j] = f2bf_rne(s_out[(ss % och) * HPAD + j]);
+                        next_x[(size_t)(off + (dir ? len - 1 - ss : ss)) * XKP + dir * HID + j] = mg_bf16_rne_finite(s_out[(ss % och) * HPAD + j]);
                     }
                     if (dir == 0)
                         for (int e = tid; e < (s + 1 - s0) * (XKP - 2 * HID); e += MTHR)

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void pack_w_split_kernel(const float* __restri
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float x = (n < N && k0 + j < K) ? W[(size_t)n * K + k0 + j] : 0.f;
-            split_store(Whi, Wlo, (int)(i * 8 + j), x);
+            mg_split_store(Whi, Wlo, (int)(i * 8 + j), x);
         }
     }
 }
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(NTHR) void mha_proj_c16_kernel(const float* __restr
             if (c8 + 4 <= D) a = *reinterpret_cast<const f32x4*>(xr);
             if (c8 + 8 <= D) b = *reinterpret_cast<const f32x4*>(xr + 4);
         }
-        s_a[i] = make_uint4(f2bf2_t(a[0], a[1]), f2bf2_t(a[2], a[3]), f2bf2_t(b[0], b[1]), f2bf2_t(b[2], b[3]));
+        s_a[i] = make_uint4(mg_bf16x2(a[0], a[1]), mg_bf16x2(a[2], a[3]), mg_bf16x2(b[0], b[1]), mg_bf16x2(b[2], b[3]));
     }
     __syncthreads();
     bf16x8 aq[KSd];

@@ -89,9 +89,9 @@ __device__ __forceinline__ void ln_rows_emit(float* __restrict__ buf, const floa
                 const float y = gamma[i] * (v[i] - mean) * inv + beta[i];
                 row[c] = y;
                 if (emit_bf16) {
-                    const unsigned short h = f2bf_t(y);
+                    const unsigned short h = mg_bf16(y);       // (written out: mg_split_store under the TERMS test schedules differently)
                     hi[r * SCD * 8 + c] = h;
-                    if (TERMS == 3) lo[r * SCD * 8 + c] = f2bf_t(y - bf2f_t(h));
+                    if (TERMS == 3) lo[r * SCD * 8 + c] = mg_bf16(y - mg_bf16_f32(h));
                 }
                 if (gout && r < rows_valid) gout[(size_t)r * D + c] = y;
             }
@@ -196,11 +196,11 @@ __device__ __forceinline__ void tail_bf16_body(unsigned char* smem_b, const floa
             if (i < ROWS * so) {
                 uint4 hq, lq = make_uint4(0u, 0u, 0u, 0u);
                 const f32x4 x0 = v[it][0], x1 = v[it][1];
-                hq.x = f2bf2_t(x0[0], x0[1]); hq.y = f2bf2_t(x0[2], x0[3]); hq.z = f2bf2_t(x1[0], x1[1]); hq.w = f2bf2_t(x1[2], x1[3]);
-                if (TERMS == 3) {
-                    auto res = [](float x, unsigned int packed, int half) { return x - bf2f_t((unsigned short)(half ? packed >> 16 : packed & 0xFFFFu)); };
-                    lq.x = f2bf2_t(res(x0[0], hq.x, 0), res(x0[1], hq.x, 1)); lq.y = f2bf2_t(res(x0[2], hq.y, 0), res(x0[3], hq.y, 1));
-                    lq.z = f2bf2_t(res(x1[0], hq.z, 0), res(x1[1], hq.z, 1)); lq.w = f2bf2_t(res(x1[2], hq.w, 0), res(x1[3], hq.w, 1));
+                hq.x = mg_bf16x2(x0[0], x0[1]); hq.y = mg_bf16x2(x0[2], x0[3]); hq.z = mg_bf16x2(x1[0], x1[1]); hq.w = mg_bf16x2(x1[2], x1[3]);
+                if (TERMS == 3) {       // (written out: mg_split2 per word gives this kernel another register allocation)
+                    auto res = [](float x, unsigned int packed, int half) { return x - mg_bf16_f32(half ? packed >> 16 : packed & 0xFFFFu); };
+                    lq.x = mg_bf16x2(res(x0[0], hq.x, 0), res(x0[1], hq.x, 1)); lq.y = mg_bf16x2(res(x0[2], hq.y, 0), res(x0[3], hq.y, 1));
+                    lq.z = mg_bf16x2(res(x1[0], hq.z, 0), res(x1[1], hq.z, 1)); lq.w = mg_bf16x2(res(x1[2], hq.w, 0), res(x1[3], hq.w, 1));
                 }
                 s_oh[i] = hq;
                 if (TERMS == 3) s_ol[i] = lq;
@@ -239,14 +239,12 @@ __device__ __forceinline__ void tail_bf16_body(unsigned char* smem_b, const floa
         // Nobody waits: the rank that arrives LAST adds the partials in rank order and runs the rest of the tail for the tile
         // alone, the others are done -- the LayerNorm / FFN chain runs once per tile, and there is no co-residency assumption
         // (the first form had every rank wait for the partials and repeat the chain: same speed, 4x the chain's CU time).
-        typedef int tl_i32x4 __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t xp = __builtin_amdgcn_make_buffer_rsrc(xpart + (size_t)tile * csize * (8 * 3 * 64 * 4), 0,
-                                                                            csize * 8 * 3 * 64 * 16, 0x00027000);
+        const __amdgpu_buffer_rsrc_t xp = mg_buffer(xpart + (size_t)tile * csize * (8 * 3 * 64 * 4), csize * 8 * 3 * 64 * 16);
         const int slot = (wave * 3 * 64 + lane) * 16;
 #pragma unroll
         for (int t = 0; t < 3; ++t)
             if (wave + 8 * t < DT)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tl_i32x4, acc[t]), xp, slot + t * 64 * 16, crank * (8 * 3 * 64 * 16), 17);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, acc[t]), xp, slot + t * 64 * 16, crank * (8 * 3 * 64 * 16), 17);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's write-through stores are acknowledged
         __syncthreads();
         int* s_flag = reinterpret_cast<int*>(s_t);
@@ -302,8 +300,8 @@ __device__ __forceinline__ void tail_bf16_body(unsigned char* smem_b, const floa
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float x = fmaxf(acc[t][r] + bv, 0.f);
-                if (TERMS == 3) split_store(ah16, al16, (crow + r) * SCD * 8 + n, x);
-                else ah16[(crow + r) * SCD * 8 + n] = f2bf_t(x);
+                if (TERMS == 3) mg_split_store(ah16, al16, (crow + r) * SCD * 8 + n, x);
+                else ah16[(crow + r) * SCD * 8 + n] = mg_bf16(x);
             }
         }
     }

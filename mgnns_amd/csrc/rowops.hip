@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void classifier_part_kernel(const float* __res
     __shared__ int s_last;
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(parts, 0, nparts * B * NL * 4, 0x00027000);
+    const __amdgpu_buffer_rsrc_t prs = mg_buffer(parts, nparts * B * NL * 4);
     if (b < B) {
         const float* fb = f + (size_t)b * D;
         float x[NI];

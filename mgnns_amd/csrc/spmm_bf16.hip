@@ -15,17 +15,12 @@
 //     row read (64 lanes x 8 B) + dot products.  Needs the adjacency re-ordered once into per-(wave, column block) entry
 //     streams (mgnns_amd/spmm_plan.py; the adjacency is a static parameter of the model).
 #include "common.hpp"
+#include "bf16.hpp"
 
 namespace {
 
 typedef __bf16 sb_bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int sb_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned sb_pack_bf16(float a, float b) {   // (lo = a, hi = b), round to nearest even
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // Direct (gather) kernel.  A lane group of 16 lanes owns one row at a time: 16 lanes x 16 B = the 256-B segment of one
@@ -123,8 +118,8 @@ __global__ __launch_bounds__(256) void spmm_bf16_slab_kernel(const int32_t* __re
 #pragma unroll
                         for (int j = 0; j < 8; ++j) o[j] = mg_act(acc[u][q][j], act);
                         if (y_bf16) {
-                            const u32x4 ov = {sb_pack_bf16(o[0], o[1]), sb_pack_bf16(o[2], o[3]), sb_pack_bf16(o[4], o[5]),
-                                              sb_pack_bf16(o[6], o[7])};
+                            const u32x4 ov = {mg_bf16x2(o[0], o[1]), mg_bf16x2(o[2], o[3]), mg_bf16x2(o[4], o[5]),
+                                              mg_bf16x2(o[6], o[7])};
                             __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(static_cast<uint16_t*>(Yv) + (size_t)orow[u] * F + f[q]));
                         } else {
                             float* yp = static_cast<float*>(Yv) + (size_t)orow[u] * F + f[q];
@@ -328,8 +323,8 @@ __global__ __launch_bounds__(256) void spmm_bf16_ring_kernel(const int32_t* __re
 #pragma unroll
                         for (int j = 0; j < 8; ++j) o[j] = mg_act(acc[q][j], act);
                         if (y_bf16) {
-                            const u32x4 ov = {sb_pack_bf16(o[0], o[1]), sb_pack_bf16(o[2], o[3]), sb_pack_bf16(o[4], o[5]),
-                                              sb_pack_bf16(o[6], o[7])};
+                            const u32x4 ov = {mg_bf16x2(o[0], o[1]), mg_bf16x2(o[2], o[3]), mg_bf16x2(o[4], o[5]),
+                                              mg_bf16x2(o[6], o[7])};
                             __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(static_cast<uint16_t*>(Yv) + (size_t)ro * F + f[q]));
                         } else {
                             float* yp = static_cast<float*>(Yv) + (size_t)ro * F + f[q];
@@ -554,10 +549,10 @@ __global__ __launch_bounds__(1024) void spmm_bf16_tiled_kernel(const uint32_t* _
             if (y_bf16) {
                 uint16_t* yp = static_cast<uint16_t*>(Yv) + (size_t)row * F + fbase;
                 if constexpr (NA == 4) {
-                    const sb_u32x2 ov = {sb_pack_bf16(o[0], o[1]), sb_pack_bf16(o[2], o[3])};
+                    const sb_u32x2 ov = {mg_bf16x2(o[0], o[1]), mg_bf16x2(o[2], o[3])};
                     __builtin_nontemporal_store(ov, reinterpret_cast<sb_u32x2*>(yp));
                 } else {
-                    __builtin_nontemporal_store(sb_pack_bf16(o[0], o[1]), reinterpret_cast<unsigned*>(yp));
+                    __builtin_nontemporal_store(mg_bf16x2(o[0], o[1]), reinterpret_cast<unsigned*>(yp));
                 }
             } else {
                 float* yp = static_cast<float*>(Yv) + (size_t)row * F + fbase;
@@ -576,9 +571,9 @@ __global__ __launch_bounds__(1024) void spmm_bf16_tiled_kernel(const uint32_t* _
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, long long n) {
     const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
     if (i + 1 < n) {
-        *reinterpret_cast<unsigned*>(dst + i) = sb_pack_bf16(src[i], src[i + 1]);
+        *reinterpret_cast<unsigned*>(dst + i) = mg_bf16x2(src[i], src[i + 1]);
     } else if (i < n) {
-        dst[i] = (uint16_t)(sb_pack_bf16(src[i], 0.f) & 0xffffu);
+        dst[i] = (uint16_t)(mg_bf16x2(src[i], 0.f) & 0xffffu);
     }
 }
 

@@ -24,25 +24,22 @@
 //                           Scores use the row's own sample's query, the softmax is segmented per sample, the weighted sum
 //                           is taken per 8-row block in registers and the blocks of a sample are added through LDS.
 #include "common.hpp"
+#include "bf16.hpp"
+#include "sq_mha_util.hpp"
 #include "sq_mha_plan.hpp"
 
 #ifdef MG_MHA32_TRACE
 // profiling aid (off by default; tools/dev/mha32_trace.py): s_memtime stamps of waves 0 (K units) and 4 (V units) of workgroups
 // 0 and 129 of sq_mha32_core_kernel at every phase boundary
 __device__ unsigned long long g_mha32_trace[4][64];
-#define MG_STAMP(slot)                                                                              \
-    do {                                                                                            \
-        if ((threadIdx.x & 255) == 0 && (blockIdx.x == 0 || blockIdx.x == 129) && blockIdx.y == 0)  \
-            g_mha32_trace[(blockIdx.x ? 2 : 0) + (threadIdx.x >> 8)][(slot)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
+#define MG_STAMP(slot) MG_MHA_STAMP(g_mha32_trace, slot)
 #else
 #define MG_STAMP(slot) do { } while (0)
 #endif
 
 namespace {
 
-typedef __bf16 bfx8 __attribute__((ext_vector_type(8)));
-typedef int i32x4v __attribute__((ext_vector_type(4)));
+using namespace mg_mha;
 
 constexpr int RT = 32;                  // bank rows per tile
 constexpr int MT = 7;                   // row tiles a workgroup can hold (L <= 224)
@@ -57,12 +54,6 @@ constexpr int FRAG = 1024;              // bytes per weight fragment (64 lanes x
 constexpr int QMAX = 2048;              // floats of projected query a per-sample workgroup keeps (H * 128 <= QMAX)
 constexpr int MAXH = QMAX / DK;
 constexpr int TILE_BYTES = RT * LSTR * 16;
-
-__device__ __forceinline__ unsigned short f2bf(float x) {      // round-to-nearest-even
-    unsigned int u = __float_as_uint(x);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
 
 // Wp[h][kv][slice][ks][lane][8] = W_kv[h*128 + slice*32 + (lane&31)][ks*16 + (lane>>5)*8 + j]  (0 beyond D)
 __global__ __launch_bounds__(256) void pack_kv_weights32_kernel(const float* __restrict__ Wk, const float* __restrict__ Wv,
@@ -80,7 +71,7 @@ __global__ __launch_bounds__(256) void pack_kv_weights32_kernel(const float* __r
         const int k0 = ks * 16 + (lane >> 5) * 8;
         unsigned short v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (k0 + j < D) ? f2bf(W[(size_t)row * D + k0 + j]) : (unsigned short)0;
+        for (int j = 0; j < 8; ++j) v[j] = (k0 + j < D) ? mg_bf16_rne_finite(W[(size_t)row * D + k0 + j]) : 0u;
         uint4 o;
         o.x = v[0] | ((unsigned)v[1] << 16);
         o.y = v[2] | ((unsigned)v[3] << 16);
@@ -97,39 +88,6 @@ __global__ __launch_bounds__(256) void pack_kv_weights32_kernel(const float* __r
 __device__ __forceinline__ float halves_sum2(float a, float b) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
     return a + b;
-}
-
-// LDS counters instead of s_barrier (LDS operations of a wave complete in order: lgkmcnt(0) in front of an arrival publishes
-// this wave's LDS writes to whoever sees the count)
-__device__ __forceinline__ int lds_arrive(int* ctr, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    int old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return __builtin_amdgcn_readfirstlane(old);
-}
-__device__ __forceinline__ void lds_wait_ge(int* ctr, int target) {
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < target)
-        __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-}
-
-template <int N> struct IC { static constexpr int v = N; };
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(IC<I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// Weight fragments through a buffer resource: one VGPR (lane * 16) addresses every fragment, the fragment is a wave-uniform
-// byte offset in an SGPR
-struct WStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-__device__ __forceinline__ uint4 wfrag(const WStream& w, int soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(w.rsrc, w.voff, soff, 0));
 }
 
 #ifndef MG_MHA32_RING
@@ -205,7 +163,7 @@ __device__ __forceinline__ void kv_gemm(f32x16 (&acc)[NT], Frags<NT>& f, unsigne
     __builtin_amdgcn_sched_barrier(0);
     static_for<0, KS>([&](auto ksc) {
         constexpr int ks = decltype(ksc)::v;
-        const bfx8 wv = __builtin_bit_cast(bfx8, f.bq[ks % BD]);
+        const bf16x8 wv = __builtin_bit_cast(bf16x8, f.bq[ks % BD]);
         if constexpr (LATE && ks == KS - BD) {
             // >= 2 NT fragment reads were issued behind the draw and at most RA are in flight: it has landed
             wb_next = next_stream(lds_ticket_value<RA>(raw_ticket));
@@ -222,7 +180,7 @@ __device__ __forceinline__ void kv_gemm(f32x16 (&acc)[NT], Frags<NT>& f, unsigne
             __builtin_amdgcn_sched_barrier(0);
             static_for<0, cnt>([&](auto jc) {
                 constexpr int i = i0 + decltype(jc)::v;
-                const bfx8 xv = __builtin_bit_cast(bfx8, ga[(ks * NT + i) % RA]);
+                const bf16x8 xv = __builtin_bit_cast(bf16x8, ga[(ks * NT + i) % RA]);
                 if constexpr (VT) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xv, wv, acc[i], 0, 0, 0);
                 else acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv, xv, acc[i], 0, 0, 0);
             });
@@ -328,7 +286,7 @@ __device__ __forceinline__ void mha_body(unsigned char* smem, int B, int L, int 
     const unsigned a_lo = mg_lds_addr(Xs + (lane & 31) * LSTR + half), a_hi = a_lo + 4 * TILE_BYTES;
     const float inv_temp = 1.0f / temp;
     WStream wsr;
-    wsr.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Wp), 0, 0x7fffffff, 0x00027000);
+    wsr.rsrc = mg_buffer(Wp, 0x7fffffff);
     wsr.voff = lane * 16;
     // this workgroup's head pairs: blockIdx.y, + gridDim.y, ...: local head n = 2 (pair index) + (0 | 1); tickets per slice in the
     // order K(2p) K(2p+1) V(2p) V(2p+1) per pair p -- and K(2p) V(2p) for a last pair with ONE head (odd H): every ticket below
@@ -358,7 +316,7 @@ __device__ __forceinline__ void mha_body(unsigned char* smem, int B, int L, int 
         unit_of(t < nunits ? t : 0, n, v);
         return (((head_of(n) * 2 + (v ? 1 : 0)) * 4 + wq) * KS) * FRAG;
     };
-    const __amdgpu_buffer_rsrc_t attn_rsrc = __builtin_amdgcn_make_buffer_rsrc(attn, 0, attn ? 0x7fffffff : 0, 0x00027000);
+    const __amdgpu_buffer_rsrc_t attn_rsrc = mg_buffer(attn, attn ? 0x7fffffff : 0);
 
     int t = draw();
     Frags<NT> f;
@@ -570,7 +528,7 @@ __device__ __forceinline__ void packed_body(unsigned char* smem, int B, int L, i
     const int wq = wave & 3;
     const unsigned a_lo = mg_lds_addr(Xs + (lane & 31) * LSTR + half), a_hi = a_lo + 4 * TILE_BYTES;
     WStream wsr;
-    wsr.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Wp), 0, 0x7fffffff, 0x00027000);
+    wsr.rsrc = mg_buffer(Wp, 0x7fffffff);
     wsr.voff = lane * 16;
     const int nunits = 2 * hl;
     const float inv_temp = 1.0f / temp;

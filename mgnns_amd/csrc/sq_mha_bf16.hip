@@ -11,21 +11,20 @@
 // carries X.  Per head pair: phase 0 = K tiles -> scores -> softmax, phase 1 = V tiles -> weighted sum.
 // Row tiles behind the last unmasked position are skipped (their probability is exactly 0).
 #include "common.hpp"
-#include "tile_bf16.hpp"         // (defines bf16x8)
+#include "bf16.hpp"
+#include "sq_mha_util.hpp"
 
 #ifdef MG_MHA_TRACE
 // profiling aid (off by default): s_memtime stamps of wave 0 / wave 4 of two workgroups at every phase boundary
 __device__ unsigned long long g_mha_trace[4][64];
-#define MG_STAMP(slot)                                                                              \
-    do {                                                                                            \
-        if ((threadIdx.x & 255) == 0 && (blockIdx.x == 0 || blockIdx.x == 129) && blockIdx.y == 0)  \
-            g_mha_trace[(blockIdx.x ? 2 : 0) + (threadIdx.x >> 8)][(slot)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
+#define MG_STAMP(slot) MG_MHA_STAMP(g_mha_trace, slot)
 #else
 #define MG_STAMP(slot) do { } while (0)
 #endif
 
 namespace {
+
+using namespace mg_mha;
 
 constexpr int MT = 13;                  // row tiles of 16 (L <= 208)
 constexpr int LMAX = MT * 16;
@@ -39,13 +38,6 @@ constexpr int DK = 128;
 #endif
 constexpr int NTHR = MG_MHA_NTHR;
 constexpr int QMAX = 2048;              // floats of the projected query kept in LDS (H * 128 <= QMAX)
-
-__device__ __forceinline__ unsigned short f2bf(float x) {      // round-to-nearest-even; NaN stays a quiet NaN
-    unsigned int u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x40u);     // (the carry of a large payload would reach the sign)
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
 
 // Wp[h][kv][nt][ks][lane][8] = W_kv[h*128 + nt*16 + (lane&15)][ks*32 + (lane>>4)*8 + j]  (0 beyond D)
 __global__ __launch_bounds__(256) void pack_kv_weights_kernel(const float* __restrict__ Wk, const float* __restrict__ Wv,
@@ -63,7 +55,7 @@ __global__ __launch_bounds__(256) void pack_kv_weights_kernel(const float* __res
         const int k0 = ks * 32 + (lane >> 4) * 8;
         unsigned short v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (k0 + j < D) ? f2bf(W[(size_t)row * D + k0 + j]) : (unsigned short)0;
+        for (int j = 0; j < 8; ++j) v[j] = (k0 + j < D) ? mg_bf16_rne(W[(size_t)row * D + k0 + j]) : (unsigned short)0;
         uint4 o;
         o.x = v[0] | ((unsigned)v[1] << 16);
         o.y = v[2] | ((unsigned)v[3] << 16);
@@ -83,7 +75,7 @@ __global__ __launch_bounds__(256) void cast_pad_bf16_kernel(const float* __restr
         const int c0 = (int)(i - r * c8n) * 8;
         unsigned short v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (c0 + j < D) ? f2bf(x[r * D + c0 + j]) : (unsigned short)0;
+        for (int j = 0; j < 8; ++j) v[j] = (c0 + j < D) ? mg_bf16_rne(x[r * D + c0 + j]) : (unsigned short)0;
         uint4 o;
         o.x = v[0] | ((unsigned)v[1] << 16);
         o.y = v[2] | ((unsigned)v[3] << 16);
@@ -91,35 +83,6 @@ __global__ __launch_bounds__(256) void cast_pad_bf16_kernel(const float* __restr
         o.w = v[6] | ((unsigned)v[7] << 16);
         reinterpret_cast<uint4*>(y)[i] = o;
     }
-}
-
-// Sum over the four 16-lane rows of the wave for FOUR values at once (a transposing reduction): on return the rows of the
-// result hold the row sums of [a, c, b, d] -- row 0: a, row 1: c, row 2: b, row 3: d.  v_permlane32_swap exchanges the upper
-// half of its first operand with the lower half of its second, v_permlane16_swap the odd rows of the first with the even rows
-// of the second, so one swap + one add folds TWO values by one level: 3 swaps + 3 adds for four tiles (the one-value form, both
-// operands the same register, cost 2 swaps + 2 adds per tile).  Inline asm: both registers of a swap are read AND written (hipcc
-// 7.2's builtin loses the second result here); the s_nop 1 on either side cover the VALU-write -> swap-read and swap-write ->
-// VALU-read hazards, which the compiler's hazard recogniser does not see through an asm block.
-__device__ __forceinline__ float rows4_sum4(float a, float b, float c, float d) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\ts_nop 1"
-                 : "+v"(a), "+v"(b), "+v"(c), "+v"(d));      // a = [a.lo, b.lo], b = [a.hi, b.hi] (same for c, d)
-    float ab = a + b, cd = c + d;                             // halves: [a: r0+r2, r1+r3 | b: r0+r2, r1+r3]
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(ab), "+v"(cd));
-    return ab + cd;                                           // rows: [a, c, b, d]
-}
-
-// Cross-wave hand-over inside the workgroup goes through LDS counters, not s_barrier (see mha_body).  LDS operations of a wave
-// complete in order: lgkmcnt(0) in front of an arrival publishes this wave's LDS writes to whoever sees the count.
-__device__ __forceinline__ int lds_arrive(int* ctr, int lane) {          // -> the count before this arrival (wave-uniform)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    int old = 0;
-    if (lane == 0) old = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    return __builtin_amdgcn_readfirstlane(old);
-}
-__device__ __forceinline__ void lds_wait_ge(int* ctr, int target) {
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < target)
-        __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
 }
 
 // LDS map behind the staged bank
@@ -150,17 +113,6 @@ struct Frags {
     uint4 bq[BD][2];
 };
 
-// The packed weights are read through a buffer resource: one VGPR (lane * 16) addresses every fragment, the
-// fragment itself is selected by a wave-uniform byte offset in an SGPR.  (64-bit per-lane pointers for the two live
-// weight streams cost the 13-tile class enough registers to spill its head-pair loop state.)
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-struct WStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;                                   // lane * 16
-};
-__device__ __forceinline__ uint4 wfrag(const WStream& w, int soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(w.rsrc, w.voff, soff, 0));
-}
 constexpr int FRAG = 1024;                      // bytes per fragment
 template <int NMT>
 __device__ __forceinline__ void frags_prime_b(Frags<NMT>& f, const WStream& w, int wb) {
@@ -170,17 +122,6 @@ __device__ __forceinline__ void frags_prime_b(Frags<NMT>& f, const WStream& w, i
         f.bq[d][1] = wfrag(w, wb + (KSTEPS + d) * FRAG);
     }
 }
-// compile-time loop: f(IC<0>{}), f(IC<1>{}), ... -- the index is a constant expression inside f (immediate offsets / counts of
-// inline-asm instructions need one)
-template <int N> struct IC { static constexpr int v = N; };
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(IC<I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 // acc[i][j] += X[tile i] * W^T[tile j] over the padded model dim, for a COMPILE-TIME number of live row tiles.
 // The kernel is bound by instruction ISSUE, not by the matrix pipe alone: a SIMD issues ~1.3 other instructions in the shadow
 // of one 16-cycle MFMA (tools/dev/micro/mfma_valu.hip), and the compiler-scheduled form of this loop carried 2.2 per MFMA --
@@ -290,7 +231,7 @@ __device__ __forceinline__ void mha_body(unsigned char* smem, int B, int L, int 
     const unsigned a_lo = mg_lds_addr(Xs + (lane & 15) * LSTR + (lane >> 4)), a_hi = a_lo + 7 * 16 * LSTR * 16;
     const float inv_temp = 1.0f / temp;
     WStream wsr;
-    wsr.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(Wp), 0, 0x7fffffff, 0x00027000);
+    wsr.rsrc = mg_buffer(Wp, 0x7fffffff);
     wsr.voff = lane * 16;
     // this workgroup's head pairs: blockIdx.y, + gridDim.y, ...; ticket t -> pair t / 4, head t & 1 of the pair, V if t & 2
     const int pairs = (H + 1) / 2;
@@ -312,9 +253,9 @@ __device__ __forceinline__ void mha_body(unsigned char* smem, int B, int L, int 
         return (((h * 2 + ((t >> 1) & 1)) * 8 + wq * 2) * KSTEPS) * FRAG;
     };
     // o row of this sample / b_v: buffer resources (uniform base, 32-bit per-lane offsets)
-    const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(o + (size_t)b * H * DK, 0, H * DK * 4, 0x00027000);
-    const __amdgpu_buffer_rsrc_t bv_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bv), 0, bv ? H * DK * 4 : 0, 0x00027000);
-    const __amdgpu_buffer_rsrc_t attn_rsrc = __builtin_amdgcn_make_buffer_rsrc(attn, 0, attn ? 0x7fffffff : 0, 0x00027000);
+    const __amdgpu_buffer_rsrc_t o_rsrc = mg_buffer(o + (size_t)b * H * DK, H * DK * 4);
+    const __amdgpu_buffer_rsrc_t bv_rsrc = mg_buffer(bv, bv ? H * DK * 4 : 0);
+    const __amdgpu_buffer_rsrc_t attn_rsrc = mg_buffer(attn, attn ? 0x7fffffff : 0);
     // the tiles are computed TRANSPOSED (rows = head dims, columns = bank rows): this lane's accumulator element
     // [i][j][r] is head dim d(j,r) = wq*32 + 16j + 4*(lane>>4) + r of bank row 16i + (lane&15)
     const int dbase = wq * 32 + (lane >> 4) * 4;

@@ -120,7 +120,7 @@ __global__ __launch_bounds__(NTHR) void folded_attn_bf16_kernel(const float* __r
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = 8 * c + j < D ? src[j] : 0.f;
         uint4 q;
-        q.x = f2bf2_t(v[0], v[1]); q.y = f2bf2_t(v[2], v[3]); q.z = f2bf2_t(v[4], v[5]); q.w = f2bf2_t(v[6], v[7]);
+        q.x = mg_bf16x2(v[0], v[1]); q.y = mg_bf16x2(v[2], v[3]); q.z = mg_bf16x2(v[4], v[5]); q.w = mg_bf16x2(v[6], v[7]);
         *reinterpret_cast<uint4*>(smem + OFF_U + (size_t)h * ROWB + (size_t)c * 16) = q;
     }
     for (int i = tid; i < 16 * PROW / 8; i += NTHR) reinterpret_cast<uint4*>(s_p)[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(NTHR) void folded_attn_bf16_kernel(const float* __r
             if (attn && l < L) attn[((size_t)h * B + b) * L + l] = p;
             if (l < PROW) {
                 const int ks = l >> 5, r32 = l & 31;
-                s_p[h * PROW + ((ks * 4 + ((r32 >> 2) & 3)) << 3) + ((r32 >> 4) << 2) + (r32 & 3)] = f2bf_t(p);
+                s_p[h * PROW + ((ks * 4 + ((r32 >> 2) & 3)) << 3) + ((r32 >> 4) << 2) + (r32 & 3)] = mg_bf16(p);
             }
         }
     }
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(NTHR) void folded_attn_bf16_kernel(const float* __r
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int h = 4 * g + r;
-                    if (h < H) C[(size_t)b * ldc + h * D + f] = f2bf_t(acc[t][r]);
+                    if (h < H) C[(size_t)b * ldc + h * D + f] = mg_bf16(acc[t][r]);
                 }
             }
         }

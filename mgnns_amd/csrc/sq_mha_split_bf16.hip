@@ -24,11 +24,7 @@
 #ifdef MG_MHAS_TRACE
 // profiling aid (off by default): s_memtime stamps of wave 0 / wave 4 of two workgroups at every phase boundary
 __device__ unsigned long long g_mhas_trace[4][64];
-#define MGS_STAMP(slot)                                                                             \
-    do {                                                                                            \
-        if ((threadIdx.x & 255) == 0 && (blockIdx.x == 0 || blockIdx.x == 129) && blockIdx.y == 0 && (slot) < 64)  \
-            g_mhas_trace[(blockIdx.x ? 2 : 0) + (threadIdx.x >> 8)][(slot)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
+#define MGS_STAMP(slot) MG_MHA_STAMP(g_mhas_trace, slot)
 #else
 #define MGS_STAMP(slot) do { } while (0)
 #endif
@@ -80,11 +76,7 @@ __global__ __launch_bounds__(256) void pack_kv_weights_split_kernel(const float*
         const int k0 = ks * 32 + (lane >> 4) * 8;
         unsigned short vh[8], vl[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float x = (k0 + j < D) ? W[(size_t)row * D + k0 + j] : 0.f;
-            vh[j] = f2bf_t(x);
-            vl[j] = f2bf_t(x - bf2f_t(vh[j]));
-        }
+        for (int j = 0; j < 8; ++j) mg_split((k0 + j < D) ? W[(size_t)row * D + k0 + j] : 0.f, vh[j], vl[j]);
         uint4 oh, ol;
         oh.x = vh[0] | ((unsigned)vh[1] << 16); oh.y = vh[2] | ((unsigned)vh[3] << 16);
         oh.z = vh[4] | ((unsigned)vh[5] << 16); oh.w = vh[6] | ((unsigned)vh[7] << 16);
@@ -114,10 +106,7 @@ __global__ __launch_bounds__(256) void split_pad_bf16_kernel(const float* __rest
         }
         unsigned short vh[8], vl[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            vh[j] = f2bf_t(v[j]);
-            vl[j] = f2bf_t(v[j] - bf2f_t(vh[j]));
-        }
+        for (int j = 0; j < 8; ++j) mg_split(v[j], vh[j], vl[j]);
         uint4 oh, ol;
         oh.x = vh[0] | ((unsigned)vh[1] << 16); oh.y = vh[2] | ((unsigned)vh[3] << 16);
         oh.z = vh[4] | ((unsigned)vh[5] << 16); oh.w = vh[6] | ((unsigned)vh[7] << 16);
@@ -244,7 +233,7 @@ __device__ __forceinline__ void half_body(const Ctx& c, int half, bool two, int&
     const int b = blockIdx.x, B = c.B, L = c.L, H = c.H;
     const unsigned a_h = mg_lds_addr(smem + ((lane & 15) * LSTR + (lane >> 4)) * 16), a_l = a_h + (unsigned)OFF_LO;
     WStream wsr;
-    wsr.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(c.Wp), 0, 0x7fffffff, 0x00027000);
+    wsr.rsrc = mg_buffer(c.Wp, 0x7fffffff);
     wsr.voff = lane * 16;
     const int lo_off = c.lo_off;
     // this workgroup's head pairs: blockIdx.y, + gridDim.y, ...; ticket t -> pair t / 4, head t & 1 of the pair, V if t & 2
@@ -265,9 +254,9 @@ __device__ __forceinline__ void half_body(const Ctx& c, int half, bool two, int&
         const int h = t < nunits ? head_of(t) : 0;
         return (((h * 2 + ((t >> 1) & 1)) * 8 + wq * 2) * KSTEPS) * FRAG;
     };
-    const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(c.o + (size_t)b * H * DK, 0, H * DK * 4, 0x00027000);
-    const __amdgpu_buffer_rsrc_t bv_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(c.bv), 0, c.bv ? H * DK * 4 : 0, 0x00027000);
-    const __amdgpu_buffer_rsrc_t attn_rsrc = __builtin_amdgcn_make_buffer_rsrc(c.attn, 0, c.attn ? 0x7fffffff : 0, 0x00027000);
+    const __amdgpu_buffer_rsrc_t o_rsrc = mg_buffer(c.o + (size_t)b * H * DK, H * DK * 4);
+    const __amdgpu_buffer_rsrc_t bv_rsrc = mg_buffer(c.bv, c.bv ? H * DK * 4 : 0);
+    const __amdgpu_buffer_rsrc_t attn_rsrc = mg_buffer(c.attn, c.attn ? 0x7fffffff : 0);
     // the tiles are computed TRANSPOSED (rows = head dims, columns = bank rows): this lane's accumulator element
     // [i][j][r] is head dim d(j,r) = wq*32 + 16j + 4*(lane>>4) + r of bank row half*LH + 16i + (lane&15)
     const int dbase = wq * 32 + (lane >> 4) * 4;
@@ -585,7 +574,7 @@ __device__ __forceinline__ void group_body(const GCtx& c) {
     const int H = c.H;
     const unsigned a_h = mg_lds_addr(smem + ((lane & 15) * LSTR + (lane >> 4)) * 16), a_l = a_h + (unsigned)OFF_LO;
     WStream wsr;
-    wsr.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(c.Wp), 0, 0x7fffffff, 0x00027000);
+    wsr.rsrc = mg_buffer(c.Wp, 0x7fffffff);
     wsr.voff = lane * 16;
     const int lo_off = c.lo_off;
     // tickets K(h0) K(h1) V(h0) V(h1); a head beyond the pair's count is skipped.  (Opaque to the compiler: with a literal 4 it
@@ -605,7 +594,7 @@ __device__ __forceinline__ void group_body(const GCtx& c) {
         const int h = c.h0 + (t < nunits ? (t & 1) : 0);
         return (((h * 2 + ((t >> 1) & 1)) * 8 + wq * 2) * KSTEPS) * FRAG;
     };
-    const __amdgpu_buffer_rsrc_t bv_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(c.bv), 0, c.bv ? H * DK * 4 : 0, 0x00027000);
+    const __amdgpu_buffer_rsrc_t bv_rsrc = mg_buffer(c.bv, c.bv ? H * DK * 4 : 0);
     const int dbase = wq * 32 + (lane >> 4) * 4;
     // group-local sample of every tile: wave-uniform values (scalar registers)
     int ts[HT];

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(TG_SHORT_THREADS) void textgcn_lean_kernel(const in
         // this thread's 4 features of node row t: byte offset (t * D + 4 f) * 4 into a buffer resource over the table -- 32-bit
         // offsets (64-bit pointers for the nine rows in flight put the ngram-4 instance at 66 registers; 64 is what is left
         // beside an image-bank workgroup)
-        const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(node_hidden), 0, 0x7fffffff, 0x00027000);
+        const __amdgpu_buffer_rsrc_t hrs = mg_buffer(node_hidden, 0x7fffffff);
         const int fo = f * 16, rowb = D * 4;
         for (int j0 = cidx; j0 < n; j0 += C) {
             if (!s_first[j0]) continue;

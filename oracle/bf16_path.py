@@ -2,7 +2,7 @@
 
 restatement.forward is the fp32 network; this module is the same network with the HIP path's bf16 rounding points, in the
 style of trunk_cpu.features_bf16_emulated: every value the kernels round to bf16 is rounded here (round to nearest even, the
-kernels' f2bf / v_cvt_pk_bf16_f32, torch's .to(torch.bfloat16)), everything else is computed in fp64.  What remains between a
+kernels' bf16.hpp conversions, torch's .to(torch.bfloat16)), everything else is computed in fp64.  What remains between a
 kernel and this emulation is fp32 summation order (~1e-6 relative) and the occasional intermediate that lands on the other side
 of a bf16 rounding boundary, so the kernels can be held far tighter than against the fp32 answer.
 
@@ -19,11 +19,11 @@ Rounding points (names = the keys of POINTS; `rounding` selects which are on, de
                                                                    imgbank_bf16.hip:343-363, imgbank_bf16_pairs.hip:303-304
   BiLSTM with the bf16 recurrence, csrc/lstm.hip:
     lstm_x       layer inputs: embedding rows, layer-0 output rows for layer 1   lstm.hip:299-320 (gather cast; lstm_prep_kernel
-                 :336 does the same), lstm.hip:619-622 (next_x = f2bf_rne(h)); the folded layer-0 table is
+                 :336 does the same), lstm.hip:619-622 (next_x = mg_bf16_rne_finite(h)); the folded layer-0 table is
                  bf16(emb) . bf16(W_ih0)^T + b_ih0 (lstm.hip:833-853), the same values
     lstm_wih     W_ih                                              lstm.hip:706, 788, 852 (mgnns_cast_pad_bf16)
     lstm_whh     W_hh                                              lstm.hip:410-420 (lstm_pack_whh_kernel)
-    lstm_h       h as the A operand of W_hh . h at every step      lstm.hip:606 (s_h = pack2_bf16(hh)); gates, cell state and
+    lstm_h       h as the A operand of W_hh . h at every step      lstm.hip:606 (s_h = mg_bf16x2(hh, 0)); gates, cell state and
                  the h row itself stay fp32 (lstm.hip:590-607)
     lstm_out     the bank's bf16 side copy RNE(h), read by the fusion attention  lstm.hip:165 (flush_rows)
   faithful attention, csrc/sq_mha_bf16.hip (16x16x32 form) and sq_mha32_bf16.hip (masked / packed form):
@@ -66,8 +66,8 @@ FOLDED_ONLY = ("fold_u", "fold_p", "fold_c")
 
 
 def bf16_bits(x):
-    """fp32 -> bf16 bit pattern (uint16), round to nearest even: the kernels' f2bf (u + 0x7FFF + ((u >> 16) & 1)) >> 16
-    (lstm.hip:137-141, sq_mha_bf16.hip:43-47), with NaN kept a quiet NaN as v_cvt_pk_bf16_f32 and torch do."""
+    """fp32 -> bf16 bit pattern (uint16), round to nearest even: the kernels' integer form (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+    (csrc/bf16.hpp: mg_bf16_rne), with NaN kept a quiet NaN as v_cvt_pk_bf16_f32 and torch do."""
     a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
     u = a.view(np.uint32).astype(np.uint64)
     r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
