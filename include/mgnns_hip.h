@@ -52,7 +52,7 @@ int mgnns_take_status(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* mgnns_last_error(void);
 /* ABI version (bumped on any signature change). */
-#define MGNNS_ABI_VERSION 25
+#define MGNNS_ABI_VERSION 26
 int mgnns_abi_version(void);
 /* 16 hex digits: sha256 over the sources this library was built from (every .hip and .hpp file of csrc and every header of
  * include; mgnns_amd/build.py generates the unit).  A measurement records it; the host side refuses to file a profile under
@@ -759,6 +759,40 @@ int mgnns_maxpool3x3s2_nhwc_fwd(const void* x, int B, int H, int W, int C, void*
 int mgnns_conv_bf16_nhwc_fwd(const void* x, int B, int H, int W, int Cin, const void* wt, const float* bias, int Cout,
                              int KH, int KW, int stride, int pad, const void* residual, int relu, int out_nchw_f32,
                              void* y, mgnns_stream_t stream);
+
+/* ---- f4 (trunk half, training; ABI 26): backward of the bottleneck convolutions for frozen-statistics fine-tuning
+ * (csrc/conv_train.hip).  The forward is mgnns_conv_bf16_nhwc_fwd on the folded weights; these give its gradients on the bf16
+ * matrix pipe with fp32 accumulation.  Geometry of all of them: 1x1 or 3x3, stride 1 or 2, pad <= k/2, C_in and C_out powers of
+ * two >= 64; H, W are the extents of the convolution's INPUT, OH = (H + 2 pad - k) / stride + 1.  Operands 16-byte aligned.
+ * Nothing uses float atomics: results are bit-identical from call to call.
+ *  mgnns_conv_transpose_pack_bf16   the data gradient's derived pack: wT[c, (kh, kw, o)] = wt[o, (kh, kw, c)] (bf16, any dims).
+ *  mgnns_conv_dgrad_bf16_nhwc       dx[b,ih,iw,c] = sum over (kh,kw,o) with oh*s - p + kh == ih, ow*s - p + kw == iw of
+ *                                   dy[b,oh,ow,o] * wT[c,(kh,kw,o)]; then dx = mask > 0 ? dx + add : 0, rounded to bf16 once.
+ *                                   dy [B,OH,OW,C_out], dx / mask / add [B,H,W,C_in], all bf16 NHWC; mask, add may be NULL.
+ *                                   Input pixels no output pixel reads (stride 2) get exactly add (or 0).
+ *  mgnns_conv_wgrad_bf16_nhwc       dW[o,(kh,kw,c)] = sum over output pixels m of dy[m,o] * x[pixel(m,kh,kw),c] (padding taps
+ *                                   contribute zero), db[o] = sum_m dy[m,o]; x, dy bf16 NHWC, dW [C_out, k*k*C_in] and db fp32.
+ *                                   The pixels are split into shares across workgroups, written to `workspace`
+ *                                   (mgnns_conv_wgrad_workspace_bytes bytes, may be 0 / NULL for a single share) and added in
+ *                                   share order.  B == 0 zeroes the outputs.
+ *  mgnns_conv_bn_unfold             from dWp / dbp (the gradients of the FOLDED weight and bias), the fp32 w [C_out,C_in,KH,KW] and
+ *                                   the BatchNorm's gamma, running mean / var, eps, with r = 1 / sqrt(var + eps):
+ *                                   dW[o,c,kh,kw] = gamma[o] r[o] dWp[o,(kh,kw,c)], dgamma[o] = r[o] (sum_k w[o,k] dWp[o,k] -
+ *                                   mean[o] dbp[o]), dbeta[o] = dbp[o]; each of dW, dgamma, dbeta may be NULL.
+ *  mgnns_map_grad_relu_nhwc_bf16    the entry of the chain: g[b,p,c] = bf16(map[b,c,p] > 0 ? dmap[b,c,p] : 0) from the fp32
+ *                                   NCHW map the last convolution wrote and its gradient; C % 8 == 0.
+ */
+int mgnns_conv_transpose_pack_bf16(const void* wt, int Cout, int Cin, int KH, int KW, void* wT, mgnns_stream_t stream);
+int mgnns_conv_dgrad_bf16_nhwc(const void* dy, int B, int H, int W, int Cin, const void* wT, int Cout, int KH, int KW,
+                               int stride, int pad, const void* mask, const void* add, void* dx, mgnns_stream_t stream);
+size_t mgnns_conv_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+int mgnns_conv_wgrad_bf16_nhwc(const void* x, const void* dy, int B, int H, int W, int Cin, int Cout, int KH, int KW,
+                               int stride, int pad, float* dW, float* db, void* workspace, size_t workspace_bytes,
+                               mgnns_stream_t stream);
+int mgnns_conv_bn_unfold(const float* dWp, const float* dbp, const float* w, const float* gamma, const float* mean,
+                         const float* var, float eps, int Cout, int Cin, int KH, int KW, float* dW, float* dgamma,
+                         float* dbeta, mgnns_stream_t stream);
+int mgnns_map_grad_relu_nhwc_bf16(const float* map, const float* dmap, int B, int C, int P, void* g, mgnns_stream_t stream);
 
 /* ---- measurement aid: a one-thread kernel that writes the GPU's constant-rate real-time counter (s_memrealtime,
  * 100 MHz) into slots[idx] when the stream reaches it.  Captured into the forward's hipGraph it gives the REAL

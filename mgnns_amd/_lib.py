@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _c = ctypes
 _P = _c.c_void_p
@@ -81,6 +81,11 @@ SIGNATURES = {
     "mgnns_stem_conv7_fwd": [_P, _I, _I, _I, _P, _P, _P, _P],
     "mgnns_maxpool3x3s2_nhwc_fwd": [_P, _I, _I, _I, _I, _P, _P],
     "mgnns_conv_bf16_nhwc_fwd": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P],
+    "mgnns_conv_transpose_pack_bf16": [_P, _I, _I, _I, _I, _P, _P],
+    "mgnns_conv_dgrad_bf16_nhwc": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "mgnns_conv_wgrad_bf16_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_conv_bn_unfold": [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
+    "mgnns_map_grad_relu_nhwc_bf16": [_P, _P, _I, _I, _I, _P, _P],
     "mgnns_label_gcn_supported": [_I, _I, _I, _I, _I],
     "mgnns_label_tail_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
     "mgnns_label_tail_bf16_supported": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
@@ -153,6 +158,7 @@ SIZE_GETTERS = {
     "mgnns_imgbank_dgrad_split_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_label_attn_train_bwd_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_bilstm_train_workspace_bytes": [_I, _I, _I],
+    "mgnns_conv_wgrad_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
 }
 
 _lib = None

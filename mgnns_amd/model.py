@@ -226,6 +226,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self._adj_cache = {}                   # training mode: (CSR, CSR of the transpose) of gen_adj(A) per adjacency version
         self.last_dropout_seed = None          # training mode: the classifier dropout's seed of the last forward
         self.text_encoders_trainable = False   # unfreeze_text_encoders(): training mode trains the text encoders too
+        self.trunks_trainable = False          # unfreeze_trunks(): training mode takes images and fine-tunes the trunks' last stages
+        self.trunk_train_stages = 1
         self._lstm_cache = ops.LstmCache()     # derived LSTM weight forms live and die with this module
         self._streams = None
         self.use_streams = bool(opt.get('use_streams', True))
@@ -563,7 +565,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
                 return_last_state=True):
         """Eval mode: the scheduled forward on four streams (forward_plan).  Training mode (_forward_train): the reference's
         training forward in fp32 -- dropout at every site, logits with an autograd graph -- above frozen, eval-mode text
-        encoders (freeze_text_encoders) or trainable ones (unfreeze_text_encoders), and precomputed feature maps."""
+        encoders (freeze_text_encoders) or trainable ones (unfreeze_text_encoders), and precomputed feature maps -- or, after
+        unfreeze_trunks(), images through trunks whose last stages fine-tune."""
         if self.label_query is None:
             raise RuntimeError("label query missing: pass label_glove=... / opt['label_glove'], call "
                                "set_label_query(), or run from a directory holding %s" % (LABEL_GLOVE_CANDIDATES,))
@@ -624,7 +627,39 @@ class Multi_GCN_Multihead_Att(nn.Module):
                                            self.lstm.dropout if self.lstm.training else 0.0)
         return tf, bank
 
-    def _train_maps(self, x, name):
+    TRUNKS = ('object_features', 'place_features')
+
+    def unfreeze_trunks(self, stages=1):
+        """Opt in to fine-tuning the CNN trunks with frozen BatchNorm statistics (call after model.train()): both trunks go to
+        .eval() -- their running statistics are used and never change -- the parameters of the last `stages` bottleneck stages
+        (1..4) of each trunk that is present require a gradient and the rest do not, and training mode takes [B,3,H,W] images for
+        either image input (ResNetFeatures.forward_train).  This departs from the reference, whose model.train() gives the trunks
+        batch statistics.  freeze_trunks() undoes it."""
+        if not 1 <= int(stages) <= 4:
+            raise ValueError("stages must be 1..4, got %r" % (stages,))
+        for n in self.TRUNKS:
+            t = getattr(self, n).eval()
+            t.requires_grad_(False)
+            if not isinstance(t, _NoTrunk):
+                for li in range(8 - int(stages), 8):
+                    t[li].requires_grad_(True)
+        self.trunks_trainable, self.trunk_train_stages = True, int(stages)
+        return self
+
+    def freeze_trunks(self):
+        """Undo unfreeze_trunks(): every trunk parameter requires a gradient again (as after construction; training mode never gives
+        them one), the trunks follow the model's training flag, and training mode takes precomputed feature maps only."""
+        for n in self.TRUNKS:
+            getattr(self, n).requires_grad_(True).train(self.training)
+        self.trunks_trainable = False
+        return self
+
+    def _train_maps(self, x, name, trunk=None):
+        if self.trunks_trainable and x.dim() == 4 and x.shape[1] == 3:
+            if isinstance(trunk, _NoTrunk):
+                raise RuntimeError("%s holds [B,3,H,W] images but the model was built without that CNN trunk: pass a trunk to "
+                                   "Multi_GCN_Multihead_Att or feed precomputed [B,2048,h,w] feature maps" % name)
+            return trunk.forward_train(x, self.trunk_train_stages)
         if not (x.dim() == 4 and x.shape[1] == 2048):
             raise NotImplementedError("training mode takes precomputed [B,2048,h,w] feature maps for %s (the CNN trunks do not "
                                       "train); got %s" % (name, tuple(x.shape)))
@@ -659,7 +694,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
                  self.object_linear_5, self.object_x_linear),
                 ('place', place_feature, place_inp, self.place_A, self.liner_img_place, self.place_attention,
                  self.place_linear_5, self.place_x_linear)):
-            maps = self._train_maps(trunk_in, 'object_feature' if tag == 'obj' else 'place_feature')
+            maps = self._train_maps(trunk_in, 'object_feature' if tag == 'obj' else 'place_feature',
+                                    self.object_features if tag == 'obj' else self.place_features)
             setattr(self, 'object_feature' if tag == 'obj' else 'place_feature', maps)      # MODEL:450,482 keep them
             f3 = (maps if maps.requires_grad else maps.detach()).float().contiguous().view(B, maps.shape[1], -1)
             if self.train_bank_precision == 'fp32':

@@ -1495,6 +1495,108 @@ def conv_bf16_nhwc(x, wt, bias, ksize, stride=1, pad=0, residual=None, relu=True
     return y
 
 
+# ---- f4, training: backward of the bottleneck convolutions (csrc/conv_train.hip) -------------------------------------------
+def conv_transpose_pack(wt, ksize):
+    """The data gradient's pack of a folded weight: wt [Cout, k*k*Cin] bf16 -> wT [Cin, k*k*Cout] bf16, wT[c,(kh,kw,o)] = wt[o,(kh,kw,c)]."""
+    _chk(wt, "wt", torch.bfloat16, 2)
+    Cout, K = wt.shape
+    if K % (ksize * ksize):
+        raise ValueError("wt %s is no %dx%d folded weight" % (tuple(wt.shape), ksize, ksize))
+    Cin = K // (ksize * ksize)
+    wT = torch.empty(Cin, ksize * ksize * Cout, device=wt.device, dtype=torch.bfloat16)
+    L = _lib.lib()
+    _launch("mgnns_conv_transpose_pack_bf16", ("mgnns_conv_transpose_pack_bf16",), L.mgnns_conv_transpose_pack_bf16, _p(wt), Cout, Cin,
+            ksize, ksize, _p(wT), _stream())
+    return wT
+
+
+def _conv_out(H, W, ksize, stride, pad):
+    return (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+
+
+def conv_dgrad_bf16_nhwc(dy, wT, in_hw, ksize, stride=1, pad=0, mask=None, add=None):
+    """Data gradient of conv_bf16_nhwc: dy [B,OH,OW,Cout] bf16, wT [Cin, k*k*Cout] (conv_transpose_pack), in_hw = (H, W) of the
+    convolution's input -> dx [B,H,W,Cin] bf16 = (mask > 0 ? sum + add : 0); mask / add [B,H,W,Cin] bf16 or None."""
+    _chk(dy, "dy", torch.bfloat16, 4)
+    _chk(wT, "wT", torch.bfloat16, 2)
+    B, OH, OW, Cout = dy.shape
+    H, W = in_hw
+    Cin = wT.shape[0]
+    if wT.shape[1] != ksize * ksize * Cout or (OH, OW) != _conv_out(H, W, ksize, stride, pad):
+        raise ValueError("dy %s / wT %s do not match a %dx%d stride-%d pad-%d convolution of a %dx%d input"
+                         % (tuple(dy.shape), tuple(wT.shape), ksize, ksize, stride, pad, H, W))
+    for t, n in ((mask, "mask"), (add, "add")):
+        if t is not None:
+            _chk(t, n, torch.bfloat16, 4)
+            if tuple(t.shape) != (B, H, W, Cin):
+                raise ValueError("%s %s != input %s" % (n, tuple(t.shape), (B, H, W, Cin)))
+    dx = torch.empty(B, H, W, Cin, device=dy.device, dtype=torch.bfloat16)
+    L = _lib.lib()
+    _launch("mgnns_conv_dgrad_bf16_nhwc", ("mgnns_conv_dgrad_bf16_nhwc", ksize, Cin, Cout, stride, OH), L.mgnns_conv_dgrad_bf16_nhwc,
+            _p(dy), B, H, W, Cin, _p(wT), Cout, ksize, ksize, stride, pad, _p(mask), _p(add), _p(dx), _stream())
+    return dx
+
+
+def conv_wgrad_bf16_nhwc(x, dy, ksize, stride=1, pad=0):
+    """Weight gradient of conv_bf16_nhwc with respect to the FOLDED weight and bias: x [B,H,W,Cin], dy [B,OH,OW,Cout] bf16 ->
+    (dW' [Cout, k*k*Cin] fp32 with k = (kh, kw, c), db' [Cout] fp32); pixels reduced in a fixed order."""
+    _chk(x, "x", torch.bfloat16, 4)
+    _chk(dy, "dy", torch.bfloat16, 4)
+    B, H, W, Cin = x.shape
+    Cout = dy.shape[3]
+    if tuple(dy.shape[:3]) != (B,) + _conv_out(H, W, ksize, stride, pad):
+        raise ValueError("dy %s does not match a %dx%d stride-%d pad-%d convolution of x %s"
+                         % (tuple(dy.shape), ksize, ksize, stride, pad, tuple(x.shape)))
+    dW = torch.empty(Cout, ksize * ksize * Cin, device=x.device, dtype=torch.float32)
+    db = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    L = _lib.lib()
+    nbytes = L.mgnns_conv_wgrad_workspace_bytes(B, H, W, Cin, Cout, ksize, ksize, stride, pad)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    _launch("mgnns_conv_wgrad_bf16_nhwc", ("mgnns_conv_wgrad_bf16_nhwc", ksize, Cin, Cout, stride, dy.shape[1]),
+            L.mgnns_conv_wgrad_bf16_nhwc, _p(x), _p(dy), B, H, W, Cin, Cout, ksize, ksize, stride, pad, _p(dW), _p(db), _p(ws), nbytes,
+            _stream())
+    return dW, db
+
+
+def conv_bn_unfold(dwp, dbp, weight, bn, want=(True, True, True)):
+    """Gradients of the fp32 master parameters from those of the folded pair (conv_wgrad_bf16_nhwc): weight [Cout,Cin,KH,KW],
+    bn = (gamma, running_mean, running_var, eps) -> (dW like weight, dgamma [Cout], dbeta [Cout]); want picks which are
+    computed (the others are None)."""
+    _chk(weight, "weight", ndim=4)
+    Cout, Cin, KH, KW = weight.shape
+    _chk(dwp, "dwp", ndim=2)
+    _chk(dbp, "dbp", ndim=1)
+    g, m, v, eps = bn
+    for t, n in ((g, "bn.weight"), (m, "bn.running_mean"), (v, "bn.running_var"), (dbp, "dbp")):
+        _chk(t, n, ndim=1)
+        if t.shape[0] != Cout:
+            raise ValueError("%s has %d entries for %d output channels" % (n, t.shape[0], Cout))
+    if tuple(dwp.shape) != (Cout, KH * KW * Cin):
+        raise ValueError("dwp %s does not match weight %s" % (tuple(dwp.shape), tuple(weight.shape)))
+    dW = torch.empty_like(weight) if want[0] else None
+    dg = torch.empty(Cout, device=weight.device, dtype=torch.float32) if want[1] else None
+    dbeta = torch.empty(Cout, device=weight.device, dtype=torch.float32) if want[2] else None
+    L = _lib.lib()
+    _launch("mgnns_conv_bn_unfold", ("mgnns_conv_bn_unfold",), L.mgnns_conv_bn_unfold, _p(dwp), _p(dbp), _p(weight), _p(g), _p(m), _p(v),
+            float(eps), Cout, Cin, KH, KW, _p(dW), _p(dg), _p(dbeta), _stream())
+    return dW, dg, dbeta
+
+
+def map_grad_relu_nhwc(fmap, dmap):
+    """The entry of the trunk's backward: fmap (the post-ReLU fp32 NCHW map) and its gradient [B,C,h,w] -> bf16 NHWC
+    g = (fmap > 0 ? dmap : 0)."""
+    _chk(fmap, "map", ndim=4)
+    _chk(dmap, "dmap", ndim=4)
+    if fmap.shape != dmap.shape:
+        raise ValueError("map %s / dmap %s" % (tuple(fmap.shape), tuple(dmap.shape)))
+    B, C, h, w = fmap.shape
+    g = torch.empty(B, h, w, C, device=fmap.device, dtype=torch.bfloat16)
+    L = _lib.lib()
+    _launch("mgnns_map_grad_relu_nhwc_bf16", ("mgnns_map_grad_relu_nhwc_bf16",), L.mgnns_map_grad_relu_nhwc_bf16, _p(fmap), _p(dmap), B, C,
+            h * w, _p(g), _stream())
+    return g
+
+
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------
 _timeline = None          # (slots tensor [uint64 as int64], names list) while tools/graph_timeline.py is recording
 

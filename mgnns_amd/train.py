@@ -9,9 +9,10 @@ generator per training forward (kept as `last_dropout_seed`), so torch.manual_se
 The rest of the model trains through the Functions below the fusion layers' (csrc/model_train.hip): the image memory banks
 (their weight gradient is the backward's hot path), the label GCN (propagated back with the transposed adjacency), the label
 attention with dropout on its probabilities, the channel tails and the classifier with its dropout.  The text encoders train
-through the Functions at the end of this file once unfrozen.  The CNN trunks have no backward here: the model takes precomputed
-feature maps, and maps that require a gradient get one (ImgBankFunction, csrc/map_grad.hip), so a torch trunk in front of the
-model fine-tunes through torch's own backward.
+through the Functions at the end of this file once unfrozen.  Feature maps that require a gradient get one (ImgBankFunction,
+csrc/map_grad.hip), so a torch trunk in front of the model fine-tunes through torch's own backward; the trunks of
+mgnns_amd.trunk fine-tune their trailing bottleneck stages with frozen BatchNorm statistics through TrunkStageFunction
+(csrc/conv_train.hip, model.unfreeze_trunks()).
 """
 import torch
 
@@ -380,3 +381,117 @@ def bilstm_train_forward(lstm, embedding, text, text_lens, rate):
             flat += [getattr(lstm, "%s_l%d%s" % (n, layer, suffix)) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
     return BiLSTMTrainFunction.apply(text.long().contiguous(), lens, seed, rate, lstm.hidden_size, lstm.num_layers, embedding.weight,
                                      *flat)
+
+
+# ---- the CNN trunks' trailing stages (csrc/conv_train.hip) ------------------------------------------------------------------
+class TrunkStageFunction(torch.autograd.Function):
+    """map [B, C, h, w] fp32 = a chain of bottlenecks out = relu(conv3(o2) + idn(x)), o2 = relu(conv2(o1)), o1 = relu(conv1(x)), run by
+    the eval forward's kernels on the folded bf16 weights (BatchNorm keeps its running statistics) with x, o1, o2 of every block
+    and the map kept for the backward.  x: NHWC bf16, or NCHW fp32 (converted, as is its gradient).  blocks: the Bottlenecks;
+    packs: trunk.block_packs of each; keep: None or a list that receives the saved activations {"x", "blocks": [(o1, o2, out)]}
+    (what tests compute their reference from); params: (conv.weight, bn.weight, bn.bias) per trunk.block_layers of each block.
+    Backward: dmap is masked by the map and rounded to bf16 NHWC, then per block, last to first: weight
+    gradients of conv3 and the downsample from g_out; g_o2 = dgrad_conv3(g_out) masked by o2; wgrad conv2; g_o1 =
+    dgrad_conv2(g_o2) masked by o1; wgrad conv1; g_x = dgrad_conv1(g_o1) + (g_out or dgrad_down(g_out)), masked by x where x is a
+    block's output.  Gradients travel in bf16, accumulate in fp32 and reach the fp32 parameters through ops.conv_bn_unfold;
+    a parameter gets one iff it requires one, and so does x."""
+
+    @staticmethod
+    def forward(ctx, x, blocks, packs, keep, *params):
+        nchw = x.dtype == torch.float32
+        if nchw:
+            xh = x.detach().permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
+        elif x.dtype == torch.bfloat16:
+            xh = x.detach().contiguous()
+        else:
+            raise TypeError("TrunkStageFunction: x must be NHWC bfloat16 or NCHW float32, got %s" % x.dtype)
+        y, acts, stats = xh, [], []
+        for i, (blk, pk) in enumerate(zip(blocks, packs)):
+            last = i == len(blocks) - 1
+            idn = y
+            if len(pk) == 4:
+                wt, bias, _, k, s, p = pk[3]
+                idn = ops.conv_bf16_nhwc(y, wt, bias, k, s, p, relu=False)
+            wt, bias, _, k, s, p = pk[0]
+            o1 = ops.conv_bf16_nhwc(y, wt, bias, k, s, p)
+            wt, bias, _, k, s, p = pk[1]
+            o2 = ops.conv_bf16_nhwc(o1, wt, bias, k, s, p)
+            wt, bias, _, k, s, p = pk[2]
+            y = ops.conv_bf16_nhwc(o2, wt, bias, k, s, p, residual=idn, out_nchw_f32=last)
+            acts += [o1, o2, y]
+            stats += [t for _, bn in _block_layers(blk) for t in (bn.running_mean, bn.running_var)]
+        if keep is not None:
+            keep.append({"x": xh, "blocks": [tuple(acts[3 * i:3 * i + 3]) for i in range(len(blocks))]})
+        ctx.nchw, ctx.nblk = nchw, len(blocks)
+        ctx.geom = [[(k, s, p) for _, _, _, k, s, p in pk] for pk in packs]
+        ctx.eps = [[bn.eps for _, bn in _block_layers(blk)] for blk in blocks]
+        wTs = [c[2] for pk in packs for c in pk]
+        ctx.save_for_backward(xh, *acts, *wTs, *stats, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dmap):
+        st = ctx.saved_tensors
+        nb = ctx.nblk
+        nconv = [len(g) for g in ctx.geom]
+        total = sum(nconv)
+        xh, acts = st[0], st[1:1 + 3 * nb]
+        wTs, stats, params = st[1 + 3 * nb:1 + 3 * nb + total], st[1 + 3 * nb + total:1 + 3 * nb + 3 * total], st[1 + 3 * nb + 3 * total:]
+        need = ctx.needs_input_grad[4:]
+        grads = [None] * len(params)
+        base = [sum(nconv[:i]) for i in range(nb)]
+
+        def weight_grads(bi, ci, x_in, g):
+            j = base[bi] + ci
+            want = tuple(need[3 * j:3 * j + 3])
+            if not any(want):
+                return
+            k, s, p = ctx.geom[bi][ci]
+            dwp, dbp = ops.conv_wgrad_bf16_nhwc(x_in, g, k, s, p)
+            grads[3 * j:3 * j + 3] = ops.conv_bn_unfold(dwp, dbp, params[3 * j], (params[3 * j + 1], stats[2 * j], stats[2 * j + 1],
+                                                                               ctx.eps[bi][ci]), want=want)
+
+        def data_grad(bi, ci, g, x_in, mask=None, add=None):
+            k, s, p = ctx.geom[bi][ci]
+            return ops.conv_dgrad_bf16_nhwc(g, wTs[base[bi] + ci], tuple(x_in.shape[1:3]), k, s, p, mask=mask, add=add)
+
+        g = ops.map_grad_relu_nhwc(acts[3 * nb - 1], dmap.contiguous().float())
+        for bi in range(nb - 1, -1, -1):
+            x_in = acts[3 * bi - 1] if bi else xh
+            o1, o2 = acts[3 * bi], acts[3 * bi + 1]
+            down = nconv[bi] == 4
+            weight_grads(bi, 2, o2, g)
+            if down:
+                weight_grads(bi, 3, x_in, g)
+            g2 = data_grad(bi, 2, g, o2, mask=o2)
+            weight_grads(bi, 1, o1, g2)
+            g1 = data_grad(bi, 1, g2, o1, mask=o1)
+            weight_grads(bi, 0, x_in, g1)
+            if bi == 0 and not ctx.needs_input_grad[0]:
+                g = None
+                break
+            other = data_grad(bi, 3, g, x_in) if down else g
+            g = data_grad(bi, 0, g1, x_in, mask=x_in if bi else None, add=other)
+        if g is not None and ctx.nchw:
+            g = g.float().permute(0, 3, 1, 2).contiguous()
+        return (g, None, None, None, *grads)
+
+
+def _block_layers(blk):
+    from .trunk import block_layers
+    return block_layers(blk)
+
+
+def trunk_stage_forward(stages, x, keep=None):
+    """The feature map of `stages` -- an nn.Sequential of trunk.Bottleneck, or a list of such stages run one after the other -- over
+    x (NHWC bf16 or NCHW fp32) with autograd through TrunkStageFunction.  BatchNorm uses and keeps its running statistics."""
+    from .trunk import Bottleneck, block_packs
+    if not x.is_cuda:
+        raise RuntimeError("x is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % x.device)
+    if isinstance(stages, torch.nn.Sequential) and all(isinstance(b, Bottleneck) or hasattr(b, "conv3") for b in stages):
+        stages = [stages]
+    blocks = [b for st in stages for b in st]
+    if not blocks:
+        raise ValueError("trunk_stage_forward: no bottleneck blocks")
+    params = [t for b in blocks for conv, bn in _block_layers(b) for t in (conv.weight, bn.weight, bn.bias)]
+    return TrunkStageFunction.apply(x, blocks, [block_packs(b) for b in blocks], keep, *params)

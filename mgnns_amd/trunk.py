@@ -9,6 +9,9 @@ on the 3x3 convolution) with torchvision's parameter names, which is what makes 
 
   ResNet / Bottleneck   parameter containers with torchvision's state_dict surface (conv1, bn1, layer{1..4}.{i}.conv{1..3},
                         bn{1..3}, downsample.{0,1}, fc).  Their own forward() raises: there is no PyTorch compute path.
+  block_packs           the folded weights of one Bottleneck plus the transposed packs its backward reads (derived packs,
+                        rebuilt when a parameter or a running statistic changes): what frozen-statistics fine-tuning runs on
+                        (ResNetFeatures.forward_train, train.TrunkStageFunction).
   ResNetFeatures        the reference's 8-entry nn.Sequential (same child indices -> same `object_features.4.0.conv1.weight`
                         keys), whose forward runs the HIP trunk: BatchNorm folded into bf16 weights once per parameter
                         version, NHWC bf16 activations, every convolution an implicit GEMM on the bf16 MFMA, the last
@@ -21,6 +24,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .derived import derived
 
 
 class _ContainerOnly(nn.Module):
@@ -98,6 +102,34 @@ def _conv_geometry(conv, name):
     return k, s, p
 
 
+def block_layers(blk):
+    """[(conv, bn)] of a bottleneck in the order its packs and gradients are kept: conv1, conv2, conv3(, downsample)."""
+    layers = [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)]
+    if blk.downsample is not None:
+        layers.append((blk.downsample[0], blk.downsample[1]))
+    return layers
+
+
+def block_packs(blk):
+    """[(wt, bias, wT, k, stride, pad)] per block_layers(blk): the eval forward's folded bf16 weight and fp32 bias
+    (ops.conv_fold_bn) and the data gradient's transposed pack (ops.conv_transpose_pack), kept on the block and rebuilt when
+    one of the five tensors they derive from changes."""
+    store = blk.__dict__.setdefault("_train_packs", {})
+    out = []
+    for slot, (conv, bn) in enumerate(block_layers(blk)):
+        k, s, p = _conv_geometry(conv, "bottleneck")
+        if conv.bias is not None:
+            raise NotImplementedError("trunk fine-tuning: convolutions with a bias are not supported (torchvision's have none)")
+
+        def build(conv=conv, bn=bn, k=k):
+            wt, bias = ResNetFeatures._fold(conv, bn)
+            return wt, bias, ops.conv_transpose_pack(wt, k)
+        wt, bias, wT = derived(store, slot, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build,
+                               extra=(bn.eps,))
+        out.append((wt, bias, wT, k, s, p))
+    return out
+
+
 class ResNetFeatures(nn.Sequential):
     """MODEL:274-294 `nn.Sequential(conv1, bn1, relu, maxpool, layer1..layer4)` with a HIP forward.
 
@@ -142,6 +174,43 @@ class ResNetFeatures(nn.Sequential):
         self._plan, self._plan_key = (stem, blocks), key
         return self._plan
 
+    @staticmethod
+    def _run_block(y, convs, down, last=False):
+        idn = y
+        if down is not None:
+            w, b, k, s, p = down
+            idn = ops.conv_bf16_nhwc(y, w, b, k, s, p, relu=False)
+        w, b, k, s, p = convs[0]
+        o = ops.conv_bf16_nhwc(y, w, b, k, s, p)
+        w, b, k, s, p = convs[1]
+        o = ops.conv_bf16_nhwc(o, w, b, k, s, p)
+        w, b, k, s, p = convs[2]
+        return ops.conv_bf16_nhwc(o, w, b, k, s, p, residual=idn, out_nchw_f32=last)
+
+    def forward_train(self, img, stages=1):
+        """Frozen-statistics fine-tuning forward: img [B,3,H,W] -> the [B,2048,h,w] fp32 map under autograd, with gradients
+        for the parameters of the last `stages` bottleneck stages that require one (train.TrunkStageFunction).  The stem, the
+        max-pool and the stages below run as in forward(), without a graph.  BatchNorm keeps its running statistics, so the
+        module must be in eval mode (model.unfreeze_trunks() puts it there)."""
+        from . import train as _train
+        if self.training:
+            raise RuntimeError("ResNetFeatures.forward_train keeps BatchNorm's running statistics (frozen-statistics fine-tuning): "
+                               "call .eval() on the trunk, or model.unfreeze_trunks()")
+        if not 1 <= int(stages) <= 4:
+            raise ValueError("stages must be 1..4, got %r" % (stages,))
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError("trunk input must be [B, 3, H, W], got %s" % (tuple(img.shape),))
+        if not img.is_cuda:
+            raise RuntimeError("img is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % img.device)
+        first = 8 - int(stages)
+        with torch.no_grad():
+            stem, blocks = self._prepare()
+            y = ops.stem_conv7(img.detach().contiguous(), *stem)
+            y = ops.maxpool3x3s2_nhwc(y)
+            for convs, down in blocks[:sum(len(self[li]) for li in range(4, first))]:
+                y = self._run_block(y, convs, down)
+        return _train.trunk_stage_forward([self[li] for li in range(first, 8)], y)
+
     def forward(self, img):
         if self.training:
             raise RuntimeError("ResNetFeatures: eval-mode forward only on the HIP path (BatchNorm uses running statistics); call .eval()")
@@ -151,17 +220,7 @@ class ResNetFeatures(nn.Sequential):
         y = ops.stem_conv7(img.contiguous(), *stem)
         y = ops.maxpool3x3s2_nhwc(y)
         for i, (convs, down) in enumerate(blocks):
-            last = i == len(blocks) - 1
-            idn = y
-            if down is not None:
-                w, b, k, s, p = down
-                idn = ops.conv_bf16_nhwc(y, w, b, k, s, p, relu=False)
-            w, b, k, s, p = convs[0]
-            o = ops.conv_bf16_nhwc(y, w, b, k, s, p)
-            w, b, k, s, p = convs[1]
-            o = ops.conv_bf16_nhwc(o, w, b, k, s, p)
-            w, b, k, s, p = convs[2]
-            y = ops.conv_bf16_nhwc(o, w, b, k, s, p, residual=idn, out_nchw_f32=last)
+            y = self._run_block(y, convs, down, last=i == len(blocks) - 1)
         return y
 
 

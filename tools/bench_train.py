@@ -15,9 +15,13 @@ backward-to-input at the same shape.
 --bank-precision fp32|bf16x3 (with --model-only or --maps): the model's set_train_bank_precision for the step timings; with
 bf16x3, --maps also times the three image-bank products (forward, wgrad, dgrad) in both forms and the whole step in both modes,
 alternately in one process, three rounds each, best and all rounds reported (csrc/bank_grad_split.hip).
+--trunk: frozen-statistics fine-tuning of the trunks' layer4 (csrc/conv_train.hip) at mvsa_multiple_b256 -- the training step with
+precomputed maps against the step with [B,3,448,448] images and unfreeze_trunks() (ResNet-101 / ResNet-50 trunks; --batch N for a
+smaller batch), three alternating rounds, and each new kernel alone per layer4 geometry with its FLOPs and share of the 2.5 PF bf16
+matrix peak (1x1 layers also algorithmic bytes and TB/s).
 --steps-only K: nothing but K whole-model training steps with map gradients in the chosen bank precision -- the run a kernel
 trace is taken of (rocprofv3 --kernel-trace --stats, as tools/prof.sh does for bench.py; table by tools/rocpd_stats.py).
-Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps | --steps-only K] [--bank-precision fp32|bf16x3]"""
+Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps | --trunk [--batch N] | --steps-only K] [--bank-precision fp32|bf16x3]"""
 import json
 import math
 import os
@@ -439,6 +443,78 @@ def split_case(model, args, plain, step, f3, W, dbank, dpooled, arg, n):
     return out
 
 
+BF16_PEAK = 2.5e15        # bf16 MFMA, dense
+
+# layer4 of a bottleneck ResNet at 448 x 448 (its input is 28 x 28 x 1024): (name, H, W, Cin, Cout, k, stride, how many per trunk)
+LAYER4 = [("4.0.conv1", 28, 28, 1024, 512, 1, 1, 1), ("4.0.conv2", 28, 28, 512, 512, 3, 2, 1), ("4.0.downsample", 28, 28, 1024, 2048, 1, 2, 1),
+          ("4.x.conv3", 14, 14, 512, 2048, 1, 1, 3), ("4.1-2.conv1", 14, 14, 2048, 512, 1, 1, 2), ("4.1-2.conv2", 14, 14, 512, 512, 3, 1, 2)]
+
+
+def trunk_case(n):
+    from mgnns_amd import harness, synth
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    B = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else cfg.B
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV, trunks=True).train().freeze_text_encoders()
+    args = list(harness.call_args(inp, DEV))
+    G = torch.randn(B, cfg.NL, device=DEV)
+    g = torch.Generator().manual_seed(1)
+    imgs = list(args)
+    for i in (3, 4):
+        imgs[i] = torch.randn(B, 3, 448, 448, generator=g).to(DEV)
+    res = {"case": "trunk_%s" % cfg.name, "B": B, "device": torch.cuda.get_device_name(0), "iters": n}
+
+    def step(a):
+        model.zero_grad(set_to_none=True)
+        torch.autograd.backward(model(*a), G)
+
+    with torch.no_grad():
+        model.eval()
+        fwd = [timeit(lambda: (model.object_features(imgs[3]), model.place_features(imgs[4])), n, warm=1) for _ in range(2)]
+        model.train().freeze_text_encoders()
+    res["trunks_eval_fwd_us"] = round(min(fwd), 1)
+    ta, tb = [], []
+    for _ in range(3):
+        model.freeze_trunks()
+        ta.append(timeit(lambda: step(args), n, warm=1))
+        model.unfreeze_trunks()
+        tb.append(timeit(lambda: step(imgs), n, warm=1))
+    res["step_precomputed_maps_us"] = round(min(ta), 1)
+    res["step_images_unfrozen_layer4_us"] = round(min(tb), 1)
+    res["step_runs_us"] = {"maps": [round(t, 1) for t in ta], "images": [round(t, 1) for t in tb]}
+
+    kern = {}
+    for name, H, W, Cin, Cout, k, s, count in LAYER4:
+        p = k // 2
+        OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        x = torch.randn(B, H, W, Cin, device=DEV).to(torch.bfloat16)
+        dy = torch.randn(B, OH, OW, Cout, device=DEV).to(torch.bfloat16)
+        wT = torch.randn(Cin, k * k * Cout, device=DEV).to(torch.bfloat16)
+        flop = 2.0 * B * OH * OW * Cout * Cin * k * k
+        td = timeit(lambda: ops.conv_dgrad_bf16_nhwc(dy, wT, (H, W), k, s, p, mask=x), n, warm=1)
+        tw = timeit(lambda: ops.conv_wgrad_bf16_nhwc(x, dy, k, s, p), n, warm=1)
+        row = {"per_trunk": count, "GFLOP": round(flop / 1e9, 1)}
+        for key, t, by in (("dgrad", td, dy.numel() * 2 + 2 * x.numel() * 2 + wT.numel() * 2),
+                           ("wgrad", tw, dy.numel() * 2 + x.numel() * 2 + wT.numel() * 4)):
+            row[key] = {"us": round(t, 1), "TF/s": round(flop / t / 1e6, 1), "pct_bf16_peak": round(100.0 * flop / t / 1e6 / (BF16_PEAK / 1e12), 2)}
+            if k == 1:
+                row[key].update({"alg_MB": round(by / 1e6, 1), "TB/s": round(by / t / 1e6, 2)})
+        kern[name] = row
+        del x, dy, wT
+    res["kernels"] = kern
+    fmap = torch.randn(B, 2048, 14, 14, device=DEV).clamp_min(0)
+    t = timeit(lambda: ops.map_grad_relu_nhwc(fmap, fmap), n, warm=1)
+    by = fmap.numel() * 10
+    res["map_grad_entry"] = {"us": round(t, 1), "alg_MB": round(by / 1e6, 1), "TB/s": round(by / t / 1e6, 2)}
+    w = torch.randn(512, 512, 3, 3, device=DEV)
+    v = torch.rand(512, device=DEV) + 0.5
+    dwp, dbp = torch.randn(512, 4608, device=DEV), torch.randn(512, device=DEV)
+    res["bn_unfold_512x4608_us"] = round(timeit(lambda: ops.conv_bn_unfold(dwp, dbp, w, (v, v, v, 1e-5)), n, warm=1), 1)
+    return res
+
+
 def steps_only(k):
     from mgnns_amd import harness, synth
     cfg = synth.CONFIGS["mvsa_multiple_b256"]
@@ -468,6 +544,9 @@ def main():
         return
     if "--maps" in sys.argv:
         print(json.dumps(maps_case(n)), flush=True)
+        return
+    if "--trunk" in sys.argv:
+        print(json.dumps(trunk_case(n)), flush=True)
         return
     if "--text" in sys.argv:
         print(json.dumps(text_case(n)), flush=True)
