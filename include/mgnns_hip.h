@@ -794,6 +794,33 @@ int mgnns_conv_bn_unfold(const float* dWp, const float* dbp, const float* w, con
                          float* dbeta, mgnns_stream_t stream);
 int mgnns_map_grad_relu_nhwc_bf16(const float* map, const float* dmap, int B, int C, int P, void* g, mgnns_stream_t stream);
 
+/* ---- f4 (trunk half, training with batch statistics): BatchNorm as a training operator (csrc/bn_train.hip).  Added under ABI 26
+ * without a bump: the change is additive -- no existing signature or behaviour moves, and a binding that does not know these
+ * names is unaffected.  z, g, residual, y, gz are [M, C] views of NHWC bf16 activations (M = B*OH*OW >= 2, C % 8 == 0, 16-byte
+ * aligned); mean, rstd, var, gamma, beta, the running buffers, dgamma, dbeta are fp32 [C].  Every reduction over rows goes through
+ * per-slab partials in `workspace` that are added in slab order (slabs are a function of (M, C) alone); no float atomics:
+ * results are bit-identical from call to call.
+ *  mgnns_bn_stats_bf16     mean[c] and rstd[c] = 1 / sqrt(var_biased[c] + eps) of the stored bf16 z, from per-slab (mean, M2) about
+ *                          local centres (never E[z^2] - mean^2); var (may be NULL) receives var_biased.  With running_mean /
+ *                          running_var (both or neither) the same launch updates them in place: running_mean = (1 - momentum)
+ *                          running_mean + momentum mean, running_var = (1 - momentum) running_var + momentum var_biased M / (M - 1).
+ *  mgnns_bn_apply_bf16     y = relu?(a z + b + residual?), a = gamma rstd, b = beta - mean a in fp32, one rounding to bf16 [M, C];
+ *                          with out_nchw_f32 the unrounded fp32 map [M / P, C, P] instead (P = OH*OW pixels per image; else unused).
+ *  mgnns_bn_backward_bf16  with xhat = (z - mean) rstd: dbeta = sum g, dgamma = sum g xhat (each may be NULL: not returned), and
+ *                          gz = bf16(gamma rstd (g - dbeta / M - xhat dgamma / M)), always.
+ */
+size_t mgnns_bn_stats_workspace_bytes(int M, int C);
+int mgnns_bn_stats_bf16(const void* z, int M, int C, float eps, double momentum, float* mean, float* rstd, float* var,
+                        float* running_mean, float* running_var, void* workspace, size_t workspace_bytes,
+                        mgnns_stream_t stream);
+int mgnns_bn_apply_bf16(const void* z, int M, int C, const float* mean, const float* rstd, const float* gamma,
+                        const float* beta, const void* residual, int relu, int out_nchw_f32, int P, void* y,
+                        mgnns_stream_t stream);
+size_t mgnns_bn_backward_workspace_bytes(int M, int C);
+int mgnns_bn_backward_bf16(const void* g, const void* z, int M, int C, const float* mean, const float* rstd,
+                           const float* gamma, void* gz, float* dgamma, float* dbeta, void* workspace,
+                           size_t workspace_bytes, mgnns_stream_t stream);
+
 /* ---- measurement aid: a one-thread kernel that writes the GPU's constant-rate real-time counter (s_memrealtime,
  * 100 MHz) into slots[idx] when the stream reaches it.  Captured into the forward's hipGraph it gives the REAL
  * timeline of the concurrent branches of a replay (rocprofv3 serialises / perturbs them): tools/graph_timeline.py.

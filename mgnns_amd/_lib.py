@@ -86,6 +86,9 @@ SIGNATURES = {
     "mgnns_conv_wgrad_bf16_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
     "mgnns_conv_bn_unfold": [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
     "mgnns_map_grad_relu_nhwc_bf16": [_P, _P, _I, _I, _I, _P, _P],
+    "mgnns_bn_stats_bf16": [_P, _I, _I, _F, _c.c_double, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "mgnns_bn_apply_bf16": [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "mgnns_bn_backward_bf16": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "mgnns_label_gcn_supported": [_I, _I, _I, _I, _I],
     "mgnns_label_tail_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
     "mgnns_label_tail_bf16_supported": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
@@ -159,6 +162,8 @@ SIZE_GETTERS = {
     "mgnns_label_attn_train_bwd_workspace_bytes": [_I, _I, _I, _I],
     "mgnns_bilstm_train_workspace_bytes": [_I, _I, _I],
     "mgnns_conv_wgrad_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
+    "mgnns_bn_stats_workspace_bytes": [_I, _I],
+    "mgnns_bn_backward_workspace_bytes": [_I, _I],
 }
 
 _lib = None

@@ -228,6 +228,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self.text_encoders_trainable = False   # unfreeze_text_encoders(): training mode trains the text encoders too
         self.trunks_trainable = False          # unfreeze_trunks(): training mode takes images and fine-tunes the trunks' last stages
         self.trunk_train_stages = 1
+        self.trunk_train_batchnorm = 'frozen'  # or 'batch': the trainable stages' BatchNorm uses the statistics of the batch
         self._lstm_cache = ops.LstmCache()     # derived LSTM weight forms live and die with this module
         self._streams = None
         self.use_streams = bool(opt.get('use_streams', True))
@@ -629,21 +630,29 @@ class Multi_GCN_Multihead_Att(nn.Module):
 
     TRUNKS = ('object_features', 'place_features')
 
-    def unfreeze_trunks(self, stages=1):
-        """Opt in to fine-tuning the CNN trunks with frozen BatchNorm statistics (call after model.train()): both trunks go to
-        .eval() -- their running statistics are used and never change -- the parameters of the last `stages` bottleneck stages
+    def unfreeze_trunks(self, stages=1, batchnorm='frozen'):
+        """Opt in to fine-tuning the CNN trunks (call after model.train()): the parameters of the last `stages` bottleneck stages
         (1..4) of each trunk that is present require a gradient and the rest do not, and training mode takes [B,3,H,W] images for
-        either image input (ResNetFeatures.forward_train).  This departs from the reference, whose model.train() gives the trunks
-        batch statistics.  freeze_trunks() undoes it."""
+        either image input (ResNetFeatures.forward_train).  batchnorm='frozen' (the default): both trunks go to .eval() -- their
+        running statistics are used and never change; this departs from the reference, whose model.train() gives the trunks batch
+        statistics.  batchnorm='batch': the trainable stages go to .train() and their BatchNorm layers normalise
+        with the statistics of the batch, move their running buffers and are differentiated through the statistics, as in the
+        reference; the trunk containers, the stem and the stages below stay in .eval() and still run under no_grad with their
+        running statistics (with stages=4 only the stem does).  freeze_trunks() undoes either."""
+        from .train import TRUNK_BATCHNORM_MODES
         if not 1 <= int(stages) <= 4:
             raise ValueError("stages must be 1..4, got %r" % (stages,))
+        if batchnorm not in TRUNK_BATCHNORM_MODES:
+            raise ValueError("batchnorm must be one of %s, got %r" % (TRUNK_BATCHNORM_MODES, batchnorm))
         for n in self.TRUNKS:
             t = getattr(self, n).eval()
             t.requires_grad_(False)
             if not isinstance(t, _NoTrunk):
                 for li in range(8 - int(stages), 8):
                     t[li].requires_grad_(True)
-        self.trunks_trainable, self.trunk_train_stages = True, int(stages)
+                    if batchnorm == 'batch':
+                        t[li].train()
+        self.trunks_trainable, self.trunk_train_stages, self.trunk_train_batchnorm = True, int(stages), batchnorm
         return self
 
     def freeze_trunks(self):
@@ -651,7 +660,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         them one), the trunks follow the model's training flag, and training mode takes precomputed feature maps only."""
         for n in self.TRUNKS:
             getattr(self, n).requires_grad_(True).train(self.training)
-        self.trunks_trainable = False
+        self.trunks_trainable, self.trunk_train_batchnorm = False, 'frozen'
         return self
 
     def _train_maps(self, x, name, trunk=None):
@@ -659,7 +668,9 @@ class Multi_GCN_Multihead_Att(nn.Module):
             if isinstance(trunk, _NoTrunk):
                 raise RuntimeError("%s holds [B,3,H,W] images but the model was built without that CNN trunk: pass a trunk to "
                                    "Multi_GCN_Multihead_Att or feed precomputed [B,2048,h,w] feature maps" % name)
-            return trunk.forward_train(x, self.trunk_train_stages)
+            if self.trunk_train_batchnorm == 'frozen':
+                return trunk.forward_train(x, self.trunk_train_stages)
+            return trunk.forward_train(x, self.trunk_train_stages, batchnorm=self.trunk_train_batchnorm)
         if not (x.dim() == 4 and x.shape[1] == 2048):
             raise NotImplementedError("training mode takes precomputed [B,2048,h,w] feature maps for %s (the CNN trunks do not "
                                       "train); got %s" % (name, tuple(x.shape)))

@@ -1597,6 +1597,102 @@ def map_grad_relu_nhwc(fmap, dmap):
     return g
 
 
+# ---- f4, training with batch statistics: BatchNorm over NHWC bf16 activations (csrc/bn_train.hip) ---------------------------
+def _bn_rows(t, name):
+    """(M, C) of an [..., C] bf16 activation; the refusals the kernels share."""
+    _chk(t, name, torch.bfloat16)
+    if t.dim() < 2:
+        raise ValueError("%s must be [..., C] with at least 2 dimensions, got shape %s" % (name, tuple(t.shape)))
+    C = t.shape[-1]
+    M = t.numel() // C if C else 0
+    if C == 0 or C % 8:
+        raise ValueError("%s: the channel count must be a positive multiple of 8, got C=%d" % (name, C))
+    if M < 2:
+        raise ValueError("%s: batch statistics need at least two values per channel, got %d (shape %s)" % (name, M, tuple(t.shape)))
+    return M, C
+
+
+def _bn_vec(t, name, C):
+    _chk(t, name, ndim=1)
+    if t.shape[0] != C:
+        raise ValueError("%s has %d entries for %d channels" % (name, t.shape[0], C))
+    return t
+
+
+def bn_stats_bf16_nhwc(z, eps, running=None, momentum=0.1, want_var=False):
+    """Batch statistics of z [..., C] bf16 over all leading axes -> (mean [C], rstd [C] = 1 / sqrt(var_biased + eps)) fp32, plus
+    var_biased when want_var.  running = (running_mean, running_var): updated in place by the same launch, running_mean = (1 - m)
+    running_mean + m mean, running_var = (1 - m) running_var + m var_biased M / (M - 1) (num_batches_tracked is the caller's).
+    Rows are reduced in an order fixed by the shape: bit-identical from call to call."""
+    M, C = _bn_rows(z, "z")
+    rm = rv = None
+    if running is not None:
+        if momentum is None:
+            raise NotImplementedError("bn_stats_bf16_nhwc: momentum=None (the cumulative moving average) is not implemented")
+        rm, rv = (_bn_vec(t, n, C) for t, n in zip(running, ("running_mean", "running_var")))
+    m = 0.0 if momentum is None else float(momentum)
+    if not 0.0 <= m <= 1.0:
+        raise ValueError("momentum must be in [0, 1], got %r" % (momentum,))
+    mean = torch.empty(C, device=z.device, dtype=torch.float32)
+    rstd = torch.empty(C, device=z.device, dtype=torch.float32)
+    var = torch.empty(C, device=z.device, dtype=torch.float32) if want_var else None
+    L = _lib.lib()
+    nbytes = L.mgnns_bn_stats_workspace_bytes(M, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    _launch("mgnns_bn_stats_bf16", ("mgnns_bn_stats_bf16", M, C), L.mgnns_bn_stats_bf16, _p(z), M, C, float(eps), m, _p(mean), _p(rstd),
+            _p(var), _p(rm), _p(rv), _p(ws), nbytes, _stream())
+    if rm is not None:                                  # written in place through their addresses: what derives from them is stale
+        torch.autograd.graph.increment_version(rm)
+        torch.autograd.graph.increment_version(rv)
+    return (mean, rstd, var) if want_var else (mean, rstd)
+
+
+def bn_apply_bf16_nhwc(z, mean, rstd, gamma, beta, residual=None, relu=True, out_nchw_f32=False):
+    """relu?(a z + b + residual?) with a = gamma rstd, b = beta - mean a: z [..., C] bf16 -> bf16 of z's shape, or, with
+    out_nchw_f32, z [B, OH, OW, C] -> the unrounded fp32 [B, C, OH, OW] map."""
+    M, C = _bn_rows(z, "z")
+    for t, n in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (beta, "beta")):
+        _bn_vec(t, n, C)
+    if residual is not None:
+        _chk(residual, "residual", torch.bfloat16)
+        if residual.shape != z.shape:
+            raise ValueError("residual %s != z %s" % (tuple(residual.shape), tuple(z.shape)))
+    P = 0
+    if out_nchw_f32:
+        if z.dim() != 4:
+            raise ValueError("out_nchw_f32 needs z as [B, OH, OW, C], got shape %s" % (tuple(z.shape),))
+        B, OH, OW, _ = z.shape
+        P = OH * OW
+        y = torch.empty(B, C, OH, OW, device=z.device, dtype=torch.float32)
+    else:
+        y = torch.empty_like(z)
+    L = _lib.lib()
+    _launch("mgnns_bn_apply_bf16", ("mgnns_bn_apply_bf16", M, C, bool(out_nchw_f32)), L.mgnns_bn_apply_bf16, _p(z), M, C, _p(mean),
+            _p(rstd), _p(gamma), _p(beta), _p(residual), 1 if relu else 0, 1 if out_nchw_f32 else 0, P, _p(y), _stream())
+    return y
+
+
+def bn_backward_bf16_nhwc(g, z, mean, rstd, gamma, want=(True, True)):
+    """Backward of training-mode BatchNorm: g (the gradient of its output, already masked by the producer's ReLU) and the saved z,
+    both [..., C] bf16 -> (g_z bf16 like z, dgamma [C], dbeta [C]) with xhat = (z - mean) rstd, dbeta = sum g, dgamma = sum g xhat,
+    g_z = bf16(gamma rstd (g - dbeta / M - xhat dgamma / M)); want = (dgamma?, dbeta?) picks which sums are returned (else None)."""
+    M, C = _bn_rows(z, "z")
+    _chk(g, "g", torch.bfloat16)
+    if g.shape != z.shape:
+        raise ValueError("g %s != z %s" % (tuple(g.shape), tuple(z.shape)))
+    for t, n in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma")):
+        _bn_vec(t, n, C)
+    gz = torch.empty_like(z)
+    dgamma = torch.empty(C, device=z.device, dtype=torch.float32) if want[0] else None
+    dbeta = torch.empty(C, device=z.device, dtype=torch.float32) if want[1] else None
+    L = _lib.lib()
+    nbytes = L.mgnns_bn_backward_workspace_bytes(M, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
+    _launch("mgnns_bn_backward_bf16", ("mgnns_bn_backward_bf16", M, C), L.mgnns_bn_backward_bf16, _p(g), _p(z), M, C, _p(mean), _p(rstd),
+            _p(gamma), _p(gz), _p(dgamma), _p(dbeta), _p(ws), nbytes, _stream())
+    return gz, dgamma, dbeta
+
+
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------
 _timeline = None          # (slots tensor [uint64 as int64], names list) while tools/graph_timeline.py is recording
 

@@ -12,7 +12,8 @@ attention with dropout on its probabilities, the channel tails and the classifie
 through the Functions at the end of this file once unfrozen.  Feature maps that require a gradient get one (ImgBankFunction,
 csrc/map_grad.hip), so a torch trunk in front of the model fine-tunes through torch's own backward; the trunks of
 mgnns_amd.trunk fine-tune their trailing bottleneck stages with frozen BatchNorm statistics through TrunkStageFunction
-(csrc/conv_train.hip, model.unfreeze_trunks()).
+(csrc/conv_train.hip, model.unfreeze_trunks()), or with the statistics of the batch -- the reference's semantics -- through
+TrunkStageBatchNormFunction (csrc/bn_train.hip, model.unfreeze_trunks(batchnorm='batch')).
 """
 import torch
 
@@ -477,15 +478,142 @@ class TrunkStageFunction(torch.autograd.Function):
         return (g, None, None, None, *grads)
 
 
+class TrunkStageBatchNormFunction(torch.autograd.Function):
+    """TrunkStageFunction with batch statistics, the reference's model.train() semantics for the stages it runs: every
+    convolution is z = conv(x; bf16(conv.weight)) without a bias (packs: trunk.block_packs_raw), every BatchNorm normalises z with
+    the statistics of the batch (ops.bn_stats_bf16_nhwc, which also moves running_mean / running_var; num_batches_tracked goes up by
+    one) and applies gamma, beta, the residual and the ReLU in one sweep (ops.bn_apply_bf16_nhwc); the last block's output is the
+    fp32 NCHW map.  Kept for the backward: x, per block z1, o1, z2, o2, z3, out (and the downsample's z_d), and (mean, rstd) per
+    layer.  keep: None or a list that receives {"x", "blocks": [{"z": [z1, z2, z3(, z_d)], "stats": [(mean, rstd), ...] -- both in
+    trunk.block_layers order --, "o1", "o2", "out", "idn"}]}.  params: (conv.weight, bn.weight, bn.bias) per layer.
+    Backward: dmap is masked by the map and rounded to bf16 NHWC; then per block, last to first, with bn' = ops.bn_backward_bf16_nhwc
+    (which differentiates through the statistics): g_z3 = bn3'(g_out), g_zd = bn_d'(g_out), dW3 = wgrad(o2, g_z3), dWd = wgrad(x, g_zd),
+    g_o2 = dgrad3(g_z3) masked by o2, g_z2 = bn2'(g_o2), dW2 = wgrad(o1, g_z2), g_o1 = dgrad2(g_z2) masked by o1, g_z1 = bn1'(g_o1),
+    dW1 = wgrad(x, g_z1), g_x = dgrad1(g_z1) + (g_out or dgrad_d(g_zd)), masked by x where x is a block's output.  The bf16 roundings of
+    the weight and of z are straight-through; gradients travel in bf16 and every sum is fp32; dW of the raw pack is the weight's own
+    gradient up to its layout.  A parameter gets a gradient iff it requires one, and so does x."""
+
+    @staticmethod
+    def forward(ctx, x, blocks, packs, keep, *params):
+        nchw = x.dtype == torch.float32
+        if nchw:
+            xh = x.detach().permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
+        elif x.dtype == torch.bfloat16:
+            xh = x.detach().contiguous()
+        else:
+            raise TypeError("TrunkStageBatchNormFunction: x must be NHWC bfloat16 or NCHW float32, got %s" % x.dtype)
+
+        def bn_layer(z, bn, residual=None, relu=True, out_nchw_f32=False):
+            running = (bn.running_mean, bn.running_var) if bn.track_running_stats and bn.running_mean is not None else None
+            mean, rstd = ops.bn_stats_bf16_nhwc(z, bn.eps, running=running, momentum=bn.momentum)
+            if running is not None and bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+            y = ops.bn_apply_bf16_nhwc(z, mean, rstd, bn.weight.detach(), bn.bias.detach(), residual=residual, relu=relu,
+                                       out_nchw_f32=out_nchw_f32)
+            return y, (mean, rstd)
+
+        y, acts, stats, kept = xh, [], [], []
+        for i, (blk, pk) in enumerate(zip(blocks, packs)):
+            layers = _block_layers(blk)
+            raw = lambda t, j: ops.conv_bf16_nhwc(t, pk[j][0], pk[j][1], *pk[j][3:], relu=False)
+            idn, zd, st_d = y, None, None
+            if len(pk) == 4:
+                zd = raw(y, 3)
+                idn, st_d = bn_layer(zd, layers[3][1], relu=False)
+            z1 = raw(y, 0)
+            o1, st1 = bn_layer(z1, layers[0][1])
+            z2 = raw(o1, 1)
+            o2, st2 = bn_layer(z2, layers[1][1])
+            z3 = raw(o2, 2)
+            y, st3 = bn_layer(z3, layers[2][1], residual=idn, out_nchw_f32=i == len(blocks) - 1)
+            zs, sts = [z1, z2, z3], [st1, st2, st3]
+            if zd is not None:
+                zs.append(zd)
+                sts.append(st_d)
+            acts += [o1, o2, y] + zs
+            stats += [t for s_ in sts for t in s_]
+            kept.append({"z": zs, "stats": sts, "o1": o1, "o2": o2, "out": y, "idn": idn})
+        if keep is not None:
+            keep.append({"x": xh, "blocks": kept})
+        ctx.nchw = nchw
+        ctx.geom = [[(k, s, p) for _, _, _, k, s, p in pk] for pk in packs]
+        wTs = [c[2] for pk in packs for c in pk]
+        ctx.save_for_backward(xh, *acts, *stats, *wTs, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dmap):
+        st = list(ctx.saved_tensors)
+        nconv = [len(g) for g in ctx.geom]
+        nb, total = len(nconv), sum(nconv)
+        xh = st.pop(0)
+        blk_acts = []
+        for n in nconv:
+            blk_acts.append((st[0], st[1], st[2], st[3:3 + n]))            # o1, o2, out, [z per layer]
+            del st[:3 + n]
+        stats, wTs, params = st[:2 * total], st[2 * total:3 * total], st[3 * total:]
+        need = ctx.needs_input_grad[4:]
+        grads = [None] * len(params)
+        base = [sum(nconv[:i]) for i in range(nb)]
+
+        def bn_back(bi, ci, g):
+            j = base[bi] + ci
+            gz, grads[3 * j + 1], grads[3 * j + 2] = ops.bn_backward_bf16_nhwc(
+                g, blk_acts[bi][3][ci], stats[2 * j], stats[2 * j + 1], params[3 * j + 1], want=(need[3 * j + 1], need[3 * j + 2]))
+            return gz
+
+        def weight_grad(bi, ci, x_in, gz):
+            j = base[bi] + ci
+            if need[3 * j]:
+                k, s, p = ctx.geom[bi][ci]
+                dw = ops.conv_wgrad_bf16_nhwc(x_in, gz, k, s, p)[0]
+                grads[3 * j] = dw.view(dw.shape[0], k, k, -1).permute(0, 3, 1, 2).contiguous()
+
+        def data_grad(bi, ci, g, x_in, mask=None, add=None):
+            k, s, p = ctx.geom[bi][ci]
+            return ops.conv_dgrad_bf16_nhwc(g, wTs[base[bi] + ci], tuple(x_in.shape[1:3]), k, s, p, mask=mask, add=add)
+
+        g = ops.map_grad_relu_nhwc(blk_acts[-1][2], dmap.contiguous().float())
+        for bi in range(nb - 1, -1, -1):
+            x_in = blk_acts[bi - 1][2] if bi else xh
+            o1, o2 = blk_acts[bi][0], blk_acts[bi][1]
+            down = nconv[bi] == 4
+            gz3 = bn_back(bi, 2, g)
+            weight_grad(bi, 2, o2, gz3)
+            gzd = None
+            if down:
+                gzd = bn_back(bi, 3, g)
+                weight_grad(bi, 3, x_in, gzd)
+            gz2 = bn_back(bi, 1, data_grad(bi, 2, gz3, o2, mask=o2))
+            weight_grad(bi, 1, o1, gz2)
+            gz1 = bn_back(bi, 0, data_grad(bi, 1, gz2, o1, mask=o1))
+            weight_grad(bi, 0, x_in, gz1)
+            if bi == 0 and not ctx.needs_input_grad[0]:
+                g = None
+                break
+            other = data_grad(bi, 3, gzd, x_in) if down else g
+            g = data_grad(bi, 0, gz1, x_in, mask=x_in if bi else None, add=other)
+        if g is not None and ctx.nchw:
+            g = g.float().permute(0, 3, 1, 2).contiguous()
+        return (g, None, None, None, *grads)
+
+
+TRUNK_BATCHNORM_MODES = ('frozen', 'batch')
+
+
 def _block_layers(blk):
     from .trunk import block_layers
     return block_layers(blk)
 
 
-def trunk_stage_forward(stages, x, keep=None):
+def trunk_stage_forward(stages, x, keep=None, batchnorm='frozen'):
     """The feature map of `stages` -- an nn.Sequential of trunk.Bottleneck, or a list of such stages run one after the other -- over
-    x (NHWC bf16 or NCHW fp32) with autograd through TrunkStageFunction.  BatchNorm uses and keeps its running statistics."""
-    from .trunk import Bottleneck, block_packs
+    x (NHWC bf16 or NCHW fp32) with autograd.  batchnorm='frozen' (TrunkStageFunction): BatchNorm uses and keeps its running
+    statistics.  batchnorm='batch' (TrunkStageBatchNormFunction): BatchNorm normalises with the statistics of the batch, moves its
+    running buffers and is differentiated through the statistics, whatever the blocks' .training flags say."""
+    from .trunk import Bottleneck, block_packs, block_packs_raw
+    if batchnorm not in TRUNK_BATCHNORM_MODES:
+        raise ValueError("batchnorm must be one of %s, got %r" % (TRUNK_BATCHNORM_MODES, batchnorm))
     if not x.is_cuda:
         raise RuntimeError("x is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % x.device)
     if isinstance(stages, torch.nn.Sequential) and all(isinstance(b, Bottleneck) or hasattr(b, "conv3") for b in stages):
@@ -494,4 +622,6 @@ def trunk_stage_forward(stages, x, keep=None):
     if not blocks:
         raise ValueError("trunk_stage_forward: no bottleneck blocks")
     params = [t for b in blocks for conv, bn in _block_layers(b) for t in (conv.weight, bn.weight, bn.bias)]
+    if batchnorm == 'batch':
+        return TrunkStageBatchNormFunction.apply(x, blocks, [block_packs_raw(b) for b in blocks], keep, *params)
     return TrunkStageFunction.apply(x, blocks, [block_packs(b) for b in blocks], keep, *params)

@@ -12,6 +12,8 @@ on the 3x3 convolution) with torchvision's parameter names, which is what makes 
   block_packs           the folded weights of one Bottleneck plus the transposed packs its backward reads (derived packs,
                         rebuilt when a parameter or a running statistic changes): what frozen-statistics fine-tuning runs on
                         (ResNetFeatures.forward_train, train.TrunkStageFunction).
+  block_packs_raw       the same for batch-statistics fine-tuning: bf16(conv.weight) with nothing folded in, BatchNorm being an
+                        operator of its own there (train.TrunkStageBatchNormFunction, csrc/bn_train.hip).
   ResNetFeatures        the reference's 8-entry nn.Sequential (same child indices -> same `object_features.4.0.conv1.weight`
                         keys), whose forward runs the HIP trunk: BatchNorm folded into bf16 weights once per parameter
                         version, NHWC bf16 activations, every convolution an implicit GEMM on the bf16 MFMA, the last
@@ -130,6 +132,25 @@ def block_packs(blk):
     return out
 
 
+def block_packs_raw(blk):
+    """[(wt, zero bias, wT, k, stride, pad)] per block_layers(blk) for batch-statistics fine-tuning (train.TrunkStageBatchNormFunction,
+    DESIGN.md 14): wt = bf16(conv.weight) without a BatchNorm folded in, a zero fp32 bias, and wt's transposed pack; kept on the
+    block and rebuilt when conv.weight changes."""
+    store = blk.__dict__.setdefault("_train_packs_raw", {})
+    out = []
+    for slot, (conv, _) in enumerate(block_layers(blk)):
+        k, s, p = _conv_geometry(conv, "bottleneck")
+        if conv.bias is not None:
+            raise NotImplementedError("trunk fine-tuning: convolutions with a bias are not supported (torchvision's have none)")
+
+        def build(conv=conv, k=k):
+            wt, bias = ops.conv_fold_bn(conv.weight.detach().contiguous(), None, None)
+            return wt, bias, ops.conv_transpose_pack(wt, k)
+        wt, bias, wT = derived(store, slot, (conv.weight,), build)
+        out.append((wt, bias, wT, k, s, p))
+    return out
+
+
 class ResNetFeatures(nn.Sequential):
     """MODEL:274-294 `nn.Sequential(conv1, bn1, relu, maxpool, layer1..layer4)` with a HIP forward.
 
@@ -187,12 +208,16 @@ class ResNetFeatures(nn.Sequential):
         w, b, k, s, p = convs[2]
         return ops.conv_bf16_nhwc(o, w, b, k, s, p, residual=idn, out_nchw_f32=last)
 
-    def forward_train(self, img, stages=1):
-        """Frozen-statistics fine-tuning forward: img [B,3,H,W] -> the [B,2048,h,w] fp32 map under autograd, with gradients
-        for the parameters of the last `stages` bottleneck stages that require one (train.TrunkStageFunction).  The stem, the
-        max-pool and the stages below run as in forward(), without a graph.  BatchNorm keeps its running statistics, so the
-        module must be in eval mode (model.unfreeze_trunks() puts it there)."""
+    def forward_train(self, img, stages=1, batchnorm='frozen'):
+        """Fine-tuning forward: img [B,3,H,W] -> the [B,2048,h,w] fp32 map under autograd, with gradients for the parameters of
+        the last `stages` bottleneck stages that require one.  The stem, the max-pool and the stages below run as in forward(),
+        without a graph and with their running statistics, so the module itself must be in eval mode (model.unfreeze_trunks()
+        puts it there).  batchnorm='frozen' (train.TrunkStageFunction): the trainable stages keep their running statistics too.
+        batchnorm='batch' (train.TrunkStageBatchNormFunction): their BatchNorm layers normalise with the statistics of the batch,
+        move running_mean / running_var / num_batches_tracked and are differentiated through the statistics."""
         from . import train as _train
+        if batchnorm not in _train.TRUNK_BATCHNORM_MODES:
+            raise ValueError("batchnorm must be one of %s, got %r" % (_train.TRUNK_BATCHNORM_MODES, batchnorm))
         if self.training:
             raise RuntimeError("ResNetFeatures.forward_train keeps BatchNorm's running statistics (frozen-statistics fine-tuning): "
                                "call .eval() on the trunk, or model.unfreeze_trunks()")
@@ -209,7 +234,7 @@ class ResNetFeatures(nn.Sequential):
             y = ops.maxpool3x3s2_nhwc(y)
             for convs, down in blocks[:sum(len(self[li]) for li in range(4, first))]:
                 y = self._run_block(y, convs, down)
-        return _train.trunk_stage_forward([self[li] for li in range(first, 8)], y)
+        return _train.trunk_stage_forward([self[li] for li in range(first, 8)], y, batchnorm=batchnorm)
 
     def forward(self, img):
         if self.training:

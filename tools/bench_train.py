@@ -19,9 +19,13 @@ alternately in one process, three rounds each, best and all rounds reported (csr
 precomputed maps against the step with [B,3,448,448] images and unfreeze_trunks() (ResNet-101 / ResNet-50 trunks; --batch N for a
 smaller batch), three alternating rounds, and each new kernel alone per layer4 geometry with its FLOPs and share of the 2.5 PF bf16
 matrix peak (1x1 layers also algorithmic bytes and TB/s).
+--trunk --batchnorm batch: fine-tuning layer4 with batch statistics (csrc/bn_train.hip) -- the step with images under
+unfreeze_trunks() against unfreeze_trunks(batchnorm='batch'), three alternating rounds, and each BatchNorm kernel alone at layer4's
+[M, C] shapes (M = B*14*14 with C = 512 and 2048, M = B*28*28 with C = 512), alternately with a torch copy_ that moves the same
+number of bytes (read + written), three rounds, best quoted, with the ratio kernel / copy; --kernels-only stops after the kernels.
 --steps-only K: nothing but K whole-model training steps with map gradients in the chosen bank precision -- the run a kernel
 trace is taken of (rocprofv3 --kernel-trace --stats, as tools/prof.sh does for bench.py; table by tools/rocpd_stats.py).
-Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps | --trunk [--batch N] | --steps-only K] [--bank-precision fp32|bf16x3]"""
+Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps | --trunk [--batchnorm batch [--kernels-only]] [--batch N] | --steps-only K] [--bank-precision fp32|bf16x3]"""
 import json
 import math
 import os
@@ -515,6 +519,77 @@ def trunk_case(n):
     return res
 
 
+def trunk_bn_case(n):
+    from mgnns_amd import harness, synth
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    B = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else cfg.B
+    res = {"case": "trunk_batchnorm_%s" % cfg.name, "B": B, "device": torch.cuda.get_device_name(0), "iters": n}
+
+    def against_copy(fn, moved):
+        """fn alternately with a copy_ that reads + writes `moved` bytes in all; three rounds, best of each."""
+        src = torch.empty(moved // 2, dtype=torch.uint8, device=DEV)
+        dst = torch.empty_like(src)
+        tk, tc = [], []
+        for _ in range(3):
+            tk.append(timeit(fn, n, warm=2))
+            tc.append(timeit(lambda: dst.copy_(src), n, warm=2))
+        return {"us": round(min(tk), 1), "copy_us": round(min(tc), 1), "ratio": round(min(tk) / min(tc), 3), "moved_MB": round(moved / 1e6, 1),
+                "TB/s": round(moved / min(tk) / 1e6, 2), "runs_us": [round(t, 1) for t in tk], "copy_runs_us": [round(t, 1) for t in tc]}
+
+    kern = {}
+    for hw, C in ((14, 512), (14, 2048), (28, 512)):
+        g = torch.Generator(device=DEV).manual_seed(hw + C)
+        z = torch.randn(B, hw, hw, C, device=DEV, generator=g).to(torch.bfloat16)
+        gy = torch.randn(B, hw, hw, C, device=DEV, generator=g).to(torch.bfloat16)
+        gamma, beta = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
+        rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+        mean, rstd = ops.bn_stats_bf16_nhwc(z, 1e-5)
+        nb = z.numel() * 2
+        row = {"M": B * hw * hw, "C": C}
+        row["bn_stats"] = against_copy(lambda: ops.bn_stats_bf16_nhwc(z, 1e-5, running=(rm, rv)), nb)
+        row["bn_apply"] = against_copy(lambda: ops.bn_apply_bf16_nhwc(z, mean, rstd, gamma, beta), 2 * nb)
+        row["bn_apply_residual"] = against_copy(lambda: ops.bn_apply_bf16_nhwc(z, mean, rstd, gamma, beta, residual=gy), 3 * nb)
+        if C == 2048:
+            row["bn_apply_residual_nchw_f32"] = against_copy(
+                lambda: ops.bn_apply_bf16_nhwc(z, mean, rstd, gamma, beta, residual=gy, out_nchw_f32=True), 4 * nb)
+        row["bn_backward"] = against_copy(lambda: ops.bn_backward_bf16_nhwc(gy, z, mean, rstd, gamma), 5 * nb)   # g, z read twice
+        kern["%dx%dx%d" % (hw, hw, C)] = row
+        del z, gy
+    res["kernels"] = kern
+    if "--kernels-only" in sys.argv:
+        return res
+
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV, trunks=True).train().freeze_text_encoders()
+    imgs = list(harness.call_args(inp, DEV))
+    G = torch.randn(B, cfg.NL, device=DEV)
+    g = torch.Generator().manual_seed(1)
+    for i in (3, 4):
+        imgs[i] = torch.randn(B, 3, 448, 448, generator=g).to(DEV)
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        torch.autograd.backward(model(*imgs), G)
+
+    ta, tb = [], []
+    for _ in range(3):
+        model.unfreeze_trunks()
+        ta.append(timeit(step, n, warm=1))
+        model.unfreeze_trunks(batchnorm="batch")
+        tb.append(timeit(step, n, warm=1))
+    res["step_images_frozen_statistics_us"] = round(min(ta), 1)
+    res["step_images_batch_statistics_us"] = round(min(tb), 1)
+    res["step_ratio"] = round(min(tb) / min(ta), 3)
+    res["step_runs_us"] = {"frozen": [round(t, 1) for t in ta], "batch": [round(t, 1) for t in tb]}
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    torch.cuda.synchronize()
+    res["step_batch_peak_GB"] = round(torch.cuda.max_memory_allocated() / 1e9, 2)
+    return res
+
+
 def steps_only(k):
     from mgnns_amd import harness, synth
     cfg = synth.CONFIGS["mvsa_multiple_b256"]
@@ -544,6 +619,12 @@ def main():
         return
     if "--maps" in sys.argv:
         print(json.dumps(maps_case(n)), flush=True)
+        return
+    if "--trunk" in sys.argv and "--batchnorm" in sys.argv:
+        mode = sys.argv[sys.argv.index("--batchnorm") + 1]
+        if mode not in ("frozen", "batch"):
+            raise SystemExit("bench_train: --batchnorm frozen|batch")
+        print(json.dumps(trunk_case(n) if mode == "frozen" else trunk_bn_case(n)), flush=True)
         return
     if "--trunk" in sys.argv:
         print(json.dumps(trunk_case(n)), flush=True)
