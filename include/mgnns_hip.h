@@ -821,6 +821,30 @@ int mgnns_bn_backward_bf16(const void* g, const void* z, int M, int C, const flo
                            const float* gamma, void* gz, float* dgamma, float* dbeta, void* workspace,
                            size_t workspace_bytes, mgnns_stream_t stream);
 
+/* ---- f4 (trunk half, training): the stem -- conv1 7x7 / stride 2 / pad 3 (3 -> 64) and MaxPool2d(3, 2, 1) -- so that a trunk
+ * fine-tunes end to end (csrc/stem_train.hip).  Added under ABI 26 without a bump, as the BatchNorm entries were:
+ * the change is additive.  OH = (H - 1) / 2 + 1 throughout.  No float atomics: results are bit-identical from call to call.
+ *  mgnns_stem_conv7_raw_fwd     z = conv1(bf16(img); wt) alone, no bias and no ReLU: img [B,3,H,W] fp32 NCHW -> z [B,OH,OW,64] bf16
+ *                               NHWC; wt the stem pack of mgnns_conv_fold_bn_bf16 (k_order 1, ld 160) built with gamma == NULL.
+ *                               mgnns_stem_conv7_fwd is the same kernel with its bias + ReLU epilogue and is unchanged.
+ *  mgnns_stem_wgrad             dW[o,(kh,kw,c)] = sum over (b,oh,ow) of g[b,oh,ow,o] * bf16(img[b,c,2 oh + kh - 3,2 ow + kw - 3])
+ *                               (zero outside the image; the image rounded as the forward rounds it), db[o] = sum g[b,oh,ow,o];
+ *                               img [B,3,H,W] fp32, g [B,OH,OW,64] bf16 NHWC, dW [64,147] and db [64] fp32.  dW is in the order
+ *                               mgnns_conv_bn_unfold reads.  Workgroups write one partial each to `workspace`
+ *                               (mgnns_stem_wgrad_workspace_bytes bytes, a function of the shape alone; always needed when
+ *                               B > 0) and a second launch adds them in order.  B == 0 zeroes the outputs.
+ *  mgnns_maxpool3x3s2_nhwc_bwd  backward of mgnns_maxpool3x3s2_nhwc_fwd: x [B,H,W,C] (the pool's input) and gy [B,OH,OW,C] ->
+ *                               gx [B,H,W,C], all bf16 NHWC, C % 8 == 0.  A pixel receives gy of every window whose FIRST
+ *                               maximum (row-major scan, strict >; torch's rule) it is; the sum is fp32 and rounded once.
+ *                               relu_mask != 0 zeroes gx where x <= 0.  x must hold no NaN.
+ */
+int mgnns_stem_conv7_raw_fwd(const float* img, int B, int H, int W, const void* wt, void* z, mgnns_stream_t stream);
+size_t mgnns_stem_wgrad_workspace_bytes(int B, int H, int W);
+int mgnns_stem_wgrad(const float* img, const void* g, int B, int H, int W, float* dW, float* db, void* workspace,
+                     size_t workspace_bytes, mgnns_stream_t stream);
+int mgnns_maxpool3x3s2_nhwc_bwd(const void* x, const void* gy, int B, int H, int W, int C, int relu_mask, void* gx,
+                                mgnns_stream_t stream);
+
 /* ---- measurement aid: a one-thread kernel that writes the GPU's constant-rate real-time counter (s_memrealtime,
  * 100 MHz) into slots[idx] when the stream reaches it.  Captured into the forward's hipGraph it gives the REAL
  * timeline of the concurrent branches of a replay (rocprofv3 serialises / perturbs them): tools/graph_timeline.py.

@@ -89,6 +89,9 @@ SIGNATURES = {
     "mgnns_bn_stats_bf16": [_P, _I, _I, _F, _c.c_double, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "mgnns_bn_apply_bf16": [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
     "mgnns_bn_backward_bf16": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
+    "mgnns_stem_conv7_raw_fwd": [_P, _I, _I, _I, _P, _P, _P],
+    "mgnns_stem_wgrad": [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_maxpool3x3s2_nhwc_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "mgnns_label_gcn_supported": [_I, _I, _I, _I, _I],
     "mgnns_label_tail_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
     "mgnns_label_tail_bf16_supported": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
@@ -164,6 +167,7 @@ SIZE_GETTERS = {
     "mgnns_conv_wgrad_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
     "mgnns_bn_stats_workspace_bytes": [_I, _I],
     "mgnns_bn_backward_workspace_bytes": [_I, _I],
+    "mgnns_stem_wgrad_workspace_bytes": [_I, _I, _I],
 }
 
 _lib = None

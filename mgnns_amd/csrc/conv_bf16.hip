@@ -52,8 +52,10 @@ __global__ __launch_bounds__(256) void conv_fold_bn_kernel(const float* __restri
 // Stem: one workgroup = 8 output rows x 32 output columns x 64 channels of one image; the 21 x 69 x 3 input patch is
 // staged in LDS as bf16; a wave owns two output rows (four 16-pixel MFMA tiles).  K = (c, kh, kw) = 147, padded to 160:
 // the A fragment of a lane (8 consecutive k) is gathered with 16-bit LDS reads through per-lane patch offsets.
+// RAW: the convolution alone -- no bias, no ReLU -- for batch-statistics fine-tuning, where bn1 is an operator of its own.
 constexpr int ST_ROWS = 8, ST_COLS = 32, ST_PR = 2 * ST_ROWS + 5, ST_PC = 2 * ST_COLS + 5, ST_K = 160;
 
+template <bool RAW>
 __global__ __launch_bounds__(256) void stem_conv7_kernel(const float* __restrict__ img, int H, int W, int OH, int OW,
                                                          const unsigned short* __restrict__ wt, const float* __restrict__ bias,
                                                          unsigned short* __restrict__ y) {
@@ -126,10 +128,15 @@ __global__ __launch_bounds__(256) void stem_conv7_kernel(const float* __restrict
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt) {
                 const int n = jt * 16 + fg * 4;
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + n);
                 uint2 o;
-                o.x = mg_bf16x2(fmaxf(acc[jt][0] + bv[0], 0.f), fmaxf(acc[jt][1] + bv[1], 0.f));
-                o.y = mg_bf16x2(fmaxf(acc[jt][2] + bv[2], 0.f), fmaxf(acc[jt][3] + bv[3], 0.f));
+                if constexpr (RAW) {
+                    o.x = mg_bf16x2(acc[jt][0], acc[jt][1]);
+                    o.y = mg_bf16x2(acc[jt][2], acc[jt][3]);
+                } else {
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(bias + n);
+                    o.x = mg_bf16x2(fmaxf(acc[jt][0] + bv[0], 0.f), fmaxf(acc[jt][1] + bv[1], 0.f));
+                    o.y = mg_bf16x2(fmaxf(acc[jt][2] + bv[2], 0.f), fmaxf(acc[jt][3] + bv[3], 0.f));
+                }
                 *reinterpret_cast<uint2*>(dst + n) = o;
             }
         }
@@ -520,9 +527,22 @@ extern "C" int mgnns_stem_conv7_fwd(const float* img, int B, int H, int W, const
     if (B == 0) return 0;
     const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
     dim3 grid((OW + ST_COLS - 1) / ST_COLS, (OH + ST_ROWS - 1) / ST_ROWS, B);
-    hipLaunchKernelGGL(stem_conv7_kernel, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, OH, OW,
+    hipLaunchKernelGGL(stem_conv7_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, OH, OW,
                        reinterpret_cast<const unsigned short*>(wt), bias, reinterpret_cast<unsigned short*>(y));
     MG_CHECK_LAUNCH("mgnns_stem_conv7_fwd");
+    return 0;
+}
+
+extern "C" int mgnns_stem_conv7_raw_fwd(const float* img, int B, int H, int W, const void* wt, void* z, mgnns_stream_t stream) {
+    MG_REQUIRE(img && wt && z, "mgnns_stem_conv7_raw_fwd: null pointer");
+    MG_REQUIRE(B >= 0 && H >= 7 && W >= 7 && B <= 65535, "mgnns_stem_conv7_raw_fwd: bad dims B=%d H=%d W=%d", B, H, W);
+    MG_REQUIRE(mg_aligned16(wt) && mg_aligned16(z), "mgnns_stem_conv7_raw_fwd: operands must be 16-byte aligned");
+    if (B == 0) return 0;
+    const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
+    dim3 grid((OW + ST_COLS - 1) / ST_COLS, (OH + ST_ROWS - 1) / ST_ROWS, B);
+    hipLaunchKernelGGL(stem_conv7_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, img, H, W, OH, OW,
+                       reinterpret_cast<const unsigned short*>(wt), (const float*)nullptr, reinterpret_cast<unsigned short*>(z));
+    MG_CHECK_LAUNCH("mgnns_stem_conv7_raw_fwd");
     return 0;
 }
 

@@ -229,6 +229,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         self.trunks_trainable = False          # unfreeze_trunks(): training mode takes images and fine-tunes the trunks' last stages
         self.trunk_train_stages = 1
         self.trunk_train_batchnorm = 'frozen'  # or 'batch': the trainable stages' BatchNorm uses the statistics of the batch
+        self.trunk_train_stem = False          # unfreeze_trunks(4, stem=True): conv1 / bn1 train with the four stages
         self._lstm_cache = ops.LstmCache()     # derived LSTM weight forms live and die with this module
         self._streams = None
         self.use_streams = bool(opt.get('use_streams', True))
@@ -630,7 +631,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
 
     TRUNKS = ('object_features', 'place_features')
 
-    def unfreeze_trunks(self, stages=1, batchnorm='frozen'):
+    def unfreeze_trunks(self, stages=1, batchnorm='frozen', stem=False):
         """Opt in to fine-tuning the CNN trunks (call after model.train()): the parameters of the last `stages` bottleneck stages
         (1..4) of each trunk that is present require a gradient and the rest do not, and training mode takes [B,3,H,W] images for
         either image input (ResNetFeatures.forward_train).  batchnorm='frozen' (the default): both trunks go to .eval() -- their
@@ -638,21 +639,26 @@ class Multi_GCN_Multihead_Att(nn.Module):
         statistics.  batchnorm='batch': the trainable stages go to .train() and their BatchNorm layers normalise
         with the statistics of the batch, move their running buffers and are differentiated through the statistics, as in the
         reference; the trunk containers, the stem and the stages below stay in .eval() and still run under no_grad with their
-        running statistics (with stages=4 only the stem does).  freeze_trunks() undoes either."""
+        running statistics.  stem=True (needs stages=4): conv1 and bn1 require a gradient too and the stem trains with the stages
+        (in 'batch' mode those two also go to .train() and bn1 uses and moves batch statistics): the whole trunk fine-tunes, as the
+        reference's optimizer has it.  freeze_trunks() undoes all of it."""
         from .train import TRUNK_BATCHNORM_MODES
         if not 1 <= int(stages) <= 4:
             raise ValueError("stages must be 1..4, got %r" % (stages,))
         if batchnorm not in TRUNK_BATCHNORM_MODES:
             raise ValueError("batchnorm must be one of %s, got %r" % (TRUNK_BATCHNORM_MODES, batchnorm))
+        if stem and int(stages) != 4:
+            raise ValueError("stem=True trains the stem below four trainable stages: it needs stages=4, got stages=%r" % (stages,))
         for n in self.TRUNKS:
             t = getattr(self, n).eval()
             t.requires_grad_(False)
             if not isinstance(t, _NoTrunk):
-                for li in range(8 - int(stages), 8):
+                for li in ((0, 1) if stem else ()) + tuple(range(8 - int(stages), 8)):
                     t[li].requires_grad_(True)
                     if batchnorm == 'batch':
                         t[li].train()
         self.trunks_trainable, self.trunk_train_stages, self.trunk_train_batchnorm = True, int(stages), batchnorm
+        self.trunk_train_stem = bool(stem)
         return self
 
     def freeze_trunks(self):
@@ -660,7 +666,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
         them one), the trunks follow the model's training flag, and training mode takes precomputed feature maps only."""
         for n in self.TRUNKS:
             getattr(self, n).requires_grad_(True).train(self.training)
-        self.trunks_trainable, self.trunk_train_batchnorm = False, 'frozen'
+        self.trunks_trainable, self.trunk_train_batchnorm, self.trunk_train_stem = False, 'frozen', False
         return self
 
     def _train_maps(self, x, name, trunk=None):
@@ -668,6 +674,8 @@ class Multi_GCN_Multihead_Att(nn.Module):
             if isinstance(trunk, _NoTrunk):
                 raise RuntimeError("%s holds [B,3,H,W] images but the model was built without that CNN trunk: pass a trunk to "
                                    "Multi_GCN_Multihead_Att or feed precomputed [B,2048,h,w] feature maps" % name)
+            if self.trunk_train_stem:
+                return trunk.forward_train(x, self.trunk_train_stages, batchnorm=self.trunk_train_batchnorm, stem=True)
             if self.trunk_train_batchnorm == 'frozen':
                 return trunk.forward_train(x, self.trunk_train_stages)
             return trunk.forward_train(x, self.trunk_train_stages, batchnorm=self.trunk_train_batchnorm)

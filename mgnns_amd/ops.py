@@ -1441,8 +1441,9 @@ def conv_fold_bn(weight, conv_bias=None, bn=None, stem=False):
     return wt, bias
 
 
-def stem_conv7(img, wt, bias):
-    """relu(bn1(conv1(img))): img [B,3,H,W] fp32 NCHW -> [B, OH, OW, 64] bf16 NHWC."""
+def stem_conv7(img, wt, bias, raw=False):
+    """relu(bn1(conv1(img))): img [B,3,H,W] fp32 NCHW -> [B, OH, OW, 64] bf16 NHWC.  raw=True: the convolution alone,
+    z = conv1(bf16(img); wt) without bias or ReLU, on the pack conv_fold_bn(w, None, None, stem=True) (the bias is not read)."""
     _chk(img, "img", ndim=4)
     _chk(wt, "wt", torch.bfloat16, 2)
     _chk(bias, "bias", ndim=1)
@@ -1452,6 +1453,10 @@ def stem_conv7(img, wt, bias):
                          % (STEM_LD, tuple(img.shape), tuple(wt.shape), tuple(bias.shape)))
     y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, device=img.device, dtype=torch.bfloat16)
     L = _lib.lib()
+    if raw:
+        _launch("mgnns_stem_conv7_raw_fwd", ("mgnns_stem_conv7_raw_fwd",), L.mgnns_stem_conv7_raw_fwd, _p(img), B, H, W, _p(wt), _p(y),
+                _stream())
+        return y
     _launch("mgnns_stem_conv7_fwd", ("mgnns_stem_conv7_fwd",), L.mgnns_stem_conv7_fwd, _p(img), B, H, W, _p(wt), _p(bias),
             _p(y), _stream())
     return y
@@ -1691,6 +1696,47 @@ def bn_backward_bf16_nhwc(g, z, mean, rstd, gamma, want=(True, True)):
     _launch("mgnns_bn_backward_bf16", ("mgnns_bn_backward_bf16", M, C), L.mgnns_bn_backward_bf16, _p(g), _p(z), M, C, _p(mean), _p(rstd),
             _p(gamma), _p(gz), _p(dgamma), _p(dbeta), _p(ws), nbytes, _stream())
     return gz, dgamma, dbeta
+
+
+# ---- f4, training: the stem's backward (csrc/stem_train.hip) ------------------------------------------------------------------
+def stem_wgrad(img, g):
+    """Weight gradient of the stem convolution: img [B,3,H,W] fp32 NCHW (rounded to bf16 as stem_conv7 rounds it), g [B,OH,OW,64]
+    bf16 NHWC (the gradient of the convolution's output) -> (dW' [64,147] fp32 with k = (kh, kw, c) -- the layout conv_bn_unfold
+    takes --, db' [64] fp32); pixels reduced in an order fixed by the shape."""
+    _chk(img, "img", ndim=4)
+    _chk(g, "g", torch.bfloat16, 4)
+    B, C, H, W = img.shape
+    if C != 3 or H < 7 or W < 7:
+        raise ValueError("stem expects img [B,3,H,W] with H, W >= 7, got %s" % (tuple(img.shape),))
+    if tuple(g.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64):
+        raise ValueError("g %s does not match the stem's output [%d,%d,%d,64] for img %s"
+                         % (tuple(g.shape), B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, tuple(img.shape)))
+    dW = torch.empty(64, 147, device=img.device, dtype=torch.float32)
+    db = torch.empty(64, device=img.device, dtype=torch.float32)
+    L = _lib.lib()
+    nbytes = L.mgnns_stem_wgrad_workspace_bytes(B, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device) if nbytes else None
+    _launch("mgnns_stem_wgrad", ("mgnns_stem_wgrad", H, W), L.mgnns_stem_wgrad, _p(img), _p(g), B, H, W, _p(dW), _p(db), _p(ws), nbytes,
+            _stream())
+    return dW, db
+
+
+def maxpool3x3s2_bwd_nhwc(x, g_y, relu_mask=False):
+    """Backward of maxpool3x3s2_nhwc: x [B,H,W,C] bf16 (the pool's input), g_y [B,OH,OW,C] bf16 -> g_x [B,H,W,C] bf16.  A pixel takes
+    g_y of the windows whose first maximum it is (row-major scan, strict >: torch's rule), summed in fp32 and rounded once;
+    relu_mask=True also zeroes g_x where x <= 0 (a ReLU whose output x is)."""
+    _chk(x, "x", torch.bfloat16, 4)
+    _chk(g_y, "g_y", torch.bfloat16, 4)
+    B, H, W, C = x.shape
+    if C == 0 or C % 8:
+        raise ValueError("x: the channel count must be a positive multiple of 8, got C=%d" % C)
+    if H == 0 or W == 0 or tuple(g_y.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C):
+        raise ValueError("g_y %s does not match the pooled shape of x %s" % (tuple(g_y.shape), tuple(x.shape)))
+    g_x = torch.empty_like(x)
+    L = _lib.lib()
+    _launch("mgnns_maxpool3x3s2_nhwc_bwd", ("mgnns_maxpool3x3s2_nhwc_bwd", bool(relu_mask)), L.mgnns_maxpool3x3s2_nhwc_bwd, _p(x), _p(g_y),
+            B, H, W, C, 1 if relu_mask else 0, _p(g_x), _stream())
+    return g_x
 
 
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------

@@ -13,7 +13,9 @@ through the Functions at the end of this file once unfrozen.  Feature maps that 
 csrc/map_grad.hip), so a torch trunk in front of the model fine-tunes through torch's own backward; the trunks of
 mgnns_amd.trunk fine-tune their trailing bottleneck stages with frozen BatchNorm statistics through TrunkStageFunction
 (csrc/conv_train.hip, model.unfreeze_trunks()), or with the statistics of the batch -- the reference's semantics -- through
-TrunkStageBatchNormFunction (csrc/bn_train.hip, model.unfreeze_trunks(batchnorm='batch')).
+TrunkStageBatchNormFunction (csrc/bn_train.hip, model.unfreeze_trunks(batchnorm='batch')).  With all four stages trainable the
+stem -- conv1, bn1, ReLU, max-pool -- trains too, through TrunkStemFunction / TrunkStemBatchNormFunction (csrc/stem_train.hip,
+model.unfreeze_trunks(4, stem=True)): nothing of a trunk is then left frozen.
 """
 import torch
 
@@ -599,6 +601,107 @@ class TrunkStageBatchNormFunction(torch.autograd.Function):
 
 
 TRUNK_BATCHNORM_MODES = ('frozen', 'batch')
+
+
+# ---- the CNN trunks' stem (csrc/stem_train.hip) -----------------------------------------------------------------
+def _stem_gy(g_y, y0):
+    if g_y.dtype != torch.bfloat16:
+        raise TypeError("the stem's backward takes the stage Function's bf16 NHWC input gradient, got %s" % g_y.dtype)
+    return ops.maxpool3x3s2_bwd_nhwc(y0, g_y.contiguous(), relu_mask=True)
+
+
+class TrunkStemFunction(torch.autograd.Function):
+    """y [B, OH/2, OW/2, 64] bf16 NHWC = maxpool(y0), y0 = relu(bn1(conv1(img))) with frozen statistics: the eval stem, bit for bit
+    (ops.stem_conv7 on the folded pack `pack` = (wt, bias) of ops.conv_fold_bn(..., stem=True), then ops.maxpool3x3s2_nhwc).  Kept for
+    the backward: the fp32 image and y0.  keep: None or a list that receives {"img": the image as bf16 (what the convolution
+    multiplied), "y0", "y"}.  Backward, from g_y (bf16 NHWC, the stage Function's unmasked input gradient): g_y0 =
+    ops.maxpool3x3s2_bwd_nhwc(y0, g_y, relu_mask=True) -- the pool's first-maximum routing and the ReLU's mask in one rounding --,
+    (dW', db') = ops.stem_wgrad(img, g_y0), and ops.conv_bn_unfold gives the gradients of conv1.weight, bn1.weight and bn1.bias; each
+    gets one iff it requires one.  The image never gets a gradient (None): no kernel here differentiates the stem with respect to
+    its input."""
+
+    @staticmethod
+    def forward(ctx, img, bn, pack, keep, conv_w, gamma, beta):
+        imgc = img.detach().contiguous()
+        y0 = ops.stem_conv7(imgc, *pack)
+        y = ops.maxpool3x3s2_nhwc(y0)
+        if keep is not None:
+            keep.append({"img": imgc.to(torch.bfloat16), "y0": y0, "y": y})
+        ctx.eps = bn.eps
+        ctx.save_for_backward(imgc, y0, bn.running_mean, bn.running_var, conv_w, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        img, y0, mean, var, conv_w, gamma = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[4:7])
+        if not any(want):
+            return (None,) * 7
+        dwp, dbp = ops.stem_wgrad(img, _stem_gy(g_y, y0))
+        return (None, None, None, None, *ops.conv_bn_unfold(dwp, dbp, conv_w, (gamma, mean, var, ctx.eps), want=want))
+
+
+class TrunkStemBatchNormFunction(torch.autograd.Function):
+    """TrunkStemFunction with batch statistics: z0 = conv1(bf16(img); bf16(conv1.weight)) without bias or ReLU (ops.stem_conv7(raw=True)
+    on `pack` = ops.conv_fold_bn(w, None, None, stem=True)), (mean, rstd) of z0 over the batch (ops.bn_stats_bf16_nhwc, which moves
+    bn1.running_mean / running_var; num_batches_tracked goes up by one), y0 = relu(gamma (z0 - mean) rstd + beta)
+    (ops.bn_apply_bf16_nhwc), y = maxpool(y0).  Kept: the image, z0, y0, (mean, rstd); keep receives {"img" (bf16), "z0", "y0", "y",
+    "stats": (mean, rstd)}.  Backward: g_y0 as in TrunkStemFunction, (g_z0, dgamma, dbeta) = ops.bn_backward_bf16_nhwc(g_y0, z0, ...)
+    through the statistics, dW = ops.stem_wgrad(img, g_z0)[0] re-laid out as conv1.weight (the bf16 rounding of the weight is
+    straight-through).  A parameter gets a gradient iff it requires one; the image never does."""
+
+    @staticmethod
+    def forward(ctx, img, bn, pack, keep, conv_w, gamma, beta):
+        imgc = img.detach().contiguous()
+        z0 = ops.stem_conv7(imgc, *pack, raw=True)
+        running = (bn.running_mean, bn.running_var) if bn.track_running_stats and bn.running_mean is not None else None
+        mean, rstd = ops.bn_stats_bf16_nhwc(z0, bn.eps, running=running, momentum=bn.momentum)
+        if running is not None and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        y0 = ops.bn_apply_bf16_nhwc(z0, mean, rstd, gamma.detach(), beta.detach())
+        y = ops.maxpool3x3s2_nhwc(y0)
+        if keep is not None:
+            keep.append({"img": imgc.to(torch.bfloat16), "z0": z0, "y0": y0, "y": y, "stats": (mean, rstd)})
+        ctx.save_for_backward(imgc, z0, y0, mean, rstd, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, g_y):
+        img, z0, y0, mean, rstd, gamma = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[4:7])
+        if not any(want):
+            return (None,) * 7
+        gz, dgamma, dbeta = ops.bn_backward_bf16_nhwc(_stem_gy(g_y, y0), z0, mean, rstd, gamma, want=want[1:])
+        dw = None
+        if want[0]:
+            dw = ops.stem_wgrad(img, gz)[0].view(64, 7, 7, 3).permute(0, 3, 1, 2).contiguous()
+        return (None, None, None, None, dw, dgamma, dbeta)
+
+
+def stem_pack_raw(conv):
+    """(bf16(conv1.weight) in the stem's [64, 160] layout, a zero bias): the pack of batch-statistics fine-tuning, kept on the module
+    and rebuilt when the weight changes."""
+    from .derived import derived
+    store = conv.__dict__.setdefault("_train_packs_raw", {})
+    return derived(store, "stem", (conv.weight,), lambda: ops.conv_fold_bn(conv.weight.detach().contiguous(), None, None, stem=True))
+
+
+def trunk_stem_forward(conv, bn, img, pack=None, keep=None, batchnorm='frozen'):
+    """The stem of a trunk -- conv (7x7 / 2 / 3, 3 -> 64, no bias), bn, ReLU, MaxPool2d(3, 2, 1) -- over img [B,3,H,W] fp32 with
+    autograd: -> [B, h, w, 64] bf16 NHWC, which requires a gradient iff one of conv.weight, bn.weight, bn.bias does.  pack: the folded
+    stem pack if the caller has it (frozen mode), else it is built here."""
+    if batchnorm not in TRUNK_BATCHNORM_MODES:
+        raise ValueError("batchnorm must be one of %s, got %r" % (TRUNK_BATCHNORM_MODES, batchnorm))
+    if not img.is_cuda:
+        raise RuntimeError("img is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % img.device)
+    if conv.bias is not None:
+        raise NotImplementedError("trunk fine-tuning: convolutions with a bias are not supported (torchvision's have none)")
+    if batchnorm == 'batch':
+        return TrunkStemBatchNormFunction.apply(img, bn, stem_pack_raw(conv), keep, conv.weight, bn.weight, bn.bias)
+    if pack is None:
+        from .trunk import ResNetFeatures
+        pack = ResNetFeatures._fold(conv, bn, stem=True)
+    return TrunkStemFunction.apply(img, bn, pack, keep, conv.weight, bn.weight, bn.bias)
 
 
 def _block_layers(blk):

@@ -14,6 +14,8 @@ on the 3x3 convolution) with torchvision's parameter names, which is what makes 
                         (ResNetFeatures.forward_train, train.TrunkStageFunction).
   block_packs_raw       the same for batch-statistics fine-tuning: bf16(conv.weight) with nothing folded in, BatchNorm being an
                         operator of its own there (train.TrunkStageBatchNormFunction, csrc/bn_train.hip).
+  (the stem)            with all four stages trainable the stem trains too: ResNetFeatures.forward_train(img, 4, stem=True),
+                        train.TrunkStemFunction / TrunkStemBatchNormFunction, csrc/stem_train.hip, DESIGN.md 15.
   ResNetFeatures        the reference's 8-entry nn.Sequential (same child indices -> same `object_features.4.0.conv1.weight`
                         keys), whose forward runs the HIP trunk: BatchNorm folded into bf16 weights once per parameter
                         version, NHWC bf16 activations, every convolution an implicit GEMM on the bf16 MFMA, the last
@@ -208,13 +210,16 @@ class ResNetFeatures(nn.Sequential):
         w, b, k, s, p = convs[2]
         return ops.conv_bf16_nhwc(o, w, b, k, s, p, residual=idn, out_nchw_f32=last)
 
-    def forward_train(self, img, stages=1, batchnorm='frozen'):
+    def forward_train(self, img, stages=1, batchnorm='frozen', stem=False):
         """Fine-tuning forward: img [B,3,H,W] -> the [B,2048,h,w] fp32 map under autograd, with gradients for the parameters of
         the last `stages` bottleneck stages that require one.  The stem, the max-pool and the stages below run as in forward(),
         without a graph and with their running statistics, so the module itself must be in eval mode (model.unfreeze_trunks()
         puts it there).  batchnorm='frozen' (train.TrunkStageFunction): the trainable stages keep their running statistics too.
         batchnorm='batch' (train.TrunkStageBatchNormFunction): their BatchNorm layers normalise with the statistics of the batch,
-        move running_mean / running_var / num_batches_tracked and are differentiated through the statistics."""
+        move running_mean / running_var / num_batches_tracked and are differentiated through the statistics.
+        stem=True (needs stages=4): the stem trains too -- conv1.weight, bn1.weight and bn1.bias get gradients if they require one
+        (train.TrunkStemFunction), and in 'batch' mode bn1 uses and moves batch statistics like every other BatchNorm
+        (train.TrunkStemBatchNormFunction).  The image itself never gets a gradient."""
         from . import train as _train
         if batchnorm not in _train.TRUNK_BATCHNORM_MODES:
             raise ValueError("batchnorm must be one of %s, got %r" % (_train.TRUNK_BATCHNORM_MODES, batchnorm))
@@ -223,10 +228,19 @@ class ResNetFeatures(nn.Sequential):
                                "call .eval() on the trunk, or model.unfreeze_trunks()")
         if not 1 <= int(stages) <= 4:
             raise ValueError("stages must be 1..4, got %r" % (stages,))
+        if stem and int(stages) != 4:
+            raise ValueError("stem=True trains the stem below four trainable stages: it needs stages=4, got stages=%r" % (stages,))
         if img.dim() != 4 or img.shape[1] != 3:
             raise ValueError("trunk input must be [B, 3, H, W], got %s" % (tuple(img.shape),))
         if not img.is_cuda:
             raise RuntimeError("img is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % img.device)
+        if stem:
+            pack = None
+            if batchnorm == 'frozen':
+                with torch.no_grad():
+                    pack = self._prepare()[0]
+            y = _train.trunk_stem_forward(self[0], self[1], img, pack=pack, batchnorm=batchnorm)
+            return _train.trunk_stage_forward([self[li] for li in range(4, 8)], y, batchnorm=batchnorm)
         first = 8 - int(stages)
         with torch.no_grad():
             stem, blocks = self._prepare()

@@ -23,6 +23,11 @@ matrix peak (1x1 layers also algorithmic bytes and TB/s).
 unfreeze_trunks() against unfreeze_trunks(batchnorm='batch'), three alternating rounds, and each BatchNorm kernel alone at layer4's
 [M, C] shapes (M = B*14*14 with C = 512 and 2048, M = B*28*28 with C = 512), alternately with a torch copy_ that moves the same
 number of bytes (read + written), three rounds, best quoted, with the ratio kernel / copy; --kernels-only stops after the kernels.
+--trunk --stem: fine-tuning the whole trunk, stem included (csrc/stem_train.hip) -- maxpool3x3s2_bwd with the ReLU mask at the stem's
+[B,224,224,64] alternately with a torch copy_ of the same bytes, stem_wgrad (with its reduce launch) at [B,3,448,448] alternately with
+conv_wgrad at layer4.0.conv2's geometry (its % of the 2.5 PF bf16 peak and the ratio), the raw stem forward next to the folded one, and
+the step with images under unfreeze_trunks(4) against unfreeze_trunks(4, stem=True) in each BatchNorm mode; three alternating rounds,
+best quoted; --kernels-only stops after the kernels, --batch N sizes everything.
 --steps-only K: nothing but K whole-model training steps with map gradients in the chosen bank precision -- the run a kernel
 trace is taken of (rocprofv3 --kernel-trace --stats, as tools/prof.sh does for bench.py; table by tools/rocpd_stats.py).
 Usage: python tools/bench_train.py [--iters N] [--model-only | --text | --maps | --trunk [--batchnorm batch [--kernels-only]] [--batch N] | --steps-only K] [--bank-precision fp32|bf16x3]"""
@@ -590,6 +595,88 @@ def trunk_bn_case(n):
     return res
 
 
+def trunk_stem_case(n):
+    from mgnns_amd import harness, synth
+    cfg = synth.CONFIGS["mvsa_multiple_b256"]
+    B = int(sys.argv[sys.argv.index("--batch") + 1]) if "--batch" in sys.argv else cfg.B
+    res = {"case": "trunk_stem_%s" % cfg.name, "B": B, "device": torch.cuda.get_device_name(0), "iters": n}
+
+    def alternately(fa, fb):
+        ta, tb = [], []
+        for _ in range(3):
+            ta.append(timeit(fa, n, warm=2))
+            tb.append(timeit(fb, n, warm=2))
+        return ta, tb
+
+    gen = torch.Generator(device=DEV).manual_seed(3)
+    img = torch.randn(B, 3, 448, 448, device=DEV, generator=gen)
+    w = torch.randn(64, 3, 7, 7, device=DEV, generator=gen) * 0.1
+    v = torch.rand(64, device=DEV, generator=gen) + 0.5
+    folded = ops.conv_fold_bn(w, None, (v, v - 1.0, v - 1.0, v, 1e-5), stem=True)
+    raw = ops.conv_fold_bn(w, None, None, stem=True)
+    y0 = ops.stem_conv7(img, *folded)
+    g_y = torch.randn(B, 112, 112, 64, device=DEV, generator=gen).to(torch.bfloat16)
+    g_y0 = ops.maxpool3x3s2_bwd_nhwc(y0, g_y, relu_mask=True)
+    kern = {}
+    # the pool's backward is a stream: y0 read, g_y read, g_y0 written
+    moved = y0.numel() * 2 + g_y.numel() * 2 + y0.numel() * 2
+    src = torch.empty(moved // 2, dtype=torch.uint8, device=DEV)
+    dst = torch.empty_like(src)
+    tk, tc = alternately(lambda: ops.maxpool3x3s2_bwd_nhwc(y0, g_y, relu_mask=True), lambda: dst.copy_(src))
+    kern["maxpool3x3s2_bwd_relu_mask"] = {"us": round(min(tk), 1), "copy_us": round(min(tc), 1), "ratio": round(min(tk) / min(tc), 3),
+                                          "moved_MB": round(moved / 1e6, 1), "TB/s": round(moved / min(tk) / 1e6, 2),
+                                          "runs_us": [round(t, 1) for t in tk], "copy_runs_us": [round(t, 1) for t in tc]}
+    del src, dst
+    # stem_wgrad against the one other pixel-contracted weight gradient, at layer4.0.conv2's geometry
+    x4 = torch.randn(B, 28, 28, 512, device=DEV, generator=gen).to(torch.bfloat16)
+    dy4 = torch.randn(B, 14, 14, 512, device=DEV, generator=gen).to(torch.bfloat16)
+    flop_s = 2.0 * B * 224 * 224 * 64 * 147
+    flop_4 = 2.0 * B * 14 * 14 * 512 * 512 * 9
+    ts, t4 = alternately(lambda: ops.stem_wgrad(img, g_y0), lambda: ops.conv_wgrad_bf16_nhwc(x4, dy4, 3, 2, 1))
+    by = img.numel() * 4 + g_y0.numel() * 2
+    kern["stem_wgrad"] = {"us": round(min(ts), 1), "GFLOP": round(flop_s / 1e9, 1), "pct_bf16_peak": round(100.0 * flop_s / min(ts) / 1e6 / (BF16_PEAK / 1e12), 2),
+                          "alg_MB": round(by / 1e6, 1), "TB/s": round(by / min(ts) / 1e6, 2),
+                          "layer4_0_conv2_wgrad_us": round(min(t4), 1), "layer4_0_conv2_GFLOP": round(flop_4 / 1e9, 1),
+                          "layer4_0_conv2_pct_bf16_peak": round(100.0 * flop_4 / min(t4) / 1e6 / (BF16_PEAK / 1e12), 2),
+                          "ratio": round(min(ts) / min(t4), 3), "runs_us": [round(t, 1) for t in ts], "layer4_0_conv2_runs_us": [round(t, 1) for t in t4]}
+    del x4, dy4
+    tf, tr = alternately(lambda: ops.stem_conv7(img, *folded), lambda: ops.stem_conv7(img, *raw, raw=True))
+    kern["stem_conv7"] = {"folded_us": round(min(tf), 1), "raw_us": round(min(tr), 1)}
+    res["kernels"] = kern
+    del img, y0, g_y, g_y0
+    if "--kernels-only" in sys.argv:
+        return res
+
+    pmi, count = synth.synth_pmi(cfg.V, seed=2)
+    A_obj, A_place = harness.synthetic_adjacencies(cfg)
+    inp = synth.make_inputs(cfg, B=B, seed=7, pmi=pmi)
+    model = harness.build_model(cfg, pmi, count, A_obj, A_place, inp["label_query"], DEV, trunks=True).train().freeze_text_encoders()
+    imgs = list(harness.call_args(inp, DEV))
+    G = torch.randn(B, cfg.NL, device=DEV)
+    g = torch.Generator().manual_seed(1)
+    for i in (3, 4):
+        imgs[i] = torch.randn(B, 3, 448, 448, generator=g).to(DEV)
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        torch.autograd.backward(model(*imgs), G)
+
+    for mode in ("frozen", "batch"):
+        ta, tb = [], []
+        for _ in range(3):
+            model.unfreeze_trunks(4, batchnorm=mode)
+            ta.append(timeit(step, n, warm=1))
+            model.unfreeze_trunks(4, batchnorm=mode, stem=True)
+            tb.append(timeit(step, n, warm=1))
+        torch.cuda.reset_peak_memory_stats()
+        step()
+        torch.cuda.synchronize()
+        res["step_%s" % mode] = {"stages4_us": round(min(ta), 1), "stages4_stem_us": round(min(tb), 1), "difference_us": round(min(tb) - min(ta), 1),
+                                 "ratio": round(min(tb) / min(ta), 3), "peak_GB_with_stem": round(torch.cuda.max_memory_allocated() / 1e9, 2),
+                                 "runs_us": {"stages4": [round(t, 1) for t in ta], "stages4_stem": [round(t, 1) for t in tb]}}
+    return res
+
+
 def steps_only(k):
     from mgnns_amd import harness, synth
     cfg = synth.CONFIGS["mvsa_multiple_b256"]
@@ -619,6 +706,9 @@ def main():
         return
     if "--maps" in sys.argv:
         print(json.dumps(maps_case(n)), flush=True)
+        return
+    if "--trunk" in sys.argv and "--stem" in sys.argv:
+        print(json.dumps(trunk_stem_case(n)), flush=True)
         return
     if "--trunk" in sys.argv and "--batchnorm" in sys.argv:
         mode = sys.argv[sys.argv.index("--batchnorm") + 1]
