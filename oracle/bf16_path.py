@@ -282,7 +282,7 @@ def label_tail(p, chan, pooled, G, Q, n_heads=5, next_w=None, next_b=None, terms
     o = (torch.softmax(e, dim=-1) * V.view(B, 1, n_heads, dh)).reshape(B, NLQ, hid)
     w5, wfc = _d(p[chan + "_linear_5.weight"]), _d(p[a + "fc.weight"])
     wc, bc = w5 @ wfc, w5 @ _d(p[a + "fc.bias"]) + _d(p[chan + "_linear_5.bias"])
-    y = rd(rd(o) @ rd(wc).t() + bc).reshape(B, -1)
+    y = rd(rd(o) @ rd(wc).t() + bc).reshape(B, NLQ * wc.shape[0])           # (an empty batch cannot be reshaped through -1)
     out = y @ rd(p[chan + "_x_linear.weight"]).t() + _d(p[chan + "_x_linear.bias"])
     if next_w is None:
         return out, None

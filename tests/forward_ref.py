@@ -102,6 +102,29 @@ def gen_adj(A):
     return (A * d[None, :]).t() * d[None, :]
 
 
+def label_gcn(A, inp, w1, w2, query=None):
+    """One channel's label GCN (restatement.image_gcn): adj = gen_adj(A), G = adj @ (LeakyReLU_0.2(adj @ (inp @ w1)) @ w2) with the
+    GraphConvolution weights in their [in, out] layout.  query = (label_query, w_q.weight, w_q.bias or None) adds
+    Q = w_q(label_query).  -> (G [C, N2], Q or None)."""
+    adj = gen_adj(A)
+    x1 = torch.nn.functional.leaky_relu(adj @ (inp @ w1), 0.2)
+    G = adj @ (x1 @ w2)
+    return G, (None if query is None else linear(query[0], query[1], query[2]))
+
+
+def label_tail(pooled, G, Q, n_heads, w, next_q=None):
+    """The channel tail behind the label GCN, map by map as the model runs it: x = max over parts(pooled) . G^T, K / V, the element-wise
+    label attention, fc, linear_5, flatten, x_linear, and the next stack's query.  pooled [B, parts, K]; Q [NLQ, hid] the projected label
+    query; w: dict with wk, bk, wv, bv, wfc, bfc, w5, b5, wxl, bxl; next_q = (weight, bias or None).  -> (out [B, n_out], next or None).
+    The float64 reference of the fused kernels is oracle/bf16_path.label_tail (tests/test_label_edges_cpu.py pins this one to it); this
+    one follows the dtype of its inputs, so its float32 evaluation gives the rounding error a bound may be derived from."""
+    x = pooled.max(dim=1).values @ G.t()
+    o = label_attn_core(Q, linear(x, w["wk"], w["bk"]), linear(x, w["wv"], w["bv"]), n_heads)
+    y = linear(linear(o, w["wfc"], w["bfc"]), w["w5"], w["b5"]).reshape(x.shape[0], Q.shape[0] * w["w5"].shape[0])
+    out = linear(y, w["wxl"], w["bxl"])
+    return out, (None if next_q is None else linear(out, next_q[0], next_q[1]))
+
+
 def embedding(idx, table):
     return table[idx]
 

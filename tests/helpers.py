@@ -240,3 +240,27 @@ def check_plan(plan, mask, max_rows=128, max_samples=16, align=8):
         assert r == rows, "group at sample %d says %d rows, its samples take %d" % (first, rows, r)
     assert (seen == 1).all(), "samples not in exactly one group: %s" % np.nonzero(seen != 1)[0][:8]
     return groups, off, lv
+
+
+# ---- label-channel edge sweeps (tests/label_edge_cases.py, tests/test_label_edges_gpu.py, tests/test_label_edges_cpu.py) ---------------
+def label_tail_case(C, NLQ, heads, dh, N5, n_out, K_pool, parts, HK_next, B, next_bias=True, chan="edge"):
+    """One channel tail of arbitrary shape -> dict(p, G, Q, pooled, next_w, next_b, heads, chan): p holds the parameters under the names
+    oracle/bf16_path.label_tail expects (`chan`_attention.w_k / w_v / fc, `chan`_linear_5, `chan`_x_linear); G [C, K_pool] the label GCN's
+    output, Q [NLQ, hid] the projected label query, pooled [B, parts, K_pool] non-negative (so the max over the parts matters), next_w
+    [HK_next, n_out] / next_b [HK_next] the next stack's query projection (None without one; next_b zeros when next_bias is false).
+    Weights are scaled by their fan-in, so every stage and the output stay O(1).  float32 tensors, seeded by the shape."""
+    hid = heads * dh
+    rs = np.random.RandomState((C * 7919 + NLQ * 104729 + hid * 1299709 + N5 * 15485863 + n_out * 31 + K_pool * 17 + parts * 5 + HK_next * 3 + B) % (2 ** 31))
+    w = lambda n, k: torch.from_numpy((rs.standard_normal((n, k)) / np.sqrt(k)).astype(np.float32))
+    b = lambda n: torch.from_numpy((0.5 * rs.standard_normal(n)).astype(np.float32))
+    a = chan + "_attention."
+    p = {a + "w_k.weight": w(hid, C), a + "w_k.bias": b(hid), a + "w_v.weight": w(hid, C), a + "w_v.bias": b(hid),
+         a + "fc.weight": w(hid, hid), a + "fc.bias": b(hid), chan + "_linear_5.weight": w(N5, hid), chan + "_linear_5.bias": b(N5),
+         chan + "_x_linear.weight": w(n_out, NLQ * N5), chan + "_x_linear.bias": b(n_out)}
+    case = {"p": p, "G": w(C, K_pool), "Q": torch.from_numpy(rs.standard_normal((NLQ, hid)).astype(np.float32)),
+            "pooled": torch.from_numpy(np.maximum(rs.standard_normal((B, parts, K_pool)), 0).astype(np.float32)),
+            "next_w": None, "next_b": None, "heads": heads, "chan": chan}
+    if HK_next:
+        case["next_w"] = w(HK_next, n_out)
+        case["next_b"] = b(HK_next) if next_bias else torch.zeros(HK_next)
+    return case

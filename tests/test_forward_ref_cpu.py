@@ -27,6 +27,25 @@ def test_gen_adj_matches_the_adjacency_goldens():
             assert np.array_equal(a64.numpy() != 0, g[key + "_adj"] != 0)
 
 
+def test_label_gcn_matches_the_image_gcn_goldens():
+    g = H.load_golden("image_gcn.npz")
+    adj = H.load_golden("adjacency.npz")
+    p = H.params_for({"gc1.weight": (300, 1024), "gc2.weight": (1024, 2048)})
+    proj = GI.gcn_projection()
+    rs = np.random.RandomState(11)
+    lq, wq, bq = rs.standard_normal((7, 300)), 0.05 * rs.standard_normal((300, 300)), rs.standard_normal(300)
+    for tag, key in (("object", "object_t04"), ("place", "place_t03")):
+        X, pooled = GI.image_gcn_case(tag)
+        for G, Q in _both(lambda c: F.label_gcn(c(adj[key + "_A"]), c(X), c(p["gc1.weight"]), c(p["gc2.weight"]), (c(lq), c(wq), c(bq)))):
+            assert H.relerr(G @ torch.from_numpy(proj).to(G.dtype), g[tag + "_Gproj"]) < 1e-5
+            assert H.relerr(torch.from_numpy(pooled).to(G.dtype) @ G.t(), g[tag + "_x"]) < 1e-5
+            assert H.maxabs(G, R.image_gcn(torch.from_numpy(adj[key + "_A"]), torch.from_numpy(X), p["gc1.weight"], p["gc2.weight"])) \
+                < 1e-5 * float(G.abs().max())
+            assert H.maxabs(Q, torch.nn.functional.linear(torch.from_numpy(lq), torch.from_numpy(wq), torch.from_numpy(bq))) < 1e-5
+        G0, none = F.label_gcn(*(torch.from_numpy(a) for a in (adj[key + "_A"], X)), p["gc1.weight"], p["gc2.weight"])
+        assert none is None and G0.dtype == torch.float32 and tuple(G0.shape) == (X.shape[0], 2048)
+
+
 def test_layer_norm_matches_the_golden():
     g = H.load_golden("layernorm.npz")
     p = H.params_for({"ln.gamma": (300,), "ln.beta": (300,)})
