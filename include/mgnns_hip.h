@@ -668,6 +668,10 @@ int mgnns_label_attn_train_bwd(const float* dx, const float* Q, const float* K, 
  * node) for the backward.  Tie rule: the smallest source position whose fp32 product equals the fp32 max.
  * mgnns_textgcn_train_bwd: from dy [B, D] the per-document partials: R [B, Tm, D] rows keyed by keyR [B, Tm] (the token id of
  * the source, -1 = none) for node_hidden; Eg [B, Tm, 2 ngram + 1] keyed by keyE (edge id, -1 = none) for seq_edge_w.
+ * mgnns_textgcn_train_supported: whether a training step takes the shape (a host function, 1 / 0): D in 1..320, ngram in 0..15,
+ * Tm (2 ngram + 1) < 32768 and the BACKWARD's LDS need at Tm = min(T, max_length) -- Tm (28 (2 ngram + 1) + 12) + 16 bytes -- within
+ * 160 KiB (Tm <= 4095 at ngram 0, 186 at ngram 15).  mgnns_textgcn_train_fwd requires it, so a step that could not finish is refused
+ * before anything is launched (added under ABI 26 without a bump: an addition).
  */
 #define MGNNS_DROP_LSTM       5
 #define MGNNS_DROP_TEXT_GCN   6
@@ -687,6 +691,7 @@ int mgnns_bilstm_train_unpack_drop(const float* dx, const int32_t* pack_pos, int
 int mgnns_gather_rows(const float* src, int n_src, int K, const int32_t* idx, int64_t M, float* dst, mgnns_stream_t stream);
 int mgnns_keyed_row_sum(const int64_t* sorted_keys, const int64_t* perm, int64_t M, const float* values, int D, int64_t n_values,
                         int64_t skip_below, float* out, int64_t K, mgnns_stream_t stream);
+int mgnns_textgcn_train_supported(int T, int D, int ngram, int max_length);
 int mgnns_textgcn_train_fwd(const int64_t* tok, int B, int T, const float* node_hidden, int V, int D, const float* edge_w,
                             int n_edge_w, const int32_t* pmi_row_ptr, const int32_t* pmi_col, const int32_t* pmi_eid, int ngram,
                             int max_length, uint64_t seed, float rate, float* out, float* presum, int16_t* win,

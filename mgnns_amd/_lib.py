@@ -126,6 +126,7 @@ SIGNATURES = {
     "mgnns_bilstm_train_unpack_drop": [_P, _P, _L, _I, _I, _U64, _F, _P, _P],
     "mgnns_gather_rows": [_P, _I, _I, _P, _L, _P, _P],
     "mgnns_keyed_row_sum": [_P, _P, _L, _P, _I, _L, _L, _P, _L, _P],
+    "mgnns_textgcn_train_supported": [_I, _I, _I, _I],
     "mgnns_textgcn_train_fwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _U64, _F, _P, _P, _P, _P],
     "mgnns_textgcn_train_bwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _U64, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "mgnns_comm_unique_id": [_P, _SZ],

@@ -574,15 +574,30 @@ static int tg_check(const char* who, int B, int T, int V, int D, int n_edge_w, i
     return 0;
 }
 
+// The shape limits of a text GCN training STEP as a predicate: the backward's (its per-wave slot sums make it the stricter of the two
+// kernels), so a shape the forward takes is one the backward takes too.
+extern "C" int mgnns_textgcn_train_supported(int T, int D, int ngram, int max_length) {
+    if (!(T > 0 && D > 0 && D <= TG_THREADS && ngram >= 0 && ngram <= 15 && max_length > 0)) return 0;
+    const int Tm = T < max_length ? T : max_length;
+    const int W = 2 * ngram + 1;
+    if ((long)Tm * W >= 32768) return 0;
+    return tg_lds(Tm, W, D, false, true) <= 160 * 1024 ? 1 : 0;
+}
+
 extern "C" int mgnns_textgcn_train_fwd(const int64_t* tok, int B, int T, const float* node_hidden, int V, int D, const float* edge_w,
                                        int n_edge_w, const int32_t* pmi_row_ptr, const int32_t* pmi_col, const int32_t* pmi_eid,
                                        int ngram, int max_length, uint64_t seed, float rate, float* out, float* presum,
                                        int16_t* win, mgnns_stream_t stream) {
-    MG_REQUIRE(tok && node_hidden && edge_w && pmi_row_ptr && pmi_col && out && presum && win, "mgnns_textgcn_train_fwd: null pointer");
     MG_REQUIRE(rate >= 0.f && rate <= 1.f, "mgnns_textgcn_train_fwd: dropout rate %g outside [0, 1]", (double)rate);
     int Tm, stage;
     size_t lds;
+    // (the shape first: at max_length = 0 the winners are an empty buffer, and the message should name max_length, not a pointer)
     if (int rc = tg_check("mgnns_textgcn_train_fwd", B, T, V, D, n_edge_w, ngram, max_length, false, &Tm, &lds, &stage)) return rc;
+    MG_REQUIRE(tok && node_hidden && edge_w && pmi_row_ptr && pmi_col && out && presum && win, "mgnns_textgcn_train_fwd: null pointer");
+    // a step this forward begins must be one the backward can finish: refuse here, before anything is launched
+    MG_REQUIRE(mgnns_textgcn_train_supported(T, D, ngram, max_length),
+               "mgnns_textgcn_train_fwd: min(T, max_length)=%d: the backward needs %zu B of LDS (> 160 KiB)", Tm,
+               tg_lds(Tm, 2 * ngram + 1, D, false, true));
     MG_DYN_LDS(tg_train_fwd_kernel, 160 * 1024);
     hipLaunchKernelGGL(tg_train_fwd_kernel, dim3(B), dim3(TG_THREADS), lds, (hipStream_t)stream, tok, T, Tm, node_hidden, V, D, edge_w,
                        n_edge_w, pmi_row_ptr, pmi_col, pmi_eid, ngram, stage, seed, rate, out, presum, win);

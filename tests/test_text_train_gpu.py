@@ -5,7 +5,6 @@ Gate: 1e-4 of each tensor's largest magnitude."""
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from mgnns_amd import ops, synth
 from mgnns_amd import train as T_
@@ -13,6 +12,7 @@ from mgnns_amd.pmi import PmiCsr
 from tests import dropout_ref as DR
 from tests import test_model_train_gpu as MT
 from tests.test_text_train_cpu import lstm_keep, textgcn_keep, tg_winners
+from tests.text_train_edge_cases import lstm_oracle, tg_oracle      # the oracles, shared with the edge sweep
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -27,38 +27,6 @@ def close(got, ref, what, tol=1e-4):
 
 
 # ---- BiLSTM -------------------------------------------------------------------------------------------------------------------
-def _lstm_dir(x, lens, wih, whh, bih, bhh, reverse):
-    """One direction over padded x [B, T, K] with packed semantics: a chain runs over its own length only."""
-    B, T_len, _ = x.shape
-    h = x.new_zeros(B, whh.shape[1])
-    c = x.new_zeros(B, whh.shape[1])
-    outs = [None] * T_len
-    for t in (range(T_len - 1, -1, -1) if reverse else range(T_len)):
-        m = (lens > t).to(x.dtype).unsqueeze(1)
-        z = x[:, t] @ wih.T + bih + h @ whh.T + bhh
-        i, f, g, o = z.chunk(4, 1)
-        c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
-        h2 = torch.sigmoid(o) * torch.tanh(c2)
-        c = m * c2 + (1 - m) * c
-        h = m * h2 + (1 - m) * h
-        outs[t] = h2 * m
-    return torch.stack(outs, 1)
-
-
-def lstm_oracle(tok, lens, emb, flat, seed, rate, num_layers=2):
-    """fp64 bank of the packed 2-layer BiLSTM; emb and flat (16 tensors, (w_ih, w_hh, b_ih, b_hh) per (layer, direction)) are fp64
-    leaves.  Embedding with padding_idx 0 (row 0 gets no gradient)."""
-    x = F.embedding(tok, emb, padding_idx=0)
-    B, T_len = tok.shape
-    for layer in range(num_layers):
-        w = flat[8 * layer:8 * layer + 8]
-        x = torch.cat([_lstm_dir(x, lens, *w[:4], False), _lstm_dir(x, lens, *w[4:], True)], 2)
-        if layer + 1 < num_layers:
-            keep = torch.from_numpy(lstm_keep(seed, rate, B, T_len, 2 * HID))
-            x = x * keep.double() / (1.0 - rate)
-    return x
-
-
 def _lstm_case(B, T_len, pattern, rate, V=500, seed=11):
     rs = np.random.RandomState(seed + B + T_len)
     if pattern == "full":
@@ -133,26 +101,6 @@ class _TG(torch.nn.Module):
             self.node_hidden.weight.copy_(torch.from_numpy(rs.randn(V, D).astype(np.float32)))
             self.seq_edge_w.weight.copy_(torch.from_numpy((rs.randn(count, 1) * 1.3 + 0.2).astype(np.float32)))
         self.edges_matrix, self.ngram, self.max_length = PmiCsr.coerce(pmi), ngram, max_length
-
-
-def tg_oracle(tok, nh32, ew32, pmi, ngram, max_length, presum, seed, rate):
-    """fp64 output and (node_hidden, edge weight) gradient leaves: winners from the fp32 products (tests/test_text_train_cpu.py),
-    ReLU signs from the kernel's fp32 sum."""
-    nh = torch.from_numpy(nh32).double().requires_grad_()
-    ew = torch.from_numpy(ew32).double().requires_grad_()
-    B, D = tok.shape[0], nh32.shape[1]
-    keep = torch.from_numpy(textgcn_keep(seed, rate, B, D)).double() / (1.0 - rate)
-    rows = []
-    for b in range(B):
-        nodes, win, eid, t = tg_winners(tok[b], nh32, ew32, pmi, ngram, max_length)
-        s = nh.new_zeros(D)
-        for k in range(len(nodes)):
-            src = torch.from_numpy(np.asarray(t, np.int64)[win[k]])
-            s = s + ew[torch.from_numpy(eid[k])] * nh[src, torch.arange(D)]
-        rows.append(s)
-    y = torch.stack(rows) * keep
-    sign = (presum.cpu() * keep.float() > 0).double()
-    return y * sign, nh, ew
 
 
 def _docs(B, T_len, V, rs):
