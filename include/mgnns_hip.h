@@ -850,6 +850,29 @@ int mgnns_stem_wgrad(const float* img, const void* g, int B, int H, int W, float
 int mgnns_maxpool3x3s2_nhwc_bwd(const void* x, const void* gy, int B, int H, int W, int C, int relu_mask, void* gx,
                                 mgnns_stream_t stream);
 
+/* ---- f4 (input half): the reference's image transforms in front of the trunks (utils/util.py:67-146 Warp / MultiScaleCrop,
+ * then RandomHorizontalFlip, ToTensor, Normalize; csrc/image_prep.hip).  Added under ABI 26 without a bump: the
+ * change is additive.  One launch turns a batch of decoded uint8 images of DIFFERENT sizes into the fp32 [B,3,S_h,S_w] tensor
+ * mgnns_stem_conv7_fwd reads: crop -> Pillow's 8-bit BILINEAR resize (integer arithmetic: horizontal pass over every source
+ * row into uint8, then the vertical pass, each clip8((2^21 + sum k_j * pixel_j) >> 22)) -> mirror -> lut[c][v].  Integer
+ * accumulation in a fixed order and no atomics: results are bit-identical from call to call.
+ *  pixels      packed uint8 HWC (3 channels) images; pixel_bytes = size of the buffer.  Every image starts on a 16-byte boundary
+ *              and ends at least 16 bytes before the end of the buffer (rows are fetched with 16-byte loads).
+ *  desc        [B,10] int64 per image: byte offset, source height, source width, crop x, crop y, crop width, crop height,
+ *              flip (0 / 1), index of the horizontal plan, index of the vertical plan.  1 <= height, width <= 8192; the crop
+ *              lies inside the image.  The kernel re-checks a descriptor and fills the image's output with NaN if it is bad
+ *              (the host wrapper refuses it before the launch; a descriptor buffer can change under a captured graph).
+ *  plan_table  [n_plans,4] int32 per plan: offset into plan_data (in int32s), taps per output (ksize), input extent, output
+ *              extent.  plan_data at that offset: (first source index, tap count) per output, then ksize int32 taps per
+ *              output (22 fractional bits; Pillow's precompute_coeffs + normalize_coeffs_8bpc, built in float64 on the host).
+ *              A horizontal plan's extents are (crop width, S_w), a vertical plan's (crop height, S_h).
+ *  lut         [3,256] fp32: (v / 255 - mean_c) / std_c as torch computes it.
+ *  out         [B,3,S_h,S_w] fp32, 1 <= S_h, S_w <= 1024.  B == 0 is a no-op.
+ */
+int mgnns_image_prep_fwd(const void* pixels, size_t pixel_bytes, const int64_t* desc, int B, const int32_t* plan_table,
+                         int n_plans, const int32_t* plan_data, size_t plan_ints, const float* lut, int S_h, int S_w,
+                         float* out, mgnns_stream_t stream);
+
 /* ---- measurement aid: a one-thread kernel that writes the GPU's constant-rate real-time counter (s_memrealtime,
  * 100 MHz) into slots[idx] when the stream reaches it.  Captured into the forward's hipGraph it gives the REAL
  * timeline of the concurrent branches of a replay (rocprofv3 serialises / perturbs them): tools/graph_timeline.py.

@@ -92,6 +92,7 @@ SIGNATURES = {
     "mgnns_stem_conv7_raw_fwd": [_P, _I, _I, _I, _P, _P, _P],
     "mgnns_stem_wgrad": [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P],
     "mgnns_maxpool3x3s2_nhwc_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "mgnns_image_prep_fwd": [_P, _SZ, _P, _I, _P, _I, _P, _SZ, _P, _I, _I, _P, _P],
     "mgnns_label_gcn_supported": [_I, _I, _I, _I, _I],
     "mgnns_label_tail_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
     "mgnns_label_tail_bf16_supported": [_I, _I, _I, _I, _I, _I, _I, _I, _I],

@@ -1739,6 +1739,91 @@ def maxpool3x3s2_bwd_nhwc(x, g_y, relu_mask=False):
     return g_x
 
 
+# ---- f4, input half: crop + Pillow's bilinear resize + flip + ToTensor + Normalize (csrc/image_prep.hip) -------------------------
+IMAGE_DESC = 10           # int64 per image: offset, height, width, crop x, y, w, h, flip, horizontal plan, vertical plan
+IMAGE_MAX_EXTENT = 8192
+IMAGE_MAX_SIZE = 1024
+
+
+def _chk_host(t, name, dtype, cols):
+    if not torch.is_tensor(t):
+        raise TypeError("%s must be a torch tensor" % name)
+    if t.is_cuda:
+        raise ValueError("%s is the HOST copy that is validated before the launch; got a tensor on %s" % (name, t.device))
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("%s must be [n,%d], got shape %s" % (name, cols, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return t
+
+
+def image_prep(pixels, desc, desc_dev, plan_table, plan_table_dev, plan_data, lut, size_h, size_w, out=None):
+    """A batch of decoded uint8 HWC images of different sizes -> [B,3,size_h,size_w] fp32, what stem_conv7 reads: crop, Pillow's 8-bit
+    bilinear resize, mirror, lut[c][v], in one launch (include/mgnns_hip.h, "f4 (input half)").  pixels: uint8 [n] on the GPU, every
+    image on a 16-byte boundary and at least 16 bytes of slack behind the last.  desc [B,10] int64 and plan_table [P,4] int32 are HOST
+    tensors, validated here; desc_dev / plan_table_dev are their device copies, which the kernel reads (the caller stages them: this
+    function copies nothing and does not synchronise, so it can be captured into a hipGraph over static buffers -- the validation
+    then covers the capture's call only, and the kernel's own re-check turns a bad descriptor into NaN).  plan_data: int32 [m] on
+    the GPU; lut [3,256] fp32 on the GPU."""
+    _chk(pixels, "pixels", torch.uint8, 1)
+    _chk_host(desc, "desc", torch.int64, IMAGE_DESC)
+    _chk_host(plan_table, "plan_table", torch.int32, 4)
+    _chk(desc_dev, "desc_dev", torch.int64, 2)
+    _chk(plan_table_dev, "plan_table_dev", torch.int32, 2)
+    _chk(plan_data, "plan_data", torch.int32, 1)
+    _chk(lut, "lut", ndim=2)
+    size_h, size_w = int(size_h), int(size_w)
+    if not (1 <= size_h <= IMAGE_MAX_SIZE and 1 <= size_w <= IMAGE_MAX_SIZE):
+        raise ValueError("output size %dx%d unsupported (1..%d)" % (size_h, size_w, IMAGE_MAX_SIZE))
+    B, P = desc.shape[0], plan_table.shape[0]
+    if tuple(desc_dev.shape) != tuple(desc.shape) or tuple(plan_table_dev.shape) != tuple(plan_table.shape):
+        raise ValueError("desc_dev %s / plan_table_dev %s must have the shapes of their host copies %s / %s"
+                         % (tuple(desc_dev.shape), tuple(plan_table_dev.shape), tuple(desc.shape), tuple(plan_table.shape)))
+    if tuple(lut.shape) != (3, 256):
+        raise ValueError("lut must be [3,256], got %s" % (tuple(lut.shape),))
+    for t, name in ((desc_dev, "desc_dev"), (plan_table_dev, "plan_table_dev"), (plan_data, "plan_data"), (lut, "lut")):
+        if t.device != pixels.device:
+            raise ValueError("%s is on %s, pixels on %s" % (name, t.device, pixels.device))
+    if pixels.data_ptr() % 16:
+        raise ValueError("pixels must start on a 16-byte boundary")
+    if P:
+        o, ks, n, S = plan_table.unbind(1)
+        bad = (o < 0) | (ks < 1) | (n < 1) | (n > IMAGE_MAX_EXTENT) | (S < 1) | (o.long() + S.long() * (2 + ks.long()) > plan_data.numel())
+        if bool(bad.any()):
+            raise ValueError("plan_table row %d is not a plan inside plan_data (%d int32): %s"
+                             % (int(bad.nonzero()[0]), plan_data.numel(), plan_table[int(bad.nonzero()[0])].tolist()))
+    if B:
+        off, H, W, cx, cy, cw, ch, flip, ix, iy = desc.unbind(1)
+
+        def refuse(mask, what):
+            if bool(mask.any()):
+                i = int(mask.nonzero()[0])
+                raise ValueError("image %d: %s (descriptor %s)" % (i, what, desc[i].tolist()))
+
+        refuse((H < 1) | (H > IMAGE_MAX_EXTENT) | (W < 1) | (W > IMAGE_MAX_EXTENT), "source extent outside 1..%d" % IMAGE_MAX_EXTENT)
+        refuse((off < 0) | (off % 16 != 0), "offset is not a non-negative multiple of 16")
+        # (written without sums that a huge int64 field could wrap)
+        refuse(off > pixels.numel() - H * W * 3 - 16, "image plus 16 bytes of slack does not fit the pixel buffer of %d bytes" % pixels.numel())
+        refuse((cx < 0) | (cy < 0) | (cw < 1) | (ch < 1) | (cw > W) | (ch > H) | (cx > W - cw) | (cy > H - ch), "crop outside the image")
+        refuse((flip != 0) & (flip != 1), "flip must be 0 or 1")
+        refuse((ix < 0) | (ix >= P) | (iy < 0) | (iy >= P), "plan index outside 0..%d" % (P - 1))
+        pt = plan_table.long()
+        refuse((pt[ix, 2] != cw) | (pt[ix, 3] != size_w), "horizontal plan is not for (crop width, %d)" % size_w)
+        refuse((pt[iy, 2] != ch) | (pt[iy, 3] != size_h), "vertical plan is not for (crop height, %d)" % size_h)
+    if out is None:
+        out = torch.empty(B, 3, size_h, size_w, device=pixels.device, dtype=torch.float32)
+    else:
+        _chk(out, "out", ndim=4)
+        if tuple(out.shape) != (B, 3, size_h, size_w) or out.device != pixels.device:
+            raise ValueError("out must be [%d,3,%d,%d] on %s, got %s on %s" % (B, size_h, size_w, pixels.device, tuple(out.shape), out.device))
+    L = _lib.lib()
+    _launch("mgnns_image_prep_fwd", ("mgnns_image_prep_fwd", size_h, size_w), L.mgnns_image_prep_fwd, _p(pixels), pixels.numel(),
+            _p(desc_dev), B, _p(plan_table_dev), P, _p(plan_data), plan_data.numel(), _p(lut), size_h, size_w, _p(out), _stream())
+    return out
+
+
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------
 _timeline = None          # (slots tensor [uint64 as int64], names list) while tools/graph_timeline.py is recording
 
