@@ -873,6 +873,46 @@ int mgnns_image_prep_fwd(const void* pixels, size_t pixel_bytes, const int64_t* 
                          int n_plans, const int32_t* plan_data, size_t plan_ints, const float* lut, int S_h, int S_w,
                          float* out, mgnns_stream_t stream);
 
+/* ---- f4 (file half): baseline JPEG files -> the packed RGB8 pixel buffer above, bit for bit what Pillow / libjpeg-turbo decode
+ * (csrc/jpeg_parse.hpp, jpeg_entropy.hpp, jpeg_pixels.hpp, jpeg_decode.hip).  Added under ABI 26 without a bump: the
+ * change is additive.
+ *
+ * The parser is host code and makes no GPU call.  It fills, for one file:
+ *  info    24 int32: reason code (0 = accepted; the MG_JPEG_* codes of csrc/jpeg_parse.hpp), detail, width, height, components,
+ *          Y sampling h, v, quantisation-table id x 3, DC table id x 3, AC table id x 3, restart interval, restart markers found,
+ *          independent segments (ceil(nMCU / Ri), or 1), MCUs per row, MCU rows.
+ *  range   2 int64: [begin, end) of the entropy-coded data.
+ *  seg     [seg_cap][2] int64: byte range of every independent segment, as many as fit (info says how many there are).
+ *  tables  the tables in use as the kernels read them (the size getter's bytes, csrc/jpeg_entropy.hpp MgJpegTables): four 8-bit
+ *          quantisation tables in natural order, then four DC and four AC decoding tables (a 9-bit look-ahead table, maxcode,
+ *          valoffset, huffval); unused ones are zero.
+ * It always returns 0 for valid arguments: a file it refuses is a reason code, not an error.
+ */
+size_t mgnns_jpeg_tableset_bytes(void);
+int mgnns_jpeg_parse(const void* data, size_t bytes, int max_extent, int32_t* info, int64_t* range, int64_t* seg, size_t seg_cap,
+                     void* tables);
+
+/* Decode a batch: `stages` is a mask of 1 = zero the coefficient workspace and Huffman-decode (one lane per segment), 2 =
+ * dequantise + jidctint 8x8 ("islow") into component planes, 4 = "fancy" chroma upsampling + YCbCr -> RGB + crop into the pixel
+ * buffer (7 = all; the split exists for measurements).  All launches go on `stream`; nothing synchronises.
+ *  data      the files' bytes, anywhere in one buffer.
+ *  img       [B,16] int64 per image: kind (1 = decode, 0 = its pixels are staged by the caller and it is skipped), width, height,
+ *            components, Y sampling h, v, MCUs per row, MCU rows, quantisation / DC / AC table ids (one byte per component
+ *            each), table set, offset of its coefficients (int16 elements, a multiple of 64), of its planes (bytes, a multiple
+ *            of 64), of its pixels (bytes, a multiple of 16) and the end of its pixels' padding, which is zeroed (at most 256
+ *            bytes behind the image).  Coefficients and planes hold the components one after the other at MCU-padded block counts.
+ *  seg       [S,5] int64 per segment: image, [begin, end) in `data`, first MCU, MCUs.
+ *  tables    n_sets table sets (above).
+ *  status    [S] int32, one word per segment: 0 ok, 1 ran out of data, 2 invalid Huffman code, 3 coefficient index above 63,
+ *            4 a record the kernel refused on its own check.  A status never stops a kernel; the caller reads the words.
+ *  max_blocks / max_pixels   the largest block count (all components) and pixel count of a decoded image: they size the grids.
+ * B <= 65535.  B == 0 or S == 0 is a no-op.
+ */
+int mgnns_jpeg_decode_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
+                          const void* tables, int n_sets, void* coef, size_t coef_elems, void* planes, size_t plane_bytes,
+                          void* pixels, size_t pixel_bytes, long long max_blocks, long long max_pixels, int stages,
+                          int32_t* status, mgnns_stream_t stream);
+
 /* ---- measurement aid: a one-thread kernel that writes the GPU's constant-rate real-time counter (s_memrealtime,
  * 100 MHz) into slots[idx] when the stream reaches it.  Captured into the forward's hipGraph it gives the REAL
  * timeline of the concurrent branches of a replay (rocprofv3 serialises / perturbs them): tools/graph_timeline.py.

@@ -93,6 +93,8 @@ SIGNATURES = {
     "mgnns_stem_wgrad": [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P],
     "mgnns_maxpool3x3s2_nhwc_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
     "mgnns_image_prep_fwd": [_P, _SZ, _P, _I, _P, _I, _P, _SZ, _P, _I, _I, _P, _P],
+    "mgnns_jpeg_parse": [_P, _SZ, _I, _P, _P, _P, _SZ, _P],
+    "mgnns_jpeg_decode_fwd": [_P, _SZ, _P, _I, _P, _I, _P, _I, _P, _SZ, _P, _SZ, _P, _SZ, _c.c_longlong, _c.c_longlong, _I, _P, _P],
     "mgnns_label_gcn_supported": [_I, _I, _I, _I, _I],
     "mgnns_label_tail_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
     "mgnns_label_tail_bf16_supported": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
@@ -170,6 +172,7 @@ SIZE_GETTERS = {
     "mgnns_bn_stats_workspace_bytes": [_I, _I],
     "mgnns_bn_backward_workspace_bytes": [_I, _I],
     "mgnns_stem_wgrad_workspace_bytes": [_I, _I, _I],
+    "mgnns_jpeg_tableset_bytes": [],
 }
 
 _lib = None

@@ -1,0 +1,222 @@
+// f4 (file half): baseline JPEG files -> the packed RGB8 pixel buffer image_prep.hip reads, bit for bit what Pillow / libjpeg-turbo
+// decode.  The host parses the markers (jpeg_parse.hpp: no GPU call) and ships the compressed bytes, one record per
+// image, one per independent segment and the distinct table sets; three launches on the caller's stream do the rest:
+//   1. jpeg_entropy_kernel   one LANE per segment (a whole scan, or the stretch between two restart markers): Huffman decoding is
+//                            serial within a segment, so the parallelism is across segments.  Quantised coefficients go as int16
+//                            [block][64] in natural order into a zeroed workspace; one status word per segment.
+//   2. jpeg_idct_kernel      dequantise + libjpeg's jidctint 8x8: eight threads per block, a column each, then a row each
+//                            -> uint8 component planes at block-padded size.
+//   3. jpeg_colour_kernel    one thread per pixel: "fancy" h2v1 / h2v2 chroma upsampling, YCbCr -> RGB, crop to W x H, interleaved
+//                            RGB8 at the image's 16-byte-aligned offset; the padding behind the image is zeroed.
+// The decoder body and the sample arithmetic live in jpeg_entropy.hpp / jpeg_pixels.hpp as host + device functions: the CPU run of
+// tools/dev/jpeg_host_check.cpp under the sanitizers executes the same code.  Every record is re-checked on the device (a record
+// buffer can change under a captured graph): a bad one gives status MG_JPEG_SEG_BAD_RECORD and writes nothing.
+#include "common.hpp"
+#include "jpeg_parse.hpp"
+#include "jpeg_pixels.hpp"
+
+namespace {
+
+constexpr int IMG = 16;         // int64 per image record
+constexpr int SEG = 5;          // int64 per segment record
+constexpr int MAXEXT = 8192;
+constexpr int NT = 256;
+constexpr int IDCT_BLOCKS = NT / 8;
+constexpr int ENT_NT = 64;      // the entropy kernel's workgroup: one wave, of which the first `lanes` lanes decode a segment each
+constexpr int LDS_SETS = 2;     // table sets kept in LDS (11 648 bytes each)
+static_assert(sizeof(MgJpegTables) % 16 == 0, "table sets are copied 16 bytes at a time");
+
+struct Img {
+    int kind, W, H, ncomp, hs, vs, mcux, mcuy, set;
+    int tq[3], td[3], ta[3];
+    long long coef_off, plane_off, pix_off, pix_end;
+    long long nmcu, blocks0, blocks;      // MCUs; blocks of component 0; blocks of all components
+};
+
+__device__ __forceinline__ bool load_img(const int64_t* __restrict__ r, int n_sets, size_t coef_elems, size_t plane_bytes,
+                                         size_t pixel_bytes, Img& m) {
+    const long long kind = r[0], W = r[1], H = r[2], nc = r[3], hs = r[4], vs = r[5], mcux = r[6], mcuy = r[7], set = r[11];
+    m.coef_off = r[12], m.plane_off = r[13], m.pix_off = r[14], m.pix_end = r[15];
+    if (kind != 0 && kind != 1) return false;
+    if (W < 1 || W > MAXEXT || H < 1 || H > MAXEXT) return false;
+    if (m.pix_off < 0 || (m.pix_off & 15) || m.pix_end < m.pix_off || (unsigned long long)m.pix_end > pixel_bytes ||
+        W * H * 3 > m.pix_end - m.pix_off)
+        return false;
+    m.kind = (int)kind, m.W = (int)W, m.H = (int)H;
+    if (kind == 0) return true;                 // pixels staged by the host: nothing else is read
+    if (!((nc == 1 && hs == 1 && vs == 1) || (nc == 3 && ((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))))) return false;
+    if (mcux != (W + 8 * hs - 1) / (8 * hs) || mcuy != (H + 8 * vs - 1) / (8 * vs)) return false;
+    if (set < 0 || set >= n_sets) return false;
+    m.ncomp = (int)nc, m.hs = (int)hs, m.vs = (int)vs, m.mcux = (int)mcux, m.mcuy = (int)mcuy, m.set = (int)set;
+    m.nmcu = mcux * mcuy;
+    m.blocks0 = m.nmcu * hs * vs;
+    m.blocks = nc == 1 ? m.blocks0 : m.blocks0 + 2 * m.nmcu;
+    if (m.coef_off < 0 || (m.coef_off & 63) || (unsigned long long)m.coef_off + (unsigned long long)m.blocks * 64 > coef_elems) return false;
+    if (m.plane_off < 0 || (m.plane_off & 63) || (unsigned long long)m.plane_off + (unsigned long long)m.blocks * 64 > plane_bytes) return false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        m.tq[c] = (int)((r[8] >> (8 * c)) & 3);
+        m.td[c] = (int)((r[9] >> (8 * c)) & 3);
+        m.ta[c] = (int)((r[10] >> (8 * c)) & 3);
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(ENT_NT) void jpeg_entropy_kernel(const uint8_t* __restrict__ data, size_t data_bytes,
+                                    const int64_t* __restrict__ img, int B, const int64_t* __restrict__ seg, int S, int lanes,
+                                    const MgJpegTables* __restrict__ tables, int n_sets,
+                                    int16_t* __restrict__ coef, size_t coef_elems, size_t plane_bytes, size_t pixel_bytes,
+                                    int32_t* __restrict__ status) {
+    // The batch's first LDS_SETS table sets -- nearly always all of them -- are copied into LDS: the look-up of a symbol is the one
+    // load every trip of the loop waits for, and it depends on the bits just read.  A lane of another set reads global memory.
+    __shared__ __attribute__((aligned(16))) MgJpegTables s_tables[LDS_SETS];
+    {
+        const int n16 = (n_sets < LDS_SETS ? n_sets : LDS_SETS) * (int)(sizeof(MgJpegTables) / 16);
+        const u32x4* const src = reinterpret_cast<const u32x4*>(tables);
+        u32x4* const dst = reinterpret_cast<u32x4*>(s_tables);
+        for (int i = threadIdx.x; i < n16; i += ENT_NT) dst[i] = src[i];
+    }
+    __syncthreads();
+    const long long s = (long long)blockIdx.x * lanes + threadIdx.x;
+    if ((int)threadIdx.x >= lanes || s >= S) return;
+    const int64_t* const r = seg + s * SEG;
+    const long long im = r[0], b = r[1], e = r[2], mcu0 = r[3], nmcu = r[4];
+    Img m;
+    int st = MG_JPEG_SEG_BAD_RECORD;
+    if (im >= 0 && im < B && b >= 0 && b <= e && (unsigned long long)e <= data_bytes && mcu0 >= 0 && nmcu >= 1 &&
+        load_img(img + im * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) && m.kind == 1 && mcu0 <= m.nmcu - nmcu) {
+        MgJpegSegment g;
+        g.ncomp = m.ncomp, g.hs = m.hs, g.vs = m.vs, g.mcux = m.mcux, g.mcu_total = (int)m.nmcu, g.mcu0 = (int)mcu0, g.nmcu = (int)nmcu;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g.td[c] = m.td[c], g.ta[c] = m.ta[c];
+        int16_t* const c0 = coef + m.coef_off;
+        int16_t* const c1 = c0 + m.blocks0 * 64;
+        int16_t* const c2 = c1 + m.nmcu * 64;
+        const MgJpegTables* const T = m.set < LDS_SETS ? &s_tables[m.set] : tables + m.set;
+        st = mg_jpeg_decode_segment(data + b, data + e, T, g, c0, c1, c2);
+    }
+    status[s] = st;
+}
+
+__global__ __launch_bounds__(NT) void jpeg_idct_kernel(const int64_t* __restrict__ img, const MgJpegTables* __restrict__ tables, int n_sets,
+                                                       const int16_t* __restrict__ coef, size_t coef_elems, uint8_t* __restrict__ planes,
+                                                       size_t plane_bytes, size_t pixel_bytes) {
+    __shared__ int32_t s_ws[IDCT_BLOCKS][8][9];
+    Img m;
+    const bool ok = load_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) && m.kind == 1;   // (block-uniform)
+    if (!ok || (long long)blockIdx.x * IDCT_BLOCKS >= m.blocks) return;
+    const int lb = threadIdx.x >> 3, t = threadIdx.x & 7;
+    const long long gb = (long long)blockIdx.x * IDCT_BLOCKS + lb;
+    const bool live = gb < m.blocks;
+    const int c = gb < m.blocks0 ? 0 : (gb < m.blocks0 + m.nmcu ? 1 : 2);
+    if (live) {
+        int32_t ws[8];
+        mg_jpeg_idct_column(coef + m.coef_off + gb * 64, tables[m.set].quant[c == 0 ? m.tq[0] : (c == 1 ? m.tq[1] : m.tq[2])], t, ws);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s_ws[lb][r][t] = ws[r];
+    }
+    __syncthreads();
+    if (live) {
+        int32_t ws[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) ws[x] = s_ws[lb][t][x];
+        union {
+            uint8_t b[8];
+            uint2 v;
+        } o;
+        mg_jpeg_idct_row(ws, o.b);
+        const long long first = c == 0 ? 0 : (c == 1 ? m.blocks0 : m.blocks0 + m.nmcu);      // the component's first block
+        const long long bi = gb - first;
+        const int bw = c == 0 ? m.mcux * m.hs : m.mcux;
+        const long long by = bi / bw, bx = bi - by * bw;
+        // 8 bytes at a multiple of 8: plane offsets are multiples of 64, the pitch 8 bw
+        *reinterpret_cast<uint2*>(planes + m.plane_off + first * 64 + (by * 8 + t) * (8LL * bw) + bx * 8) = o.v;
+    }
+}
+
+__global__ __launch_bounds__(NT) void jpeg_colour_kernel(const int64_t* __restrict__ img, int n_sets, size_t coef_elems,
+                                                         const uint8_t* __restrict__ planes, size_t plane_bytes, uint8_t* __restrict__ pixels,
+                                                         size_t pixel_bytes) {
+    Img m;
+    const bool ok = load_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) && m.kind == 1;
+    if (!ok) return;
+    const long long npix = (long long)m.W * m.H, p = (long long)blockIdx.x * NT + threadIdx.x;
+    if (blockIdx.x == 0) {                              // the padding up to the next image's start (behind the last: the slack too)
+        const long long z = m.pix_off + npix * 3 + threadIdx.x;
+        if (z < m.pix_end) pixels[z] = 0;               // (NT bytes at most: ops.jpeg_decode refuses a longer gap)
+    }
+    if (p >= npix) return;
+    const int y = (int)(p / m.W), x = (int)(p - (long long)y * m.W);
+    const uint8_t* const p0 = planes + m.plane_off;
+    const int pitch0 = 8 * m.mcux * m.hs;
+    const int Y = p0[(size_t)y * pitch0 + x];
+    uint8_t* const o = pixels + m.pix_off + p * 3;
+    if (m.ncomp == 1) {
+        o[0] = o[1] = o[2] = (uint8_t)Y;
+        return;
+    }
+    const uint8_t* const p1 = p0 + m.blocks0 * 64, * const p2 = p1 + m.nmcu * 64;
+    const int dw = (m.W + m.hs - 1) / m.hs, dh = (m.H + m.vs - 1) / m.vs, pitch = 8 * m.mcux;
+    uint8_t rgb[3];
+    mg_jpeg_rgb(Y, mg_jpeg_chroma(p1, pitch, dw, dh, m.hs, m.vs, x, y), mg_jpeg_chroma(p2, pitch, dw, dh, m.hs, m.vs, x, y), rgb);
+    o[0] = rgb[0];
+    o[1] = rgb[1];
+    o[2] = rgb[2];
+}
+
+}  // namespace
+
+extern "C" size_t mgnns_jpeg_tableset_bytes(void) { return sizeof(MgJpegTables); }
+
+extern "C" int mgnns_jpeg_parse(const void* data, size_t bytes, int max_extent, int32_t* info, int64_t* range, int64_t* seg, size_t seg_cap,
+                                void* tables) {
+    MG_REQUIRE(info && range && tables && (seg || seg_cap == 0) && (data || bytes == 0), "mgnns_jpeg_parse: null pointer");
+    MG_REQUIRE(max_extent >= 1 && max_extent <= MAXEXT, "mgnns_jpeg_parse: max_extent=%d (1..%d)", max_extent, MAXEXT);
+    static const uint8_t none = 0;
+    mg_jpeg_parse(data ? (const uint8_t*)data : &none, bytes, max_extent, info, range, seg, seg_cap, (MgJpegTables*)tables);
+    return 0;
+}
+
+extern "C" int mgnns_jpeg_decode_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
+                                     const void* tables, int n_sets, void* coef, size_t coef_elems, void* planes, size_t plane_bytes,
+                                     void* pixels, size_t pixel_bytes, long long max_blocks, long long max_pixels, int stages,
+                                     int32_t* status, mgnns_stream_t stream) {
+    MG_REQUIRE(B >= 0 && B <= 65535 && S >= 0, "mgnns_jpeg_decode_fwd: B=%d (0..65535), S=%d", B, S);
+    MG_REQUIRE(stages >= 1 && stages <= 7, "mgnns_jpeg_decode_fwd: stages=%d is no mask of 1 (entropy), 2 (IDCT), 4 (colour)", stages);
+    if (B == 0 || S == 0) return 0;                // nothing to decode (every image staged by the host, or none at all)
+    MG_REQUIRE(data && img && seg && tables && coef && planes && pixels && status, "mgnns_jpeg_decode_fwd: null pointer");
+    MG_REQUIRE(n_sets >= 1, "mgnns_jpeg_decode_fwd: no table set");
+    MG_REQUIRE(mg_aligned16(coef) && mg_aligned16(planes) && mg_aligned16(pixels) && mg_aligned16(tables),
+               "mgnns_jpeg_decode_fwd: coef, planes, pixels and tables must be 16-byte aligned");
+    MG_REQUIRE(max_blocks >= 1 && max_blocks <= 6LL * (MAXEXT / 8) * (MAXEXT / 8) && max_pixels >= 1 && max_pixels <= (long long)MAXEXT * MAXEXT,
+               "mgnns_jpeg_decode_fwd: max_blocks=%lld, max_pixels=%lld", max_blocks, max_pixels);
+    hipStream_t st = (hipStream_t)stream;
+    if (stages & 1) {
+        hipError_t e = hipMemsetAsync(coef, 0, coef_elems * sizeof(int16_t), st);
+        if (e != hipSuccess) {
+            mgnns_set_error("mgnns_jpeg_decode_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
+            return MGNNS_ERR_LAUNCH;
+        }
+        // Lanes of one wave serialise wherever their streams diverge, lanes of different waves do not: spread the segments over
+        // the SIMDs (4 per CU) before a wave gets a second lane.
+        const int cus = mg_cu_count();
+        if (cus <= 0) return MGNNS_ERR_LAUNCH;
+        int lanes = 1;
+        while (lanes < 64 && (long long)lanes * 4 * cus < S) lanes *= 2;
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((S + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
+                           data_bytes, img, B, seg, S, lanes, (const MgJpegTables*)tables, n_sets, (int16_t*)coef, coef_elems, plane_bytes,
+                           pixel_bytes, status);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_fwd (entropy)");
+    }
+    if (stages & 2) {
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)B), dim3(NT), 0, st, img,
+                           (const MgJpegTables*)tables, n_sets, (const int16_t*)coef, coef_elems, (uint8_t*)planes, plane_bytes, pixel_bytes);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_fwd (idct)");
+    }
+    if (stages & 4) {
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + NT - 1) / NT), (unsigned)B), dim3(NT), 0, st, img, n_sets,
+                           coef_elems, (const uint8_t*)planes, plane_bytes, (uint8_t*)pixels, pixel_bytes);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_fwd (colour)");
+    }
+    return 0;
+}

@@ -1,0 +1,288 @@
+// Baseline JPEG, host half: the marker parser.  Plain C++17 without a HIP header (it also compiles with the host compiler alone:
+// tools/dev/jpeg_host_check.cpp); exported from the library as mgnns_jpeg_parse, which makes no GPU call.  Every read is checked
+// against the file's length; a file that is malformed, or that the GPU decoder does not cover, gets a reason code.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "jpeg_entropy.hpp"
+
+// reason codes (info[MG_JPEG_I_REASON]); info[MG_JPEG_I_DETAIL] holds what was found (a marker, a count, a byte offset)
+enum {
+    MG_JPEG_OK = 0,
+    MG_JPEG_NOT_JPEG = 1,          // no SOI at the start
+    MG_JPEG_MALFORMED = 2,         // a segment runs past the end of the file, or contradicts another
+    MG_JPEG_UNSUPPORTED_SOF = 3,   // progressive (SOF2) or another SOFn; detail = the marker
+    MG_JPEG_ARITHMETIC = 4,        // SOF9..15 or DAC
+    MG_JPEG_PRECISION = 5,         // 12-bit samples (detail 12) or 16-bit quantisation tables (detail 16)
+    MG_JPEG_COMPONENTS = 6,        // neither 1 nor 3 components (CMYK / YCCK: 4)
+    MG_JPEG_ADOBE_TRANSFORM = 7,   // Adobe APP14 with transform 0 on three components (RGB, not YCbCr)
+    MG_JPEG_RGB_IDS = 8,           // component ids 'R','G','B'
+    MG_JPEG_SAMPLING = 9,          // sampling factors other than 1x1 / 2x1 / 2x2 for Y with 1x1 chroma
+    MG_JPEG_SCANS = 10,            // more than one scan, or a scan that does not interleave all components
+    MG_JPEG_DNL = 11,              // the height comes in a DNL segment
+    MG_JPEG_EXTENT = 12,           // width or height outside 1..max_extent
+    MG_JPEG_MISSING_TABLES = 13,   // the scan refers to a table no segment defined; detail = the component
+};
+
+// fields of info[MG_JPEG_INFO_INTS]
+enum {
+    MG_JPEG_I_REASON = 0, MG_JPEG_I_DETAIL, MG_JPEG_I_WIDTH, MG_JPEG_I_HEIGHT, MG_JPEG_I_NCOMP, MG_JPEG_I_HS, MG_JPEG_I_VS,
+    MG_JPEG_I_TQ = 7,              // 3: quantisation-table id per component
+    MG_JPEG_I_TD = 10,             // 3: DC table id per component
+    MG_JPEG_I_TA = 13,             // 3: AC table id per component
+    MG_JPEG_I_RI = 16,             // restart interval in MCUs, 0 = none
+    MG_JPEG_I_RESTARTS = 17,       // RSTn markers found in the entropy-coded data
+    MG_JPEG_I_NSEG = 18,           // independent segments of the scan: ceil(nMCU / Ri), or 1
+    MG_JPEG_I_MCUX = 19, MG_JPEG_I_MCUY = 20,
+    MG_JPEG_INFO_INTS = 24,
+};
+
+namespace mgjpeg {
+
+struct Reader {
+    const uint8_t* d;
+    size_t n;
+    bool has(size_t pos, size_t k) const { return pos <= n && k <= n - pos; }
+    int u16(size_t pos) const { return (d[pos] << 8) | d[pos + 1]; }
+};
+
+// libjpeg's jdhuff.c derivation: canonical codes from the 16 counts; -> false if the counts are no prefix code
+inline bool derive(const uint8_t* bits, const uint8_t* vals, int nvals, MgJpegHuff* h) {
+    memset(h, 0, sizeof(*h));
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int cnt = bits[l - 1];
+        if (code + cnt > (1 << l)) return false;
+        if (cnt) {
+            h->valoffset[l] = k - code;
+            for (int i = 0; i < cnt; ++i, ++k, ++code) {
+                if (l <= MG_JPEG_LOOK_BITS) {
+                    const int first = code << (MG_JPEG_LOOK_BITS - l);
+                    for (int j = 0; j < (1 << (MG_JPEG_LOOK_BITS - l)); ++j) h->look[first + j] = (uint16_t)((l << 8) | vals[k]);
+                }
+            }
+            h->maxcode[l] = code - 1;
+        } else {
+            h->maxcode[l] = -1;
+        }
+        code <<= 1;
+    }
+    h->maxcode[0] = h->maxcode[17] = -1;
+    if (k != nvals) return false;
+    memcpy(h->huffval, vals, (size_t)nvals);
+    return true;
+}
+
+}  // namespace mgjpeg
+
+// Parse one file.  info: MG_JPEG_INFO_INTS int32 (above); range: the entropy-coded data's [begin, end) byte offsets; seg: [seg_cap][2]
+// byte ranges of the scan's independent segments (as many as fit; info[NSEG] says how many there are -- call again with a larger
+// buffer if it is more than seg_cap); tables: the file's tables in use.  Segment j covers MCUs [j Ri, (j+1) Ri).  Restart markers are
+// found by scanning for FF D0..D7; a sound file has NSEG - 1 of them.  With fewer, the last segments get an empty byte range; with
+// more, the surplus is ignored: either way the decoder ends those segments with a status word, never out of range.
+// Returns the reason code (also in info[0]); everything but info[0..1] is meaningful only for MG_JPEG_OK.
+inline int mg_jpeg_parse(const uint8_t* data, size_t n, int max_extent, int32_t* info, int64_t* range, int64_t* seg, size_t seg_cap,
+                         MgJpegTables* tables) {
+    using namespace mgjpeg;
+    const Reader R{data, n};
+    memset(info, 0, sizeof(int32_t) * MG_JPEG_INFO_INTS);
+    memset(tables, 0, sizeof(*tables));
+    range[0] = range[1] = 0;
+    auto refuse = [&](int reason, long long detail) {
+        info[MG_JPEG_I_REASON] = reason;
+        info[MG_JPEG_I_DETAIL] = (int32_t)(detail > 0x7fffffffLL ? 0x7fffffffLL : detail);
+        return reason;
+    };
+    if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return refuse(MG_JPEG_NOT_JPEG, 0);
+
+    uint8_t quant[4][64];
+    uint8_t hbits[2][4][16], hvals[2][4][256];
+    int hcount[2][4];
+    bool have_q[4] = {false, false, false, false}, have_h[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    bool have_frame = false;
+    int width = 0, height = 0, ncomp = 0, comp_id[3] = {0, 0, 0}, comp_h[3] = {1, 1, 1}, comp_v[3] = {1, 1, 1}, comp_tq[3] = {0, 0, 0};
+    int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, ri = 0, adobe = -1;
+    static const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    size_t pos = 2;
+    for (;;) {
+        if (!R.has(pos, 2) || data[pos] != 0xFF) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        while (pos + 1 < n && data[pos + 1] == 0xFF) ++pos;                  // fill bytes
+        if (!R.has(pos, 2)) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        const int m = data[pos + 1];
+        pos += 2;
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;    // stand-alone markers
+        if (m == 0xD9) return refuse(MG_JPEG_MALFORMED, (long long)pos);     // EOI before any scan
+        if (!R.has(pos, 2)) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        const int ln = R.u16(pos);
+        if (ln < 2 || !R.has(pos, (size_t)ln)) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        const size_t body = pos + 2, end = pos + (size_t)ln;
+        if (m == 0xDB) {
+            size_t p = body;
+            while (p < end) {
+                const int pq = data[p] >> 4, tq = data[p] & 15;
+                if (pq != 0) return refuse(MG_JPEG_PRECISION, 16);
+                if (tq > 3 || p + 65 > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                for (int k = 0; k < 64; ++k) quant[tq][ZIGZAG[k]] = data[p + 1 + k];
+                have_q[tq] = true;
+                p += 65;
+            }
+        } else if (m == 0xC4) {
+            size_t p = body;
+            while (p < end) {
+                if (p + 17 > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                const int tc = data[p] >> 4, th = data[p] & 15;
+                int cnt = 0;
+                for (int i = 0; i < 16; ++i) cnt += data[p + 1 + i];
+                if (tc > 1 || th > 3 || cnt > 256 || p + 17 + (size_t)cnt > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                int code = 0;
+                for (int l = 1; l <= 16; ++l) {
+                    code += data[p + l];
+                    if (code > (1 << l)) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                    code <<= 1;
+                }
+                memcpy(hbits[tc][th], data + p + 1, 16);
+                memcpy(hvals[tc][th], data + p + 17, (size_t)cnt);
+                hcount[tc][th] = cnt;
+                have_h[tc][th] = true;
+                p += 17 + (size_t)cnt;
+            }
+        } else if (m == 0xDD) {
+            if (ln != 4) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            ri = R.u16(body);
+        } else if (m == 0xCC || (m >= 0xC9 && m <= 0xCF)) {
+            return refuse(MG_JPEG_ARITHMETIC, m);
+        } else if (m == 0xC1 || m == 0xC2 || m == 0xC3 || m == 0xC5 || m == 0xC6 || m == 0xC7 || m == 0xC8) {
+            return refuse(MG_JPEG_UNSUPPORTED_SOF, m);
+        } else if (m == 0xC0) {
+            if (have_frame || ln < 8) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int prec = data[body], nf = data[body + 5];
+            height = R.u16(body + 1);
+            width = R.u16(body + 3);
+            if (prec != 8) return refuse(MG_JPEG_PRECISION, prec);
+            if (ln != 8 + 3 * nf) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            if (nf != 1 && nf != 3) return refuse(MG_JPEG_COMPONENTS, nf);
+            if (height == 0) return refuse(MG_JPEG_DNL, 0);
+            if (width < 1 || width > max_extent || height > max_extent) return refuse(MG_JPEG_EXTENT, width > max_extent ? width : height);
+            ncomp = nf;
+            for (int i = 0; i < nf; ++i) {
+                comp_id[i] = data[body + 6 + 3 * i];
+                comp_h[i] = data[body + 7 + 3 * i] >> 4;
+                comp_v[i] = data[body + 7 + 3 * i] & 15;
+                comp_tq[i] = data[body + 8 + 3 * i];
+            }
+            if (nf == 3 && comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B') return refuse(MG_JPEG_RGB_IDS, 0);
+            for (int i = 0; i < nf; ++i)
+                if (comp_tq[i] > 3) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int hv = comp_h[0] * 16 + comp_v[0];
+            if (nf == 1) {
+                if (hv != 0x11) return refuse(MG_JPEG_SAMPLING, hv);
+            } else if ((hv != 0x11 && hv != 0x21 && hv != 0x22) || comp_h[1] != 1 || comp_v[1] != 1 || comp_h[2] != 1 || comp_v[2] != 1) {
+                return refuse(MG_JPEG_SAMPLING, hv);
+            }
+            have_frame = true;
+        } else if (m == 0xDC) {
+            return refuse(MG_JPEG_DNL, 0);
+        } else if (m == 0xEE && ln >= 14 && memcmp(data + body, "Adobe", 5) == 0) {
+            adobe = data[body + 11];
+        } else if (m == 0xDA) {
+            if (!have_frame) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int ns = ln >= 3 ? data[body] : 0;
+            if (ns != ncomp) return refuse(MG_JPEG_SCANS, ns);
+            if (ln != 6 + 2 * ns) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            for (int i = 0; i < ns; ++i) {
+                if (data[body + 1 + 2 * i] != comp_id[i]) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+                td[i] = data[body + 2 + 2 * i] >> 4;
+                ta[i] = data[body + 2 + 2 * i] & 15;
+                if (td[i] > 3 || ta[i] > 3) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            }
+            if (data[body + 1 + 2 * ns] != 0 || data[body + 2 + 2 * ns] != 63 || data[body + 3 + 2 * ns] != 0)
+                return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            if (adobe == 0 && ns == 3) return refuse(MG_JPEG_ADOBE_TRANSFORM, 0);
+            for (int i = 0; i < ns; ++i)
+                if (!have_q[comp_tq[i]] || !have_h[0][td[i]] || !have_h[1][ta[i]]) return refuse(MG_JPEG_MISSING_TABLES, i);
+            pos = end;
+            break;
+        }
+        pos = end;
+    }
+
+    // the entropy-coded data: up to the first marker that is neither a stuffed FF, a fill byte nor RSTn
+    const int hs = comp_h[0], vs = comp_v[0];
+    const int mcux = (width + 8 * hs - 1) / (8 * hs), mcuy = (height + 8 * vs - 1) / (8 * vs);
+    const long long nmcu = (long long)mcux * mcuy;
+    const long long nseg = ri ? (nmcu + ri - 1) / ri : 1;
+    const size_t begin = pos;
+    size_t i = pos, seg_begin = pos;
+    long long found = 0;
+    auto put = [&](long long j, size_t b, size_t e) {
+        if (j < nseg && (size_t)j < seg_cap) {
+            seg[2 * j] = (int64_t)b;
+            seg[2 * j + 1] = (int64_t)e;
+        }
+    };
+    for (;;) {
+        while (i < n && data[i] != 0xFF) ++i;
+        if (i + 1 >= n) {
+            i = n;
+            break;
+        }
+        const int b = data[i + 1];
+        if (b == 0) {
+            i += 2;
+        } else if (b == 0xFF) {
+            i += 1;
+        } else if (b >= 0xD0 && b <= 0xD7) {
+            put(found, seg_begin, i);
+            ++found;
+            i += 2;
+            seg_begin = i;
+        } else {
+            break;
+        }
+    }
+    const size_t ecs_end = i;
+    put(found, seg_begin, ecs_end);
+    for (long long j = found + 1; j < nseg; ++j) put(j, ecs_end, ecs_end);
+    // what follows: another scan or DNL is refused; anything else (EOI, nothing, rubbish) ends the file
+    while (i + 1 < n && data[i] == 0xFF) {
+        const int b = data[i + 1];
+        if (b == 0xFF) {
+            ++i;
+            continue;
+        }
+        if (b == 0xD9) break;
+        if (b == 0xDA) return refuse(MG_JPEG_SCANS, 2);
+        if (b == 0xDC) return refuse(MG_JPEG_DNL, 0);
+        if (i + 4 > n) break;
+        i += 2 + (size_t)R.u16(i + 2);
+    }
+
+    for (int c = 0; c < ncomp; ++c) {
+        memcpy(tables->quant[comp_tq[c]], quant[comp_tq[c]], 64);
+        if (!mgjpeg::derive(hbits[0][td[c]], hvals[0][td[c]], hcount[0][td[c]], &tables->dc[td[c]]) ||
+            !mgjpeg::derive(hbits[1][ta[c]], hvals[1][ta[c]], hcount[1][ta[c]], &tables->ac[ta[c]]))
+            return refuse(MG_JPEG_MALFORMED, c);
+    }
+    info[MG_JPEG_I_WIDTH] = width;
+    info[MG_JPEG_I_HEIGHT] = height;
+    info[MG_JPEG_I_NCOMP] = ncomp;
+    info[MG_JPEG_I_HS] = hs;
+    info[MG_JPEG_I_VS] = vs;
+    for (int c = 0; c < 3; ++c) {
+        info[MG_JPEG_I_TQ + c] = comp_tq[c];
+        info[MG_JPEG_I_TD + c] = td[c];
+        info[MG_JPEG_I_TA + c] = ta[c];
+    }
+    info[MG_JPEG_I_RI] = ri;
+    info[MG_JPEG_I_RESTARTS] = (int32_t)(found > 0x7fffffffLL ? 0x7fffffffLL : found);
+    info[MG_JPEG_I_NSEG] = (int32_t)nseg;
+    info[MG_JPEG_I_MCUX] = mcux;
+    info[MG_JPEG_I_MCUY] = mcuy;
+    range[0] = (int64_t)begin;
+    range[1] = (int64_t)ecs_end;
+    return MG_JPEG_OK;
+}

@@ -11,8 +11,9 @@ normalize_coeffs_8bpc do (build_plan) and the kernel runs Pillow's two passes, h
 for bit, for extents 16..4096 with an aspect of at most 4:1 (tests/test_image_prep_cpu.py); far outside that domain Pillow may
 run its passes in the other order (seen at 1000x7 -> 16 and 1000x8 -> 16) and the intermediate rounding then differs.
 
-Decoding stays the caller's: an image is a [H,W,3] uint8 array, or anything with __array_interface__ (a PIL image in mode RGB).
-This module does not import PIL."""
+An image is a [H,W,3] uint8 array, or anything with __array_interface__ (a PIL image in mode RGB) -- or the bytes of a baseline JPEG
+file, which decode_jpeg / warp_jpeg / train_jpeg decode on the GPU to exactly Pillow's pixels (csrc/jpeg_decode.hip):
+the host only parses the markers.  This module does not import PIL."""
 import math
 import random
 
@@ -100,6 +101,83 @@ def as_rgb8(img, i=0):
     return img
 
 
+# ---- JPEG files ------------------------------------------------------------------------------------------------------------
+# the parser's reason codes (csrc/jpeg_parse.hpp)
+JPEG_REASONS = {
+    0: "accepted", 1: "not a JPEG file (no SOI marker)", 2: "malformed or truncated header", 3: "progressive or another unsupported SOFn frame",
+    4: "arithmetic coding", 5: "12-bit samples or 16-bit quantisation tables", 6: "neither 1 nor 3 components (CMYK / YCCK)",
+    7: "Adobe APP14 segment with transform 0 (RGB)", 8: "component ids R, G, B", 9: "sampling factors other than 4:4:4, 4:2:2, 4:2:0",
+    10: "more than one scan, or a non-interleaved scan", 11: "height given by a DNL segment", 12: "extent out of range",
+    13: "the scan refers to a table that is not defined"}
+_JI = dict(reason=0, detail=1, width=2, height=3, ncomp=4, hs=5, vs=6, tq=7, td=10, ta=13, ri=16, restarts=17, nseg=18, mcux=19, mcuy=20)
+
+
+class UnsupportedJpeg(ValueError):
+    """A batch holds files the GPU decoder refuses and no fallback was given.  refused: [(index, reason code)]."""
+
+    def __init__(self, refused, details):
+        self.refused = refused
+        ValueError.__init__(self, "%d JPEG file(s) cannot be decoded on the GPU (pass fallback= to decode them yourself): %s" % (
+            len(refused), "; ".join("image %d: %s (reason %d, found %s)" % (i, JPEG_REASONS.get(r, "?"), r, d) for (i, r), d in zip(refused, details))))
+
+
+def _file_bytes(f, i=0):
+    if not isinstance(f, (bytes, bytearray, memoryview)):
+        raise TypeError("file %d: expected bytes, bytearray or memoryview, got %s" % (i, type(f).__name__))
+    return np.frombuffer(f, dtype=np.uint8)
+
+
+def parse_jpeg(data, max_extent=None, _seg=None):
+    """The host parser (mgnns_jpeg_parse: no GPU call) on one file's bytes -> dict: reason (0 = accepted), detail, and for an accepted
+    file width, height, ncomp, hs, vs (Y's sampling), tq / td / ta (table ids per component), ri, restarts (markers found), nseg, mcux,
+    mcuy, ecs (begin, end), segments (int64 [nseg,2] byte ranges) and tables (the table set's bytes)."""
+    from . import _lib
+    L = _lib.lib()
+    a = _file_bytes(data)
+    info = np.zeros(24, np.int32)
+    rng = np.zeros(2, np.int64)
+    tables = np.zeros(ops.jpeg_tableset_bytes(), np.uint8)
+    seg = np.zeros((64, 2), np.int64) if _seg is None else _seg
+    ptr = a.ctypes.data if a.size else None
+    _lib.check(L.mgnns_jpeg_parse(ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data, seg.ctypes.data,
+                                  seg.shape[0], tables.ctypes.data), "mgnns_jpeg_parse")
+    if info[0] == 0 and info[_JI["nseg"]] > seg.shape[0]:
+        seg = np.zeros((int(info[_JI["nseg"]]), 2), np.int64)
+        _lib.check(L.mgnns_jpeg_parse(ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data, seg.ctypes.data,
+                                      seg.shape[0], tables.ctypes.data), "mgnns_jpeg_parse")
+    out = dict(reason=int(info[0]), detail=int(info[1]))
+    if out["reason"] == 0:
+        for k in ("width", "height", "ncomp", "hs", "vs", "ri", "restarts", "nseg", "mcux", "mcuy"):
+            out[k] = int(info[_JI[k]])
+        for k in ("tq", "td", "ta"):
+            out[k] = [int(v) for v in info[_JI[k]:_JI[k] + 3]]
+        out["ecs"] = (int(rng[0]), int(rng[1]))
+        out["segments"] = seg[:out["nseg"]].copy()
+        out["tables"] = tables.tobytes()
+    return out
+
+
+class DecodedBatch:
+    """What decode_jpeg returns; unpacks as (pixels, sizes, offsets).  pixels: uint8 on the device, every image interleaved RGB8 at
+    its 16-byte-aligned offset, padding and 16 bytes of slack zero -- pack()'s layout; sizes: host int64 [B,2] (H, W); offsets: host
+    int64 [B]."""
+
+    def __init__(self, pixels, sizes, offsets):
+        self.pixels, self.sizes, self.offsets = pixels, sizes, offsets
+
+    def __iter__(self):
+        return iter((self.pixels, self.sizes, self.offsets))
+
+    def __len__(self):
+        return int(self.sizes.shape[0])
+
+    def image(self, i):
+        """Image i as a [H,W,3] uint8 device tensor (a view of pixels)."""
+        H, W = (int(v) for v in self.sizes[i])
+        o = int(self.offsets[i])
+        return self.pixels[o:o + H * W * 3].view(H, W, 3)
+
+
 class _Slot:
     """One batch's pinned staging: the packed pixels and the descriptors."""
 
@@ -108,6 +186,14 @@ class _Slot:
         self.pix = torch.empty(0, dtype=torch.uint8)
         self.desc = torch.empty(0, ops.IMAGE_DESC, dtype=torch.int64)
         self.done = torch.cuda.Event() if pin else None
+        self.raw = torch.empty(0, dtype=torch.uint8)          # JPEG batches: the files' bytes, the table sets, fall-back pixels
+        self.rec = torch.empty(0, dtype=torch.int64)          # ... and the image and segment records
+
+    def reserve_jpeg(self, nbytes, nrec):
+        if self.raw.numel() < nbytes:
+            self.raw = torch.empty(nbytes + nbytes // 4, dtype=torch.uint8, pin_memory=self.pin)
+        if self.rec.numel() < nrec:
+            self.rec = torch.empty(nrec + nrec // 4, dtype=torch.int64, pin_memory=self.pin)
 
     def reserve(self, nbytes, B):
         if self.pix.numel() < nbytes:
@@ -288,3 +374,169 @@ class ImagePrep:
             crops, flips = sc, sf
         self.last_crops, self.last_flips = [tuple(int(v) for v in c) for c in crops], [bool(f) for f in flips]
         return self._run(images, self.last_crops, self.last_flips)
+
+    # ---- JPEG files --------------------------------------------------------------------------------------------------------
+    def _jpeg_headers(self, files, fallback):
+        """Parse every file on the host (no GPU work).  Refused files go to `fallback` -- or raise UnsupportedJpeg, all of them in
+        one exception.  -> (files, parsed, {index: fall-back pixels}, [(W, H)])"""
+        files = list(files)
+        seg = np.zeros((1024, 2), np.int64)
+        parsed, refused = [], []
+        for i, f in enumerate(files):
+            _file_bytes(f, i)
+            parsed.append(parse_jpeg(f, _seg=seg))
+            if parsed[-1]["reason"]:
+                refused.append((i, parsed[-1]["reason"]))
+        if refused and fallback is None:
+            raise UnsupportedJpeg(refused, [parsed[i]["detail"] for i, _ in refused])
+        arrays = {i: as_rgb8(fallback(files[i]), i) for i, _ in refused}
+        sizes = [(arrays[i].shape[1], arrays[i].shape[0]) if i in arrays else (p["width"], p["height"]) for i, p in enumerate(parsed)]
+        return files, parsed, arrays, sizes
+
+    def _jpeg_run(self, headers, crops=None, flips=None, prep=False, staged_only=False):
+        """Stage one batch of parsed files into the next slot of the pinned ring -- the files' bytes, the distinct table sets, the
+        image and segment records, the pixels of fall-back images -- copy them over and decode.  With prep=True the descriptors of
+        (crops, flips) follow and image_prep runs on the decoded buffer.  -> DecodedBatch, or the [B,3,size,size] tensor.
+        staged_only=True stops before the decode and returns (ops.jpeg_decode's arguments, DecodedBatch): tools/bench_jpeg.py."""
+        if self.device is None:
+            raise RuntimeError("ImagePrep was built without a device: JPEG files are decoded on the GPU only (no CPU path)")
+        files, parsed, arrays, sizes = headers
+        B = len(files)
+        if crops is not None and len(crops) != B or flips is not None and len(flips) != B:
+            raise ValueError("crops / flips must have one entry per image")
+        offs, total = [], 0
+        for W, H in sizes:
+            offs.append(total)
+            total += (H * W * 3 + ALIGN - 1) // ALIGN * ALIGN
+        total += ALIGN
+        ends = offs[1:] + [total]
+        desc_rows = []
+        if prep:
+            for i, (W, H) in enumerate(sizes):
+                cw, ch, cx, cy = (W, H, 0, 0) if crops is None else (int(v) for v in crops[i])
+                if cw < 1 or ch < 1 or cx < 0 or cy < 0 or cx + cw > W or cy + ch > H:
+                    raise ValueError("image %d: crop (w=%d, h=%d, x=%d, y=%d) is not inside the %dx%d image" % (i, cw, ch, cx, cy, W, H))
+                desc_rows.append((offs[i], H, W, cx, cy, cw, ch, 1 if (flips is not None and bool(flips[i])) else 0, self.plan(cw), self.plan(ch)))
+        # layout of the raw buffer: the accepted files at 16-byte starts, the table sets, then the fall-back images' pixels
+        TB = ops.jpeg_tableset_bytes()
+        raw_off, n, sets = {}, 0, {}
+        for i, f in enumerate(files):
+            if i not in arrays:
+                raw_off[i] = n
+                n += (_file_bytes(f).size + ALIGN - 1) // ALIGN * ALIGN
+                sets.setdefault(parsed[i]["tables"], len(sets))
+        tab_off = n
+        n += len(sets) * TB
+        n_data = n
+        fb_off = {}
+        for i in arrays:
+            fb_off[i] = n
+            n += ends[i] - offs[i]
+        img = np.zeros((B, ops.JPEG_IMG), np.int64)
+        segs, coef_off, plane_off = [], 0, 0
+        for i, p in enumerate(parsed):
+            W, H = sizes[i]
+            if i in arrays:
+                img[i] = (0, W, H, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, offs[i], ends[i])
+                continue
+            nmcu = p["mcux"] * p["mcuy"]
+            blocks = nmcu if p["ncomp"] == 1 else nmcu * (p["hs"] * p["vs"] + 2)
+            pack3 = lambda v: v[0] | v[1] << 8 | v[2] << 16
+            img[i] = (1, W, H, p["ncomp"], p["hs"], p["vs"], p["mcux"], p["mcuy"], pack3(p["tq"]), pack3(p["td"]), pack3(p["ta"]),
+                      sets[p["tables"]], coef_off, plane_off, offs[i], ends[i])
+            coef_off += blocks * 64
+            plane_off += blocks * 64
+            s = np.empty((p["nseg"], ops.JPEG_SEG), np.int64)
+            s[:, 0] = i
+            s[:, 1:3] = p["segments"] + raw_off[i]
+            s[:, 3] = np.arange(p["nseg"]) * p["ri"]
+            s[:, 4] = np.minimum(p["ri"], nmcu - s[:, 3]) if p["ri"] else nmcu
+            segs.append(s)
+        seg = np.concatenate(segs) if segs else np.zeros((0, ops.JPEG_SEG), np.int64)
+        S = seg.shape[0]
+
+        slot = self._ring[self._next]
+        self._next = (self._next + 1) % len(self._ring)
+        if slot.done is not None:
+            slot.done.synchronize()              # the slot's previous H2D copies have left the pinned buffers
+        slot.reserve_jpeg(n, B * ops.JPEG_IMG + S * ops.JPEG_SEG)
+        slot.reserve(0, B)
+        raw = slot.raw.numpy()
+        for i, f in enumerate(files):
+            if i in arrays:
+                a, o = arrays[i], fb_off[i]
+                nb = a.shape[0] * a.shape[1] * 3
+                np.copyto(raw[o:o + nb].reshape(a.shape), a)
+                raw[o + nb:o + ends[i] - offs[i]] = 0
+            else:
+                o = raw_off[i]
+                raw[o:o + _file_bytes(f).size] = _file_bytes(f)
+        for t, k in sets.items():
+            raw[tab_off + k * TB:tab_off + (k + 1) * TB] = np.frombuffer(t, np.uint8)
+        img_host = slot.rec[:B * ops.JPEG_IMG].view(B, ops.JPEG_IMG)
+        seg_host = slot.rec[B * ops.JPEG_IMG:B * ops.JPEG_IMG + S * ops.JPEG_SEG].view(S, ops.JPEG_SEG)
+        img_host.numpy()[:] = img
+        seg_host.numpy()[:] = seg
+        desc = slot.desc[:B]
+        if prep and B:
+            desc.numpy()[:] = np.asarray(desc_rows, dtype=np.int64)
+
+        with torch.cuda.device(self.device):
+            raw_dev = torch.empty(max(n_data, ALIGN), dtype=torch.uint8, device=self.device)
+            rec_dev = torch.empty(max(B * ops.JPEG_IMG + S * ops.JPEG_SEG, 1), dtype=torch.int64, device=self.device)
+            pix_dev = torch.empty(total, dtype=torch.uint8, device=self.device) if B else torch.zeros(total, dtype=torch.uint8, device=self.device)
+            raw_dev[:n_data].copy_(slot.raw[:n_data], non_blocking=True)                # the files and the tables: one H2D
+            rec_dev[:B * ops.JPEG_IMG + S * ops.JPEG_SEG].copy_(slot.rec[:B * ops.JPEG_IMG + S * ops.JPEG_SEG], non_blocking=True)
+            for i in arrays:                                                             # fall-back images: their pixels, as pack stages them
+                pix_dev[offs[i]:ends[i]].copy_(slot.raw[fb_off[i]:fb_off[i] + ends[i] - offs[i]], non_blocking=True)
+            if prep:
+                table, table_dev, data_dev = self._plans_on_device()
+                desc_dev = torch.empty(desc.shape, dtype=torch.int64, device=self.device)
+                desc_dev.copy_(desc, non_blocking=True)
+            slot.done.record()
+            img_dev = rec_dev[:B * ops.JPEG_IMG].view(B, ops.JPEG_IMG)
+            seg_dev = rec_dev[B * ops.JPEG_IMG:B * ops.JPEG_IMG + S * ops.JPEG_SEG].view(S, ops.JPEG_SEG)
+            tables_dev = raw_dev[tab_off:tab_off + len(sets) * TB].view(len(sets), TB)
+            batch = DecodedBatch(pix_dev, torch.tensor([(H, W) for W, H in sizes], dtype=torch.int64).reshape(B, 2),
+                                 torch.tensor(offs, dtype=torch.int64))
+            if staged_only:                      # (host records cloned: the slot is reused two batches later)
+                return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pix_dev), batch
+            try:
+                ops.jpeg_decode(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pix_dev)
+            except ops.JpegDecodeError as e:
+                e.batch = batch                  # every image the error does not name is decoded in it
+                raise
+            if prep:
+                return ops.image_prep(pix_dev, desc, desc_dev, table, table_dev, data_dev, self.table_dev, self.size, self.size)
+        return batch
+
+    def decode_jpeg(self, files, fallback=None):
+        """Decode a batch of baseline JPEG files (bytes / bytearray / memoryview each) on the GPU to exactly the pixels Pillow's
+        Image.open(...).convert('RGB') gives -> DecodedBatch (pixels on the device in pack()'s layout, host sizes [B,2] as (H, W),
+        host offsets; .image(i) views one image).  The host parses the markers and copies the compressed bytes; raw pixels never
+        cross PCIe.  A file outside the decoder's scope (progressive, CMYK, ...: JPEG_REASONS) raises UnsupportedJpeg before any GPU
+        work -- or, with fallback=callable, is decoded by the caller: fallback(file bytes) -> a [H,W,3] uint8 array, staged into the
+        same pixel buffer.  A file whose scan is corrupt raises ops.JpegDecodeError (a ValueError) after the decode, naming the
+        image and the segment's status."""
+        return self._jpeg_run(self._jpeg_headers(files, fallback))
+
+    def warp_jpeg(self, files, fallback=None):
+        """warp() of the decoded files: one decode launch sequence and one image_prep launch -> [B,3,size,size] fp32."""
+        return self._jpeg_run(self._jpeg_headers(files, fallback), None, None, prep=True)
+
+    def train_jpeg(self, files, crops=None, flips=None, fallback=None):
+        """train() of the decoded files.  Crops and flips are sampled from the header sizes exactly as train samples them from the
+        arrays' -- check_croppable on every image first, then per image the crop and the flip -- and kept in last_crops / last_flips."""
+        headers = self._jpeg_headers(files, fallback)
+        sizes = headers[3]
+        if crops is None or flips is None:
+            if crops is None:
+                for i, (W, H) in enumerate(sizes):
+                    self.check_croppable(W, H, i)
+            sc, sf = [], []
+            for i, (W, H) in enumerate(sizes):
+                sc.append(self.sample_crop(W, H) if crops is None else tuple(crops[i]))
+                sf.append(bool(torch.rand(1) < 0.5) if flips is None else bool(flips[i]))
+            crops, flips = sc, sf
+        self.last_crops, self.last_flips = [tuple(int(v) for v in c) for c in crops], [bool(f) for f in flips]
+        return self._jpeg_run(headers, self.last_crops, self.last_flips, prep=True)

@@ -1824,8 +1824,110 @@ def image_prep(pixels, desc, desc_dev, plan_table, plan_table_dev, plan_data, lu
     return out
 
 
+# ---- f4, file half: baseline JPEG files -> the packed RGB8 pixel buffer image_prep reads (csrc/jpeg_decode.hip) --------------------
+JPEG_IMG = 16             # int64 per image: kind, width, height, components, Y sampling h, v, MCUs per row, MCU rows, quantisation /
+#                           DC / AC table ids (a byte per component), table set, coefficient / plane / pixel offset, end of the padding
+JPEG_SEG = 5              # int64 per segment: image, begin, end (bytes in the data buffer), first MCU, MCUs
+JPEG_STATUS = {0: "ok", 1: "ran out of data", 2: "invalid Huffman code", 3: "coefficient index above 63",
+               4: "record refused by the kernel"}
+JPEG_MAX_GAP = 256        # bytes of padding behind an image that the decoder zeroes
+
+
+class JpegDecodeError(ValueError):
+    """Some segments did not decode.  failed: [(image, segment, status word)], segment counted over the batch; pixels: the pixel
+    buffer -- every image not named in `failed` is decoded in it."""
+
+    def __init__(self, failed, pixels):
+        self.failed, self.pixels = failed, pixels
+        by_image = {}
+        for i, s, st in failed:
+            by_image.setdefault(i, []).append("segment %d: %s (status %d)" % (s, JPEG_STATUS.get(st, "?"), st))
+        ValueError.__init__(self, "JPEG decode failed for %d image(s): %s" % (
+            len(by_image), "; ".join("image %d: %s" % (i, ", ".join(v[:4]) + (" ..." if len(v) > 4 else "")) for i, v in sorted(by_image.items()))))
+
+
+def jpeg_tableset_bytes():
+    return int(_lib.lib().mgnns_jpeg_tableset_bytes())
+
+
+def jpeg_decode(data, img, img_dev, seg, seg_dev, tables, pixels, stages=7, check=True):
+    """Decode a batch of parsed baseline JPEG files into `pixels` (include/mgnns_hip.h, "f4 (file half)"): Huffman decoding with one
+    lane per segment, dequantisation + jidctint, chroma upsampling + colour conversion, three launches on the current stream.
+    data: uint8 [n] on the GPU, the files' bytes; img [B,16] / seg [S,5] int64 are HOST tensors, validated here, img_dev / seg_dev
+    their device copies; tables: uint8 [n_sets, jpeg_tableset_bytes()] on the GPU; pixels: uint8 [m] on the GPU, written at the
+    records' offsets (an image of kind 0 is skipped: the caller stages its pixels).  With check=True the [S] status words come back
+    in one small copy on the current stream and a JpegDecodeError (a ValueError) names every image with a segment that is not ok;
+    with check=False nothing synchronises and the status tensor is returned for the caller to read.  -> the status tensor."""
+    _chk(data, "data", torch.uint8, 1)
+    _chk(pixels, "pixels", torch.uint8, 1)
+    _chk(tables, "tables", torch.uint8, 2)
+    _chk_host(img, "img", torch.int64, JPEG_IMG)
+    _chk_host(seg, "seg", torch.int64, JPEG_SEG)
+    _chk(img_dev, "img_dev", torch.int64, 2)
+    _chk(seg_dev, "seg_dev", torch.int64, 2)
+    B, S, n_sets = img.shape[0], seg.shape[0], tables.shape[0]
+    if tuple(img_dev.shape) != tuple(img.shape) or tuple(seg_dev.shape) != tuple(seg.shape):
+        raise ValueError("img_dev %s / seg_dev %s must have the shapes of their host copies %s / %s"
+                         % (tuple(img_dev.shape), tuple(seg_dev.shape), tuple(img.shape), tuple(seg.shape)))
+    if tables.shape[1] != jpeg_tableset_bytes():
+        raise ValueError("tables must be [n_sets,%d], got %s" % (jpeg_tableset_bytes(), tuple(tables.shape)))
+    for t, name in ((img_dev, "img_dev"), (seg_dev, "seg_dev"), (tables, "tables"), (pixels, "pixels")):
+        if t.device != data.device:
+            raise ValueError("%s is on %s, data on %s" % (name, t.device, data.device))
+    if B > 65535:
+        raise ValueError("at most 65535 images per batch, got %d" % B)
+    if int(stages) < 1 or int(stages) > 7:
+        raise ValueError("stages is a mask of 1 (entropy), 2 (IDCT), 4 (colour), got %s" % (stages,))
+    status = torch.zeros(S, dtype=torch.int32, device=data.device)
+    if B == 0 or S == 0:
+        return status
+    kind, W, H, nc, hs, vs, mcux, mcuy, tq, td, ta, tset, coef_off, plane_off, pix_off, pix_end = img.unbind(1)
+
+    def refuse(mask, what, rec=img, noun="image"):
+        if bool(mask.any()):
+            i = int(mask.nonzero()[0])
+            raise ValueError("%s %d: %s (record %s)" % (noun, i, what, rec[i].tolist()))
+
+    refuse((kind != 0) & (kind != 1), "kind must be 0 or 1")
+    refuse((W < 1) | (W > IMAGE_MAX_EXTENT) | (H < 1) | (H > IMAGE_MAX_EXTENT), "extent outside 1..%d" % IMAGE_MAX_EXTENT)
+    refuse((pix_off < 0) | (pix_off % 16 != 0), "pixel offset is not a non-negative multiple of 16")
+    refuse((pix_end > pixels.numel()) | (pix_end - pix_off < W * H * 3) | (pix_end - pix_off - W * H * 3 > JPEG_MAX_GAP),
+           "pixels and their padding (at most %d bytes) do not fit the pixel buffer of %d bytes" % (JPEG_MAX_GAP, pixels.numel()))
+    dec = kind == 1
+    sampling_ok = ((nc == 1) & (hs == 1) & (vs == 1)) | ((nc == 3) & (((hs == 1) & (vs == 1)) | ((hs == 2) & ((vs == 1) | (vs == 2)))))
+    refuse(dec & ~sampling_ok, "components / sampling not supported")
+    hs1, vs1 = hs.clamp(1, 2), vs.clamp(1, 2)
+    refuse(dec & ((mcux != (W + 8 * hs1 - 1) // (8 * hs1)) | (mcuy != (H + 8 * vs1 - 1) // (8 * vs1))), "MCU counts do not match the extent")
+    refuse(dec & ((tset < 0) | (tset >= n_sets)), "table set outside 0..%d" % (n_sets - 1))
+    refuse(dec & ((tq < 0) | (td < 0) | (ta < 0) | (((tq | td | ta) & ~0x030303) != 0)), "table ids must be 0..3")
+    nmcu = mcux * mcuy
+    blocks = torch.where(nc == 1, nmcu, nmcu * (hs * vs + 2)) * dec
+    refuse(dec & ((coef_off < 0) | (coef_off % 64 != 0) | (plane_off < 0) | (plane_off % 64 != 0)), "workspace offsets must be non-negative multiples of 64")
+    coef_elems = int((coef_off * dec + blocks * 64).max())
+    plane_bytes = int((plane_off * dec + blocks * 64).max())
+    si, sb, se, m0, mn = seg.unbind(1)
+    refuse((si < 0) | (si >= B), "image index outside the batch", seg, "segment")
+    refuse(~dec[si], "segment of an image that is not decoded", seg, "segment")
+    refuse((sb < 0) | (sb > se) | (se > data.numel()), "byte range outside the data buffer of %d bytes" % data.numel(), seg, "segment")
+    refuse((m0 < 0) | (mn < 1) | (m0 > nmcu[si] - mn), "MCU range outside the image", seg, "segment")
+    if coef_elems > (1 << 34):
+        raise ValueError("the batch needs a coefficient workspace of %d int16 -- decode it in smaller batches" % coef_elems)
+    coef = torch.empty(max(coef_elems, 64), dtype=torch.int16, device=data.device)
+    planes = torch.empty(max(plane_bytes, 64), dtype=torch.uint8, device=data.device)
+    L = _lib.lib()
+    _launch("mgnns_jpeg_decode_fwd", ("mgnns_jpeg_decode_fwd", B, S), L.mgnns_jpeg_decode_fwd, _p(data), data.numel(), _p(img_dev), B,
+            _p(seg_dev), S, _p(tables), n_sets, _p(coef), coef.numel(), _p(planes), planes.numel(), _p(pixels), pixels.numel(),
+            max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1), int(stages), _p(status), _stream())
+    if check:
+        st = status.cpu()                      # one small D2H on the current stream; it also ends the workspaces' use
+        bad = st.nonzero().flatten().tolist()
+        if bad:
+            raise JpegDecodeError([(int(si[s]), s, int(st[s])) for s in bad], pixels)
+    return status
+
+
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------
-_timeline = None          # (slots tensor [uint64 as int64], names list) while tools/graph_timeline.py is recording
+_timeline = None         # (slots tensor [uint64 as int64], names list) while tools/graph_timeline.py is recording
 
 
 def timeline_begin(device, n=64):

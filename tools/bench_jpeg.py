@@ -1,0 +1,134 @@
+"""The JPEG decoder (csrc/jpeg_decode.hip) at the sizes a user runs: B = 256 files of 500 x 375 and of 1024 x 768, quality 90,
+4:2:0, encoded here by Pillow from seeded synthetic photographs (gradients plus noise) -- or, without Pillow, read from a directory
+of .jpg files given as the argument.
+
+Per case: microseconds per batch for the whole decode (zeroing the workspace, Huffman decoding, IDCT, upsampling + colour) and per
+stage (HIP events over n rounds -- 100 by default --, three rounds alternating between the whole and the stages, best of each),
+images/s, the bytes that cross PCIe (files + tables + records) against the raw-pixel path's, the host's share (parsing and staging
+a batch), Pillow's own decode time per image on this host, and the two trunks' eval forward (ResNet-101 + ResNet-50 at 448) for the
+same 256 images in the same process: the yardstick a decode launched beside them should stay under.  One JSON line.
+
+    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks]
+"""
+import glob
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mgnns_amd import _lib, ops, synth, trunk          # noqa: E402
+from mgnns_amd.images import ImagePrep                 # noqa: E402
+
+DEV = "cuda:0"
+
+
+def arg(name, default):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+def timeit(fn, n, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n * 1e3          # us per call
+
+
+def photograph(w, h, seed):
+    rs = np.random.RandomState(seed)
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    base = np.stack([255.0 * x / (w - 1), 255.0 * y / (h - 1), 127.5 + 127.5 * np.sin((x + 2 * y) / 23.0)], 2)
+    return np.clip(base + rs.normal(0.0, 12.0, size=(h, w, 3)), 0, 255).astype(np.uint8)
+
+
+def encode(w, h, B, restart_rows):
+    from PIL import Image
+    distinct = []
+    for k in range(8):
+        buf = io.BytesIO()
+        opts = dict(quality=90, subsampling=2)
+        if restart_rows:
+            opts["restart_marker_rows"] = restart_rows
+        Image.fromarray(photograph(w, h, k)).save(buf, "JPEG", **opts)
+        distinct.append(buf.getvalue())
+    return [distinct[i % 8] for i in range(B)]
+
+
+def case(prep, files, n):
+    B = len(files)
+    t0 = time.perf_counter()
+    headers = prep._jpeg_headers(files, None)
+    t1 = time.perf_counter()
+    args, batch = prep._jpeg_run(headers, staged_only=True)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    whole = lambda: ops.jpeg_decode(*args, check=False)
+    stage = {k: (lambda m=m: ops.jpeg_decode(*args, stages=m, check=False)) for k, m in (("entropy", 1), ("idct", 2), ("colour", 4))}
+    assert not bool(whole().any())
+    first = batch.pixels.clone()
+    once = timeit(whole, 2, warm=0)
+    if once * n > 4e6:                           # a round of more than 4 s: fewer iterations, and the result says how many
+        n = max(10, int(4e6 / once))
+    tw, ts = [], {k: [] for k in stage}
+    for _ in range(3):
+        tw.append(timeit(whole, n))
+        for k, fn in stage.items():
+            ts[k].append(timeit(fn, n))
+    whole()
+    assert torch.equal(batch.pixels, first)
+    t = min(tw)
+    h2d = int(args[0].numel()) + 8 * int(args[2].numel() + args[4].numel())
+    res = {"B": B, "iters_used": n, "us": round(t, 1), "images_per_s": round(B / t * 1e6), "stage_us": {k: round(min(v), 1) for k, v in ts.items()},
+           "segments": int(args[3].shape[0]), "table_sets": int(args[5].shape[0]), "file_MB": round(sum(len(f) for f in files) / 1e6, 2),
+           "h2d_MB": round(h2d / 1e6, 2), "raw_pixel_MB": round(batch.pixels.numel() / 1e6, 1),
+           "host_parse_ms": round((t1 - t0) * 1e3, 2), "host_stage_ms": round((t2 - t1) * 1e3, 2), "runs_us": [round(v, 1) for v in tw]}
+    try:
+        from PIL import Image
+        t0 = time.perf_counter()
+        for f in files[:64]:
+            Image.open(io.BytesIO(f)).convert("RGB")
+        res["pillow_ms_per_image"] = round((time.perf_counter() - t0) / min(64, B) * 1e3, 3)
+        assert torch.equal(batch.image(0).cpu(), torch.from_numpy(np.asarray(Image.open(io.BytesIO(files[0])).convert("RGB"))))
+    except ImportError:
+        pass
+    return res, t
+
+
+def main():
+    B, n, rr = arg("--batch", 256), arg("--iters", 100), arg("--restart-rows", 0)
+    built = _lib.check_sources("tools/bench_jpeg.py")
+    res = {"bench": "jpeg_decode", "device": torch.cuda.get_device_name(0), "sources": built, "iters": n, "restart_rows": rr}
+    prep = ImagePrep(448, device=DEV)
+    times = {}
+    dirs = [a for a in sys.argv[1:] if os.path.isdir(a)]
+    if dirs:
+        paths = sorted(glob.glob(os.path.join(dirs[0], "*.jpg")))
+        files = [open(paths[i % len(paths)], "rb").read() for i in range(B)]
+        res["files"], times["files"] = case(prep, files, n)
+    else:
+        for name, (w, h) in (("500x375", (500, 375)), ("1024x768", (1024, 768))):
+            res[name], times[name] = case(prep, encode(w, h, B, rr), n)
+    if "--no-trunks" not in sys.argv:
+        obj = trunk.ResNetFeatures(synth.fill_trunk_(trunk.resnet101(), 1)).to(DEV).eval()
+        place = trunk.ResNetFeatures(synth.fill_trunk_(trunk.resnet50(365), 2)).to(DEV).eval()
+        img = torch.randn(B, 3, 448, 448, device=DEV)
+        with torch.no_grad():
+            t = timeit(lambda: (obj(img), place(img)), 10, warm=2)
+        res["trunks_eval_us"] = round(t, 1)
+        res["ratio_to_trunks"] = {k: round(v / t, 3) for k, v in times.items()}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
