@@ -36,15 +36,16 @@ typedef struct mgnns_comm_s* mgnns_comm_t;      /* an RCCL communicator (one per
 #define MGNNS_ERR_UNSUPP  (-3)
 
 /* Status word of the persistent launches.  mgnns_label_gcn_fwd hands work between the workgroups of ONE launch through an
- * in-order item queue, the fused channel / layer tails exchange partial results inside clusters of adjacent workgroups; none
- * of them needs the whole grid resident, and every wait is bounded: a wait that runs out (a device in trouble, a debugger
+ * in-order item queue (the fused channel / layer tails pass partial results inside clusters of adjacent workgroups without
+ * anybody waiting: the last arriver finishes the tile); nothing
+ * needs the whole grid resident, and every wait is bounded: a wait that runs out (a device in trouble, a debugger
  * holding a wave) writes one of the codes below into the registered word and the launch drains instead of hanging.  The next
  * persistent launch of the process returns MGNNS_ERR_LAUNCH with the story in mgnns_last_error() and clears the word;
  * mgnns_take_status() reads-and-clears it explicitly (e.g. after a stream synchronise).
  * host_pinned: 4 bytes of host memory that the device can write (hipHostMalloc / a pinned torch tensor), alive until replaced;
  * NULL unregisters.  Without a registered word the waits are still bounded, only the report is lost. */
 #define MGNNS_STATUS_LABEL_GCN_TIMEOUT 1
-#define MGNNS_STATUS_CLUSTER_TIMEOUT   2
+#define MGNNS_STATUS_CLUSTER_TIMEOUT   2      /* (no launch raises it any more: no cluster exchange waits) */
 #define MGNNS_STATUS_BAD_PLAN          3      /* a masked attention launch was handed a plan of another kind / batch: it did nothing */
 int mgnns_set_status_word(int32_t* host_pinned);
 int mgnns_take_status(void);
@@ -302,7 +303,8 @@ int mgnns_label_tail_fwd(const float* x, int B, int C, const float* pooled, int 
  * G [C,K_pool], w_k, w_v [hid,C], Wc [N5,hid], x_linear.weight [n_out, NLQ*N5], w_qs.weight [HK_next, hid] (last pair may
  * be NULL; lo buffers are not read with terms = 1).  C <= 384, K_pool % 64 == 0, hid <= 320, N5 <= 128, n_out <= 384.
  * cluster_scratch / cluster_counters (both or neither; terms = 3 only): with them FOUR workgroups share each 16-sample
- * tile (read-out K and next-query columns divided, partial read-outs exchanged through the scratch):
+ * tile's read-out (K divided, partial read-outs passed through the scratch); the one that arrives LAST finishes the tile
+ * alone (nobody waits), and the next query runs as a second small launch behind the tail, inside this call:
  * scratch >= ceil(B/16) * 4 * 24576 B, 16-byte aligned; counters = 2 * ceil(B/16) ints, ZERO before the first launch
  * (every launch leaves them zero).  One (scratch, counters) pair must not be shared by launches that may run concurrently.
  */

@@ -306,18 +306,20 @@ __device__ __forceinline__ unsigned pk2(float a, float b) { return mg_bf16(a) | 
 // fusion stacks, every bf16 stage of this chain costs ~1e-2 there).  TERMS = 3 (default): split-bf16 operands, three MFMAs
 // per product, fp32-class accuracy at twice the weight bytes -- still one launch.
 //
-// CL = 4 (split-bf16 only): a CLUSTER of four workgroups shares a 16-sample tile.  The two wide phases are divided --
-// rank r contracts the r-th quarter of the read-out's K and takes a quarter of the next query's column tiles -- and the
-// narrow middle (K/V, label loop, x_linear: 44 % of the single-workgroup time) is recomputed by every rank.  The read-out
-// partials cross through global memory without fences: system-scope write-through stores, vmcnt(0), ONE relaxed agent-scope
-// arrival count per workgroup, cache-bypassing loads; every rank adds the four partials in the same order, so the ranks hold
-// identical x.  A departure count lets the last rank to finish reading re-arm both counters for the next launch.
+// CL = 4 (split-bf16 only): a CLUSTER of four workgroups shares a 16-sample tile's read-out -- rank r contracts the r-th
+// quarter of its K.  The partials cross through global memory without fences, exactly as in mg_tail::tail_bf16_body's K-split:
+// system-scope write-through stores, vmcnt(0), ONE relaxed agent-scope arrival per workgroup, cache-bypassing loads.  Nobody
+// waits: the three ranks that do not arrive last are done there, the LAST arriver re-arms the tile's counter, adds the four
+// partials in rank order (whichever rank it is, so x keeps its bits) and runs the narrow middle (K/V, label loop, x_linear)
+// for the tile alone -- once per tile, not once per rank, and with no co-residency assumption.  The next query is not part of
+// this form: label_next_q_kernel (below) computes it from `out` in a second launch behind this one, over as many small
+// workgroups per tile as its column tiles fill.
 template <int TERMS, int CL>
 __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __restrict__ pooled, int B, int n_parts, int KP, int C,
                                                                  const float* __restrict__ Q, int NLQ, int n_heads, int dh,
                                                                  LabelW w, int N5, int NO, float* __restrict__ out, int HKn,
                                                                  float* __restrict__ qh_next, float* __restrict__ xpart,
-                                                                 int* __restrict__ counters, int* __restrict__ status) {
+                                                                 int* __restrict__ counters) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];
     constexpr int NH = TERMS == 3 ? 4 : 1;                              // passes over the read-out's K (LDS holds K / NH of pooled)
     constexpr int LO = TERMS == 3 ? 1 : 0;
@@ -395,11 +397,9 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
         if (LO) touch(w.wc_l, NT5, KSh, 0, KSh);
         touch(w.xl_h, NTo, KSf, 0, KSf);
         if (LO) touch(w.xl_l, NTo, KSf, 0, KSf);
-        // (the next query's column tiles of THIS rank only: slots q_lo .. q_hi of eight tiles, computed again below)
-        const int qs_ = (NTq_ + 7) / 8, qp_ = (qs_ + CL - 1) / CL;
-        const int qt_lo = crank * qp_ * 8, qt_hi = (crank * qp_ + qp_) * 8 < NTq_ ? (crank * qp_ + qp_) * 8 : NTq_;
-        touch(w.wq_h, qt_hi - qt_lo, KSh, 0, KSh, qt_lo);
-        if (LO) touch(w.wq_l, qt_hi - qt_lo, KSh, 0, KSh, qt_lo);
+        // (the next query is not part of the cluster form)
+        if (CL == 1) touch(w.wq_h, NTq_, KSh, 0, KSh);
+        if (CL == 1 && LO) touch(w.wq_l, NTq_, KSh, 0, KSh);
     }
 #endif
     for (int i = tid; i < (1 + LO) * LT_ROWS * (sxc + shc); i += LT_THR) s_xh[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -438,33 +438,31 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
         __syncthreads();                               // every wave is done reading this part of pooled
     }
     LT_STAMP(2);
-    ring_prime(ring, KSx, w.wk_h, w.wk_l, NTh, wave, lane, 0);           // w_k flies through the conversion / exchange of x
+    // partial [tile][rank][wave][t][lane] x 16 B: a lane writes and reads exactly the accumulator slots it owns
+    const __amdgpu_buffer_rsrc_t xp = mg_buffer(CL > 1 ? xpart + (size_t)tile * CL * (8 * 3 * 64 * 4) : nullptr, CL > 1 ? CL * 8 * 3 * 64 * 16 : 0);
+    const int slot = (wave * 3 * 64 + lane) * 16;
     if (CL > 1) {
-        // partial [tile][rank][wave][t][lane] x 16 B: a lane writes and reads exactly the accumulator slots it owns
-        const __amdgpu_buffer_rsrc_t xp = mg_buffer(xpart + (size_t)tile * CL * (8 * 3 * 64 * 4), CL * 8 * 3 * 64 * 16);
-        const int slot = (wave * 3 * 64 + lane) * 16;
 #pragma unroll
         for (int t = 0; t < 3; ++t)
             if (wave + 8 * t < NTc)
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, acc[t]), xp, slot + t * 64 * 16, crank * (8 * 3 * 64 * 16), 17);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this thread's write-through stores are acknowledged
         __syncthreads();
+        int* s_flag = reinterpret_cast<int*>(s_k);             // (zeroed above, written by the K projection below)
         if (tid == 0) {
-            __hip_atomic_fetch_add(&counters[2 * tile], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // The ranks of a tile are ADJACENT in dispatch order, so at most one cluster of a launch straddles the edge of what is
-            // resident and everything in front of it retires without waiting for anybody: no co-residency requirement beyond
-            // in-order dispatch.  The wait is bounded all the same (a device in trouble must not become a hang): when it runs out
-            // the rank goes on with what has arrived and raises the library's status word (mgnns_set_status_word).
-            int spins = 0;
-            while (__hip_atomic_load(&counters[2 * tile], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < CL) {
-                if (++spins > (1 << 24)) {
-                    if (status) __hip_atomic_store(status, MGNNS_STATUS_CLUSTER_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
+            // the tile has ONE counter (the first of the two slots the scratch helper gives a tile); nothing ever waits on it
+            const int old = __hip_atomic_fetch_add(&counters[2 * tile], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int last = old == CL - 1;
+            if (last) __hip_atomic_store(&counters[2 * tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+            *s_flag = last;
         }
         __syncthreads();
+        if (!*s_flag) return;                                  // three of the four ranks are done: their partials are in the scratch
+        __syncthreads();
+        if (tid == 0) *s_flag = 0;                             // (s_k's padding stays zero)
+    }
+    ring_prime(ring, KSx, w.wk_h, w.wk_l, NTh, wave, lane, 0);           // w_k flies through the conversion / exchange of x
+    if (CL > 1) {
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             f32x4 pr[CL];
@@ -472,11 +470,10 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
             for (int rk = 0; rk < CL; ++rk)
                 pr[rk] = wave + 8 * t < NTc ? __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xp, slot + t * 64 * 16, rk * (8 * 3 * 64 * 16), 17))
                                             : f32x4{0.f, 0.f, 0.f, 0.f};
-            acc[t] = pr[0];
+            acc[t] = pr[0];                                    // rank order, whichever rank arrived last
 #pragma unroll
             for (int rk = 1; rk < CL; ++rk) acc[t] += pr[rk];
         }
-        // (the loads above are complete once acc is consumed below; the departure count follows the conversion barrier)
     }
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
@@ -488,13 +485,6 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
     }
     for (int i = tid; i < (1 + LO) * LT_ROWS * spf; i += LT_THR) s_ph[i] = make_uint4(0u, 0u, 0u, 0u);   // -> flatten buffer, zero padded
     __syncthreads();
-    if (CL > 1 && tid == 0) {      // every thread of this rank has consumed the partials: the last rank to get here re-arms the counters
-        const int old = __hip_atomic_fetch_add(&counters[2 * tile + 1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == CL - 1) {
-            __hip_atomic_store(&counters[2 * tile], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&counters[2 * tile + 1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
     // ---- K, V ----------------------------------------------------------------------------------------------------------------
     LT_STAMP(3);
     ring_gemm(acc, ring, s_xh, s_xl, sxc, KSx, w.wk_h, w.wk_l, lane);
@@ -587,10 +577,10 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
     LT_STAMP(5);
     ring_gemm(acc, ring, s_fh, s_fl, sfc, KSf, w.xl_h, w.xl_l, lane);
     LT_STAMP(6);
-    // the next query's column-tile slots (8 tiles each) are divided over the cluster ranks
-    const int q_slots = ((HKn + 15) / 16 + 7) / 8, q_per = (q_slots + CL - 1) / CL;
-    const int q_lo = crank * q_per, q_hi = q_lo + q_per < q_slots ? q_lo + q_per : q_slots;
-    if (w.wq_h) ring_prime(ring, KSh, w.wq_h, w.wq_l, (HKn + 15) / 16, wave, lane, q_lo);
+    // the next query's column-tile slots (8 tiles each); the cluster form leaves the next query to label_next_q_kernel
+    const bool next_q = CL == 1 && w.wq_h;
+    const int q_lo = 0, q_hi = ((HKn + 15) / 16 + 7) / 8;
+    if (next_q) ring_prime(ring, KSh, w.wq_h, w.wq_l, (HKn + 15) / 16, wave, lane, q_lo);
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
         const int nt = wave + 8 * t, n = nt * 16 + ccol;
@@ -600,13 +590,13 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
             for (int r = 0; r < 4; ++r) {
                 const int gr = r0 + crow + r;
                 const float v = acc[t][r] + b0;
-                if (gr < B && crank == 0) out[(size_t)gr * NO + n] = v;
-                if (w.wq_h) put(oh16, ol16, (crow + r) * shc * 8 + n, v);          // NO == hid (launcher)
+                if (gr < B) out[(size_t)gr * NO + n] = v;
+                if (next_q) put(oh16, ol16, (crow + r) * shc * 8 + n, v);          // NO == hid (launcher)
             }
         }
     }
     // ---- qh = w_qs(out) + b -----------------------------------------------------------------------------------------------------
-    if (w.wq_h) {
+    if (next_q) {
         __syncthreads();
         const int NTq = (HKn + 15) / 16;
         for (int t0 = q_lo; t0 < q_hi; t0 += 3) {
@@ -630,6 +620,79 @@ __global__ __launch_bounds__(LT_THR) void label_tail_bf16_kernel(const float* __
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(touch_sink)::"memory");      // (long landed: keeps the register reserved up to here)
 #endif
     LT_STAMP(7);
+}
+
+// The next query of the cluster form, qh = w_qs(out) + b (submodules.py:63-66), as a launch of its own behind the tail: the column
+// tiles of a 16-sample tile are independent, so every (sample tile, column tile) pair is ONE WAVE -- a workgroup of 64 threads with
+// no LDS and few registers, which finds room on a CU whose LDS a chip-filling workgroup of another stream holds entirely (the
+// attention core and the bank kernel leave 64-80 VGPRs per SIMD and no LDS: a launch that asks for 21 KB of LDS took 21 us next to
+// them, 8 us alone).  A lane reads its own A fragments -- row (lane & 15) of the tile's 16 rows of `out`, eight floats per
+// k-step: the fp32 values the tail stored, the same values the single-workgroup form splits in LDS -- splits them hi / lo the
+// same way and contracts over k in the same order, three MFMAs per k-step, so qh_next has the bits of the single-workgroup form
+// given the same `out`.
+constexpr int LQ_PF = 2;                     // k-steps in flight (16 VGPRs each)
+
+template <bool VEC>      // VEC: a row's 4-float groups are 16-byte aligned (n_out % 4 == 0, `out` aligned): 16-byte loads
+__global__ __launch_bounds__(64) void label_next_q_kernel(const float* __restrict__ out, int B, int NO,
+                                                          const unsigned short* __restrict__ wq_h,
+                                                          const unsigned short* __restrict__ wq_l,
+                                                          const float* __restrict__ bq, int HKn, float* __restrict__ qh_next,
+                                                          int NTq) {
+    const int lane = threadIdx.x;
+    const int tile = (int)blockIdx.x / NTq, nt = (int)blockIdx.x % NTq;
+    const int r0 = tile * LT_ROWS, KSh = (NO + 31) / 32;
+    const int row = r0 + (lane & 15), kq = (lane >> 4) * 8;
+    const bool rok = row < B;                                            // rows past B: zero operands, nothing stored
+    const float* prow = out + (size_t)(rok ? row : 0) * NO;
+    const uint4* Wh = reinterpret_cast<const uint4*>(wq_h) + (size_t)nt * KSh * 64 + lane;
+    const uint4* Wl = reinterpret_cast<const uint4*>(wq_l) + (size_t)nt * KSh * 64 + lane;
+    auto load = [&](int ks, f32x4& a0, f32x4& a1, uint4& wh, uint4& wl) {
+        wh = Wh[(size_t)ks * 64];
+        wl = Wl[(size_t)ks * 64];
+        const int k = ks * 32 + kq;
+        a0 = a1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (VEC) {
+            if (rok && k < NO) a0 = *reinterpret_cast<const f32x4*>(prow + k);
+            if (rok && k + 4 < NO) a1 = *reinterpret_cast<const f32x4*>(prow + k + 4);
+        } else if (rok) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (k + j < NO) a0[j] = prow[k + j];
+                if (k + 4 + j < NO) a1[j] = prow[k + 4 + j];
+            }
+        }
+    };
+    f32x4 ra0[LQ_PF], ra1[LQ_PF];
+    uint4 rh[LQ_PF], rl[LQ_PF];
+#pragma unroll
+    for (int d = 0; d < LQ_PF; ++d) load(d < KSh ? d : 0, ra0[d], ra1[d], rh[d], rl[d]);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int ks0 = 0; ks0 < KSh; ks0 += LQ_PF) {
+#pragma unroll
+        for (int d = 0; d < LQ_PF; ++d) {
+            const int ks = ks0 + d;
+            if (ks < KSh) {                                              // wave-uniform
+                const float x[8] = {ra0[d][0], ra0[d][1], ra0[d][2], ra0[d][3], ra1[d][0], ra1[d][1], ra1[d][2], ra1[d][3]};
+                const uint4 ch = rh[d], cl = rl[d];
+                if (ks + LQ_PF < KSh) load(ks + LQ_PF, ra0[d], ra1[d], rh[d], rl[d]);
+                uint4 hq, lq;
+                mg_split8(x, hq, lq);
+                const bf16x8 ah = __builtin_bit_cast(bf16x8, hq), al = __builtin_bit_cast(bf16x8, lq);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, ch), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, __builtin_bit_cast(bf16x8, cl), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, __builtin_bit_cast(bf16x8, ch), acc, 0, 0, 0);
+            }
+        }
+    }
+    const int crow = (lane >> 4) * 4, n = nt * 16 + (lane & 15);
+    if (n < HKn) {
+        const float b0 = bq ? bq[n] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int gr = r0 + crow + r;
+            if (gr < B) qh_next[(size_t)gr * HKn + n] = acc[r] + b0;
+        }
+    }
 }
 
 }  // namespace
@@ -681,22 +744,35 @@ extern "C" int mgnns_label_tail_bf16_fwd(const float* pooled, int B, int n_parts
     MG_REQUIRE(lds <= 160 * 1024, "mgnns_label_tail_bf16_fwd: K_pool=%d, C=%d need %zu B of LDS (> 160 KiB)", K_pool, C, lds);
     MG_REQUIRE((cluster_scratch != nullptr) == (cluster_counters != nullptr), "mgnns_label_tail_bf16_fwd: cluster scratch and counters go together");
     MG_REQUIRE(!cluster_scratch || mg_aligned16(cluster_scratch), "mgnns_label_tail_bf16_fwd: cluster scratch must be 16-byte aligned");
+    // (the cluster form itself waits for nothing and raises nothing; it still reports a word an EARLIER persistent launch raised)
     if (cluster_scratch)
-        if (int rc = mg_check_status("mgnns_label_tail_bf16_fwd")) return rc;   // a bounded wait of an earlier persistent launch ran out
+        if (int rc = mg_check_status("mgnns_label_tail_bf16_fwd")) return rc;
     MG_DYN_LDS((label_tail_bf16_kernel<1, 1>), 160 * 1024);
     MG_DYN_LDS((label_tail_bf16_kernel<3, 1>), 160 * 1024);
     MG_DYN_LDS((label_tail_bf16_kernel<3, 4>), 160 * 1024);
     const int tiles = (B + LT_ROWS - 1) / LT_ROWS;
     const dim3 blk(LT_THR);
-    if (terms == 3 && cluster_scratch)
+    if (terms == 3 && cluster_scratch) {
         hipLaunchKernelGGL((label_tail_bf16_kernel<3, 4>), dim3(tiles * 4), blk, lds, (hipStream_t)stream, pooled, B, n_parts, K_pool, C, Q, NLQ,
-                           n_heads, dh, w, N5, n_out, out, HK_next, qh_next, cluster_scratch, cluster_counters, mg_status_word());
-    else if (terms == 3)
+                           n_heads, dh, w, N5, n_out, out, HK_next, qh_next, cluster_scratch, cluster_counters);
+        if (w.wq_h) {
+            MG_CHECK_LAUNCH("mgnns_label_tail_bf16_fwd");
+            // the next query, right behind the tail on the same stream: one wave per (sample tile, column tile)
+            const int NTq = (HK_next + 15) / 16;
+            if (n_out % 4 == 0 && mg_aligned16(out))
+                hipLaunchKernelGGL(label_next_q_kernel<true>, dim3(tiles * NTq), dim3(64), 0, (hipStream_t)stream, out, B, n_out, w.wq_h, w.wq_l,
+                                   w.bq, HK_next, qh_next, NTq);
+            else
+                hipLaunchKernelGGL(label_next_q_kernel<false>, dim3(tiles * NTq), dim3(64), 0, (hipStream_t)stream, out, B, n_out, w.wq_h, w.wq_l,
+                                   w.bq, HK_next, qh_next, NTq);
+        }
+    } else if (terms == 3) {
         hipLaunchKernelGGL((label_tail_bf16_kernel<3, 1>), dim3(tiles), blk, lds, (hipStream_t)stream, pooled, B, n_parts, K_pool, C, Q, NLQ, n_heads, dh,
-                           w, N5, n_out, out, HK_next, qh_next, (float*)nullptr, (int*)nullptr, (int*)nullptr);
-    else
+                           w, N5, n_out, out, HK_next, qh_next, (float*)nullptr, (int*)nullptr);
+    } else {
         hipLaunchKernelGGL((label_tail_bf16_kernel<1, 1>), dim3(tiles), blk, lds, (hipStream_t)stream, pooled, B, n_parts, K_pool, C, Q, NLQ, n_heads, dh,
-                           w, N5, n_out, out, HK_next, qh_next, (float*)nullptr, (int*)nullptr, (int*)nullptr);
+                           w, N5, n_out, out, HK_next, qh_next, (float*)nullptr, (int*)nullptr);
+    }
     MG_CHECK_LAUNCH("mgnns_label_tail_bf16_fwd");
     return 0;
 }

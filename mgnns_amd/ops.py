@@ -910,7 +910,8 @@ LABEL_TAIL_CLUSTER = True
 def label_tail_bf16(pooled, g_pair, Q, n_heads, packed, next_q=None, terms=3, cluster=None):
     """bf16-mode fused channel tail (mgnns_label_tail_bf16_fwd): pooled [B,parts,K] fp32, g_pair = pack_weight_bf16_split(G
     [C,K]); packed = dict(wk, wv, wc, xl = (hi, lo) pairs of pack_weight_bf16_split, bk, bv, bc, bxl, n5, n_out, C);
-    next_q = ((hi, lo), bq, HK).  terms = 1 plain bf16 | 3 split-bf16.  cluster: four workgroups per 16-sample tile
+    next_q = ((hi, lo), bq, HK).  terms = 1 plain bf16 | 3 split-bf16.  cluster: four workgroups per 16-sample tile split the
+    read-out, the last to arrive finishes the tile, the next query is a second launch inside the same C call
     (terms = 3; default on, ops.LABEL_TAIL_CLUSTER = False turns it off); the exchange scratch lives in `packed`, one per
     channel, so the two channels' launches never share one.  -> out [B,n_out] (or (out, qh))."""
     import ctypes
