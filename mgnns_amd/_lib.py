@@ -1,185 +1,93 @@
-"""ctypes binding of libmgnns_hip.so (include/mgnns_hip.h).
+"""ctypes binding of libmgnns_hip.so, derived from include/mgnns_hip.h.
+
+The header is the one place an entry point's signature is written down: the compiler checks every definition against it (each
+.hip includes it), and this module parses it at import into the argtypes, restypes and integer constants of the binding.
 
 The library is required: there is no CPU or PyTorch fallback for any operator.  `lib()`
 raises if the shared object has not been built (python -m mgnns_amd.build).
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
-ABI_VERSION = 26
-
-_c = ctypes
-_P = _c.c_void_p
-_I = _c.c_int
-_L = _c.c_int64
-_F = _c.c_float
-_SZ = _c.c_size_t
-_U64 = _c.c_uint64
-_PP = _c.POINTER(_c.c_void_p)
-
-# name -> argtypes, in the order of include/mgnns_hip.h
-SIGNATURES = {
-    "mgnns_textgcn_fwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _P, _P],
-    "mgnns_bilstm_fwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _PP, _PP, _PP, _PP, _P, _SZ, _P, _P, _I, _P],
-    "mgnns_bilstm_bf16_fwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _PP, _PP, _PP, _PP, _P, _SZ, _P, _P, _I, _P, _P],
-    "mgnns_bilstm_bf16_prepack": [_PP, _PP, _I, _I, _I, _P, _P],
-    "mgnns_bilstm_bf16_fold_embedding": [_P, _I, _I, _I, _P, _P, _P, _SZ, _P, _P],
-    "mgnns_bilstm_bf16_table_fwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _PP, _PP, _PP, _PP, _P, _SZ, _P, _P, _I, _P, _P, _P],
-    "mgnns_embedding_fwd": [_P, _L, _P, _I, _I, _P, _P],
-    "mgnns_gen_adj": [_P, _I, _P, _P, _P, _P, _P, _P],
-    "mgnns_dense_to_csr": [_P, _I, _P, _P, _P, _P],
-    "mgnns_matmul_fwd": [_P, _I, _I, _P, _I, _P, _I, _P, _SZ, _P],
-    "mgnns_spmm_csr_fwd": [_P, _P, _P, _I, _P, _I, _P, _I, _P],
-    "mgnns_spmm_csr_bias_fwd": [_P, _P, _P, _I, _P, _I, _P, _P, _I, _P],
-    "mgnns_cast_bf16": [_P, _c.c_longlong, _P, _P],
-    "mgnns_spmm_csr_bf16_fwd": [_P, _P, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P],
-    "mgnns_spmm_tiled_bf16_fwd": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P],
-    "mgnns_linear_fwd": [_P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _SZ, _P],
-    "mgnns_imgbank_pool_fwd": [_P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P],
-    "mgnns_imgbank_pack_weights_bf16": [_P, _I, _I, _P, _P],
-    "mgnns_imgbank_pool_bf16_fwd": [_P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P, _P],
-    "mgnns_imgbank_set_form": [_I],
-    "mgnns_textgcn_set_form": [_I],
-    "mgnns_head_diff_fwd": [_P, _I, _I, _I, _P, _P],
-    "mgnns_classifier_part_fwd": [_P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P],
-    "mgnns_imgbank_pool_split_fwd": [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P],
-    "mgnns_transpose_pad": [_P, _I, _I, _P, _I, _P],
-    "mgnns_label_attn_core_fwd": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "mgnns_label_attn_core_masked_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "mgnns_label_gcn_fwd": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _SZ, _I, _P],
-    "mgnns_label_gcn_memo_fwd": [_P, _I, _P, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _SZ, _P, _SZ, _I, _P],
-    "mgnns_classifier_head_fwd": [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P],
-    "mgnns_label_tail_bf16_fwd": [_P, _I, _I, _I, _I, _I, _PP, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P],
-    "mgnns_label_tail_fwd": [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P,
-                             _I, _P, _P],
-    "mgnns_sq_mha_core_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "mgnns_sq_mha_pack_weights_bf16": [_P, _P, _I, _I, _I, _P, _P],
-    "mgnns_cast_pad_bf16": [_P, _L, _I, _I, _P, _P],
-    "mgnns_sq_mha_core_bf16_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "mgnns_sq_mha32_pack_weights_bf16": [_P, _P, _I, _I, _I, _P, _P],
-    "mgnns_sq_mha32_plan": [_P, _I, _I, _P, _P],
-    "mgnns_sq_mha32_core_bf16_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "mgnns_sq_mha_pack_weights_split": [_P, _P, _I, _I, _I, _P, _P],
-    "mgnns_split_pad_bf16": [_P, _L, _I, _I, _P, _P, _P],
-    "mgnns_sq_mha_core_split_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "mgnns_sq_mha_split_plan": [_P, _I, _I, _P, _P],
-    "mgnns_sq_mha_folded_fwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P, _P, _P],
-    "mgnns_pack_weight_f32": [_P, _I, _I, _P, _P],
-    "mgnns_mha_tail_fwd": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _P, _P],
-    "mgnns_pack_weight_bf16_split": [_P, _I, _I, _P, _P, _P],
-    "mgnns_mha_tail_bf16_fwd": [_P, _I, _P, _I, _I, _I, _PP, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _P, _I, _P, _P, _P],
-    "mgnns_mha_tail_c16_fwd": [_P, _I, _P, _I, _I, _PP, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _P, _I, _P, _P, _P],
-    "mgnns_sq_mha_folded_bf16_fwd": [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P],
-    "mgnns_transpose_cast_bf16": [_P, _I, _I, _I, _P, _P],
-    "mgnns_gemm_bf16_nt_fwd": [_P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _SZ, _P],
-    "mgnns_gemm_bf16_set_form": [_I],
-    "mgnns_gemm_bf16_pick_form": [_I, _I, _I, _I, _I],
-    "mgnns_softmax_argmax_fwd": [_P, _I, _I, _P, _P, _P, _P, _P],
-    "mgnns_conv_fold_bn_bf16": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P],
-    "mgnns_stem_conv7_fwd": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "mgnns_maxpool3x3s2_nhwc_fwd": [_P, _I, _I, _I, _I, _P, _P],
-    "mgnns_conv_bf16_nhwc_fwd": [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P],
-    "mgnns_conv_transpose_pack_bf16": [_P, _I, _I, _I, _I, _P, _P],
-    "mgnns_conv_dgrad_bf16_nhwc": [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mgnns_conv_wgrad_bf16_nhwc": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
-    "mgnns_conv_bn_unfold": [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
-    "mgnns_map_grad_relu_nhwc_bf16": [_P, _P, _I, _I, _I, _P, _P],
-    "mgnns_bn_stats_bf16": [_P, _I, _I, _F, _c.c_double, _P, _P, _P, _P, _P, _P, _SZ, _P],
-    "mgnns_bn_apply_bf16": [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "mgnns_bn_backward_bf16": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
-    "mgnns_stem_conv7_raw_fwd": [_P, _I, _I, _I, _P, _P, _P],
-    "mgnns_stem_wgrad": [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P],
-    "mgnns_maxpool3x3s2_nhwc_bwd": [_P, _P, _I, _I, _I, _I, _I, _P, _P],
-    "mgnns_image_prep_fwd": [_P, _SZ, _P, _I, _P, _I, _P, _SZ, _P, _I, _I, _P, _P],
-    "mgnns_jpeg_parse": [_P, _SZ, _I, _P, _P, _P, _SZ, _P],
-    "mgnns_jpeg_decode_fwd": [_P, _SZ, _P, _I, _P, _I, _P, _I, _P, _SZ, _P, _SZ, _P, _SZ, _c.c_longlong, _c.c_longlong, _I, _P, _P],
-    "mgnns_label_gcn_supported": [_I, _I, _I, _I, _I],
-    "mgnns_label_tail_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
-    "mgnns_label_tail_bf16_supported": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "mgnns_xcd_probe": [_P],
-    "mgnns_set_status_word": [_P],
-    "mgnns_take_status": [],
-    "mgnns_debug_slabcopy": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "mgnns_debug_stamp": [_P, _I, _P],
-    "mgnns_debug_spin": [_I, _P, _I, _P],
-    "mgnns_layernorm_fwd": [_P, _I, _I, _P, _P, _F, _P, _P],
-    "mgnns_mha_train_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _U64, _F, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mgnns_mha_train_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                            _P, _SZ, _P],
-    "mgnns_wgrad_fwd": [_P, _I, _I, _P, _I, _P, _P, _P, _SZ, _P],
-    "mgnns_drop_res_ln_fwd": [_P, _P, _I, _I, _P, _P, _F, _U64, _I, _F, _P, _P, _P, _P, _P],
-    "mgnns_drop_res_ln_bwd": [_P, _P, _P, _P, _P, _I, _I, _P, _F, _F, _P, _P, _P, _P, _P],
-    "mgnns_train_eltwise": [_I, _P, _P, _L, _P, _P],
-    "mgnns_imgbank_wgrad": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
-    "mgnns_map_argmax": [_P, _I, _I, _I, _P, _P],
-    "mgnns_imgbank_dgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
-    "mgnns_imgbank_wgrad_split": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P],
-    "mgnns_imgbank_dgrad_split": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P],
-    "mgnns_label_attn_train_fwd": [_P, _P, _P, _I, _I, _I, _I, _U64, _F, _P, _P, _P, _P],
-    "mgnns_label_attn_train_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _SZ, _P],
-    "mgnns_dropout_fwd": [_P, _L, _U64, _I, _F, _P, _P, _P],
-    "mgnns_dropout_bwd": [_P, _P, _L, _F, _P, _P],
-    "mgnns_dropout_mask": [_U64, _I, _F, _L, _P, _P],
-    "mgnns_bilstm_train_fwd": [_P, _P, _I, _I, _P, _I, _I, _I, _I, _PP, _PP, _PP, _PP, _U64, _F, _P, _I, _P, _P, _P, _P, _P, _P,
-                               _SZ, _P],
-    "mgnns_bilstm_train_bwd_rec": [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
-    "mgnns_bilstm_train_hprev": [_P, _P, _I, _I, _P, _I, _P, _P],
-    "mgnns_bilstm_train_unpack_drop": [_P, _P, _L, _I, _I, _U64, _F, _P, _P],
-    "mgnns_gather_rows": [_P, _I, _I, _P, _L, _P, _P],
-    "mgnns_keyed_row_sum": [_P, _P, _L, _P, _I, _L, _L, _P, _L, _P],
-    "mgnns_textgcn_train_supported": [_I, _I, _I, _I],
-    "mgnns_textgcn_train_fwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _U64, _F, _P, _P, _P, _P],
-    "mgnns_textgcn_train_bwd": [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _U64, _F, _P, _P, _P, _P, _P, _P, _P, _P],
-    "mgnns_comm_unique_id": [_P, _SZ],
-    "mgnns_comm_init_rank": [_I, _I, _P, _SZ, _PP],
-    "mgnns_comm_init_all": [_I, _P, _PP],
-    "mgnns_comm_info": [_P, _c.POINTER(_I), _c.POINTER(_I)],
-    "mgnns_allgather_logits": [_P, _P, _I, _I, _P, _P],
-    "mgnns_comm_group_start": [],
-    "mgnns_comm_group_end": [],
-    "mgnns_comm_destroy": [_P],
-}
-
-# size_t-returning helpers (buffer sizes the caller allocates)
-SIZE_GETTERS = {
-    "mgnns_packed_bf16_weight_bytes": [_I, _I],
-    "mgnns_packed_f32_weight_bytes": [_I, _I],
-    "mgnns_gemm_workspace_bytes": [],
-    "mgnns_gemm_bf16_workspace_bytes": [],
-    "mgnns_imgbank_packed_weight_bytes": [_I],
-    "mgnns_sq_mha_packed_weight_bytes": [_I],
-    "mgnns_sq_mha32_packed_weight_bytes": [_I],
-    "mgnns_sq_mha32_plan_ints": [_I],
-    "mgnns_sq_mha_split_packed_weight_bytes": [_I],
-    "mgnns_sq_mha_folded_workspace_bytes": [_I, _I, _I],
-    "mgnns_bilstm_workspace_bytes": [_I, _I, _I, _I],
-    "mgnns_bilstm_bf16_prepack_bytes": [_I, _I],
-    "mgnns_bilstm_bf16_table_bytes": [_I, _I],
-    "mgnns_bilstm_bf16_fold_workspace_bytes": [_I],
-    "mgnns_label_gcn_scratch_bytes": [_I, _I, _I],
-    "mgnns_label_gcn_memo_bytes": [_I, _I],
-    "mgnns_mha_tail_c16_scratch_floats": [_I, _I],
-    "mgnns_mha_train_bwd_workspace_bytes": [_I, _I, _I, _I],
-    "mgnns_wgrad_workspace_bytes": [_I, _I, _I],
-    "mgnns_imgbank_wgrad_workspace_bytes": [_I, _I, _I, _I],
-    "mgnns_imgbank_wgrad_split_workspace_bytes": [_I, _I, _I, _I],
-    "mgnns_imgbank_dgrad_split_workspace_bytes": [_I, _I, _I, _I],
-    "mgnns_label_attn_train_bwd_workspace_bytes": [_I, _I, _I, _I],
-    "mgnns_bilstm_train_workspace_bytes": [_I, _I, _I],
-    "mgnns_conv_wgrad_workspace_bytes": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "mgnns_bn_stats_workspace_bytes": [_I, _I],
-    "mgnns_bn_backward_workspace_bytes": [_I, _I],
-    "mgnns_stem_wgrad_workspace_bytes": [_I, _I, _I],
-    "mgnns_jpeg_tableset_bytes": [],
-}
-
-_lib = None
+HEADER_PATH = os.path.join(_HERE, "..", "include", "mgnns_hip.h")
 
 
 class MgnnsLibraryError(RuntimeError):
     pass
+
+
+# The closed type map: a header type outside it raises, it never binds silently.  Any single pointer is an address (callers pass
+# data_ptr() ints or None); a pointer to pointers takes a (c_void_p * n) array or a byref(handle).
+_HANDLES = ("mgnns_stream_t", "mgnns_comm_t")
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64,
+            "long long": ctypes.c_longlong, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t,
+            "mgnns_stream_t": ctypes.c_void_p, "mgnns_comm_t": ctypes.c_void_p}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_PP = ctypes.POINTER(ctypes.c_void_p)
+
+
+def _ctype(param, decl, where):
+    """One (named) parameter of a declaration -> its ctypes class."""
+    tok = [t for t in re.findall(r"\w+|\*|\S", param) if t != "const"]
+    if len(tok) > 1 and tok[-1] != "*":
+        tok.pop()                                        # the parameter's name
+    depth = tok.count("*") + (1 if tok and tok[0] in _HANDLES else 0)
+    base = " ".join(t for t in tok if t != "*")
+    if not re.fullmatch(r"[A-Za-z_]\w*( [A-Za-z_]\w*)*", base) or depth > 2 or (depth == 0 and base not in _SCALARS):
+        raise MgnnsLibraryError("%s: no ctypes mapping for the parameter '%s' of '%s'" % (where, param.strip(), decl))
+    return _SCALARS[base] if "*" not in tok else ctypes.c_void_p if depth == 1 else _PP
+
+
+def parse_header(text, where="the header"):
+    """-> ({name: (restype, [argtypes])} for every `<ret> mgnns_<name>(<params>);`, {MGNNS_<NAME>: int} for every integer #define)."""
+    text = re.sub(r"/\*.*?\*/", " ", text.replace("\\\n", " "), flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    define = r"^[ \t]*#[ \t]*define[ \t]+(MGNNS_\w+)[ \t]+\(?[ \t]*(-?\d+)[ \t]*\)?[ \t]*$"
+    constants = {n: int(v) for n, v in re.findall(define, text, flags=re.M)}
+    decls = {}
+    for stmt in re.split(r"[;{}]", re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)):
+        if "(" not in stmt:
+            continue                                     # typedefs, `extern "C"`
+        decl = " ".join(stmt.split())
+        m = re.fullmatch(r"(.+?)\s*\b(mgnns_\w+)\s*\(([^()]*)\)", decl)
+        if m is None:
+            raise MgnnsLibraryError("%s: cannot parse the declaration '%s'" % (where, decl))
+        ret, name, params = re.sub(r"\s*\*", "*", m.group(1)), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise MgnnsLibraryError("%s: no ctypes mapping for the return type '%s' of '%s'" % (where, ret, decl))
+        decls[name] = (_RETURNS[ret], [] if params == "void" else [_ctype(p, decl, where) for p in params.split(",")])
+    return decls, constants
+
+
+def _read_header(path):
+    try:
+        with open(path) as f:
+            decls, constants = parse_header(f.read(), path)
+    except OSError as e:
+        raise MgnnsLibraryError("cannot read the C header %s (%s): the binding is derived from it" % (path, e))
+    if not decls or "MGNNS_ABI_VERSION" not in constants:
+        raise MgnnsLibraryError("%s declares no mgnns_* entry point or no MGNNS_ABI_VERSION" % path)
+    return decls, constants
+
+
+_DECLS, CONSTANTS = _read_header(HEADER_PATH)
+ABI_VERSION = CONSTANTS["MGNNS_ABI_VERSION"]
+_UNCHECKED = ("mgnns_last_error", "mgnns_abi_version", "mgnns_source_fingerprint")       # bound first: lib() needs them for its own checks
+# name -> argtypes, in the order of include/mgnns_hip.h: the int-returning entry points and the size_t-returning helpers
+# (buffer sizes the caller allocates)
+SIGNATURES = {n: a for n, (r, a) in _DECLS.items() if r is ctypes.c_int and n not in _UNCHECKED}
+SIZE_GETTERS = {n: a for n, (r, a) in _DECLS.items() if r is ctypes.c_size_t}
+
+_lib = None
+_bound = {}          # name -> bound function: call() does no getattr on the CDLL per launch
+
+
+def _bind(L, name):
+    fn = getattr(L, name)          # AttributeError if the symbol is missing
+    fn.restype, fn.argtypes = _DECLS[name]
 
 
 def lib():
@@ -192,25 +100,25 @@ def lib():
             "Build it with `python -m mgnns_amd.build`." % LIB_PATH)
     import torch  # noqa: F401  -- loads libamdhip64 first so the kernels share PyTorch's HIP runtime
     L = ctypes.CDLL(LIB_PATH)
-    L.mgnns_last_error.restype = ctypes.c_char_p
-    L.mgnns_last_error.argtypes = []
-    L.mgnns_abi_version.restype = _I
-    L.mgnns_abi_version.argtypes = []
-    L.mgnns_source_fingerprint.restype = ctypes.c_char_p
-    L.mgnns_source_fingerprint.argtypes = []
+    for name in _UNCHECKED:
+        _bind(L, name)
     if L.mgnns_abi_version() != ABI_VERSION:
         raise MgnnsLibraryError("libmgnns_hip.so ABI %d != binding ABI %d; rebuild" % (L.mgnns_abi_version(), ABI_VERSION))
-    for name, args in SIZE_GETTERS.items():
-        fn = getattr(L, name)
-        fn.restype = _SZ
-        fn.argtypes = args
-    for name, args in SIGNATURES.items():
-        fn = getattr(L, name)      # AttributeError if the symbol is missing
-        fn.restype = _I
-        fn.argtypes = args
+    for name in _DECLS:
+        _bind(L, name)
     _lib = L
     _register_status_word(L)
     return L
+
+
+def call(name, *args):
+    """Call the int-returning entry point `name`; raise on a non-zero return."""
+    fn = _bound.get(name)
+    if fn is None:
+        fn = _bound[name] = getattr(lib(), name)
+    rc = fn(*args)
+    if rc != 0:
+        check(rc, name)
 
 
 def source_state():
@@ -251,9 +159,8 @@ def _register_status_word(L):
 def xcd_probe():
     """-> (ok, [XCC_ID seen for block indices b & 7 == k]): whether `blockIdx.x & 7` selects the XCD here (the placement several
     kernels use for SPEED; HIP promises nothing).  Synchronises the device: a set-up time measurement."""
-    import ctypes
     out = (ctypes.c_int32 * 9)()
-    check(lib().mgnns_xcd_probe(ctypes.addressof(out)), "mgnns_xcd_probe")
+    call("mgnns_xcd_probe", ctypes.addressof(out))
     return bool(out[0]), [int(out[1 + k]) for k in range(8)]
 
 
@@ -262,8 +169,10 @@ def take_status():
     synchronise; the next persistent launch reports a raised word on its own."""
     code = lib().mgnns_take_status()
     if code:
-        raise RuntimeError("a launch raised the library status word (status %d: 1 / 2 = a persistent launch gave up a bounded wait, "
-                           "3 = a masked attention launch refused its plan): results since then are invalid" % code)
+        raise RuntimeError("a launch raised the library status word (status %d: %d / %d = a persistent launch gave up a bounded wait, "
+                           "%d = a masked attention launch refused its plan): results since then are invalid"
+                           % (code, CONSTANTS["MGNNS_STATUS_LABEL_GCN_TIMEOUT"], CONSTANTS["MGNNS_STATUS_CLUSTER_TIMEOUT"],
+                              CONSTANTS["MGNNS_STATUS_BAD_PLAN"]))
 
 
 def check(rc, name):

@@ -18,7 +18,6 @@ class AbiComm:
 
     def __init__(self, world=1, rank=0, unique_id=None, device=None):
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        L = _lib.lib()
         if unique_id is None:
             if world != 1:
                 raise ValueError("world > 1 needs the unique id rank 0 made (AbiComm.make_unique_id)")
@@ -28,18 +27,17 @@ class AbiComm:
         buf = ctypes.create_string_buffer(bytes(unique_id), ID_BYTES)
         handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(L.mgnns_comm_init_rank(world, rank, ctypes.addressof(buf), ID_BYTES, ctypes.byref(handle)),
-                       "mgnns_comm_init_rank")
+            _lib.call("mgnns_comm_init_rank", world, rank, ctypes.addressof(buf), ID_BYTES, ctypes.byref(handle))
         self._h = handle
         w, r = ctypes.c_int(), ctypes.c_int()
-        _lib.check(L.mgnns_comm_info(self._h, ctypes.byref(w), ctypes.byref(r)), "mgnns_comm_info")
+        _lib.call("mgnns_comm_info", self._h, ctypes.byref(w), ctypes.byref(r))
         self.world, self.rank = w.value, r.value
         self._out = None
 
     @staticmethod
     def make_unique_id():
         buf = ctypes.create_string_buffer(ID_BYTES)
-        _lib.check(_lib.lib().mgnns_comm_unique_id(ctypes.addressof(buf), ID_BYTES), "mgnns_comm_unique_id")
+        _lib.call("mgnns_comm_unique_id", ctypes.addressof(buf), ID_BYTES)
         return buf.raw
 
     @classmethod
@@ -65,13 +63,13 @@ class AbiComm:
             out = self._out
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous fp32 %s tensor" % (shape,))
-        _lib.check(_lib.lib().mgnns_allgather_logits(self._h, x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(),
-                                                     torch.cuda.current_stream(x.device).cuda_stream), "mgnns_allgather_logits")
+        _lib.call("mgnns_allgather_logits", self._h, x.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(),
+                  torch.cuda.current_stream(x.device).cuda_stream)
         return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            _lib.check(_lib.lib().mgnns_comm_destroy(self._h), "mgnns_comm_destroy")
+            _lib.call("mgnns_comm_destroy", self._h)
             self._h = None
 
     def __del__(self):

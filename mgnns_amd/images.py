@@ -132,19 +132,18 @@ def parse_jpeg(data, max_extent=None, _seg=None):
     file width, height, ncomp, hs, vs (Y's sampling), tq / td / ta (table ids per component), ri, restarts (markers found), nseg, mcux,
     mcuy, ecs (begin, end), segments (int64 [nseg,2] byte ranges) and tables (the table set's bytes)."""
     from . import _lib
-    L = _lib.lib()
     a = _file_bytes(data)
     info = np.zeros(24, np.int32)
     rng = np.zeros(2, np.int64)
     tables = np.zeros(ops.jpeg_tableset_bytes(), np.uint8)
     seg = np.zeros((64, 2), np.int64) if _seg is None else _seg
     ptr = a.ctypes.data if a.size else None
-    _lib.check(L.mgnns_jpeg_parse(ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data, seg.ctypes.data,
-                                  seg.shape[0], tables.ctypes.data), "mgnns_jpeg_parse")
+    _lib.call("mgnns_jpeg_parse", ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data, seg.ctypes.data,
+              seg.shape[0], tables.ctypes.data)
     if info[0] == 0 and info[_JI["nseg"]] > seg.shape[0]:
         seg = np.zeros((int(info[_JI["nseg"]]), 2), np.int64)
-        _lib.check(L.mgnns_jpeg_parse(ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data, seg.ctypes.data,
-                                      seg.shape[0], tables.ctypes.data), "mgnns_jpeg_parse")
+        _lib.call("mgnns_jpeg_parse", ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data,
+                  seg.ctypes.data, seg.shape[0], tables.ctypes.data)
     out = dict(reason=int(info[0]), detail=int(info[1]))
     if out["reason"] == 0:
         for k in ("width", "height", "ncomp", "hs", "vs", "ri", "restarts", "nseg", "mcux", "mcuy"):

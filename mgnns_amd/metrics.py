@@ -22,9 +22,8 @@ def predict(logits, target=None, confusion=None, want_probs=True):
         ops._chk(confusion, "confusion", torch.int32, 2)
         if target.shape[0] != B or confusion.shape != (NL, NL):
             raise ValueError("target %s / confusion %s do not match logits %s" % (tuple(target.shape), tuple(confusion.shape), (B, NL)))
-    L = _lib.lib()
-    _lib.check(L.mgnns_softmax_argmax_fwd(ops._p(logits), B, NL, ops._p(probs), ops._p(pred), ops._p(target), ops._p(confusion),
-                                          ops._stream()), "mgnns_softmax_argmax_fwd")
+    _lib.call("mgnns_softmax_argmax_fwd", ops._p(logits), B, NL, ops._p(probs), ops._p(pred), ops._p(target), ops._p(confusion),
+              ops._stream())
     return probs, pred
 
 

@@ -10,7 +10,8 @@ import torch
 from . import _lib
 from .derived import derived
 
-ACT_NONE, ACT_RELU, ACT_LRELU2 = 0, 1, 2
+_C = _lib.CONSTANTS           # the #defines of include/mgnns_hip.h
+ACT_NONE, ACT_RELU, ACT_LRELU2 = _C["MGNNS_ACT_NONE"], _C["MGNNS_ACT_RELU"], _C["MGNNS_ACT_LRELU2"]
 BANK_LD = 320      # bf16 memory banks are [B, L, 320]: model dim 300 zero padded to 10 MFMA k-steps of 32
 
 
@@ -170,19 +171,20 @@ def set_timer(timer):
     _TIMER = timer
 
 
-def _launch(name, key, fn, *args):
-    """Call one C-ABI entry point, optionally bracketed by events; raise on a non-zero return."""
+def _launch(name, *args, key=(), alias=None, wanted=None):
+    """_lib.call(name, *args), bracketed by events when the timer wants `name`; they are filed under (name,) + key.
+    alias: another entry point's name, by which the timer is asked and under which the events are filed instead;
+    wanted: the name the timer is asked by, where only that differs."""
     t = _TIMER
-    if t is not None and t.wants(name):
-        a = torch.cuda.Event(enable_timing=True)
-        b = torch.cuda.Event(enable_timing=True)
-        a.record()
-        rc = fn(*args)
-        b.record()
-        t.events.setdefault(key, []).append((a, b))
-    else:
-        rc = fn(*args)
-    _lib.check(rc, name)
+    filed = alias or name
+    if t is None or not t.wants(wanted or filed):
+        return _lib.call(name, *args)
+    a = torch.cuda.Event(enable_timing=True)
+    b = torch.cuda.Event(enable_timing=True)
+    a.record()
+    _lib.call(name, *args)
+    b.record()
+    t.events.setdefault((filed,) + key, []).append((a, b))
 
 
 def _chk(t, name, dtype=torch.float32, ndim=None):
@@ -232,10 +234,8 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None):
         residual = _chk(residual.reshape(-1, N), "residual")
         if residual.shape[0] != x2.shape[0]:
             raise ValueError("residual rows mismatch")
-    L = _lib.lib()
     ws = _gemm_workspace(x.device)
-    _lib.check(L.mgnns_linear_fwd(_p(x2), x2.shape[0], K, _p(weight), _p(bias), N, _p(residual), _p(y), act,
-                                  _p(ws), ws.numel(), _stream()), "mgnns_linear_fwd")
+    _lib.call("mgnns_linear_fwd", _p(x2), x2.shape[0], K, _p(weight), _p(bias), N, _p(residual), _p(y), act, _p(ws), ws.numel(), _stream())
     return y.view(*x.shape[:-1], N)
 
 
@@ -254,9 +254,8 @@ def classifier_head(feats, weight, bias):
     if weight.shape[1] != 4 * D or bias.shape[0] != NL:
         raise ValueError("weight %s / bias %s do not match four [B,%d] features" % (tuple(weight.shape), tuple(bias.shape), D))
     out = torch.empty(B, NL, device=weight.device, dtype=torch.float32)
-    L = _lib.lib()
-    _lib.check(L.mgnns_classifier_head_fwd(_p(feats[0]), _p(feats[1]), _p(feats[2]), _p(feats[3]), B, D, _p(weight), _p(bias), NL,
-                                           _p(out), _stream()), "mgnns_classifier_head_fwd")
+    _lib.call("mgnns_classifier_head_fwd", _p(feats[0]), _p(feats[1]), _p(feats[2]), _p(feats[3]), B, D, _p(weight), _p(bias), NL, _p(out),
+              _stream())
     return out
 
 
@@ -278,9 +277,8 @@ def classifier_head_part(feat, part, nparts, weight, bias, state):
     NL = weight.shape[0]
     if weight.shape[1] != nparts * D or tuple(parts.shape) != (nparts, B, NL) or tuple(logits.shape) != (B, NL):
         raise ValueError("classifier_head_part: weight %s / state do not match %d features [B=%d,%d]" % (tuple(weight.shape), nparts, B, D))
-    L = _lib.lib()
-    _lib.check(L.mgnns_classifier_part_fwd(_p(feat), int(part), int(nparts), B, D, _p(weight), _p(bias), NL, _p(parts), _p(counter),
-                                           _p(logits), _stream()), "mgnns_classifier_part_fwd")
+    _lib.call("mgnns_classifier_part_fwd", _p(feat), int(part), int(nparts), B, D, _p(weight), _p(bias), NL, _p(parts), _p(counter),
+              _p(logits), _stream())
     return logits
 
 
@@ -291,10 +289,8 @@ def matmul(x, w, act=ACT_NONE):
     if x.shape[1] != w.shape[0]:
         raise ValueError("matmul shapes %s x %s" % (tuple(x.shape), tuple(w.shape)))
     y = torch.empty(x.shape[0], w.shape[1], device=x.device, dtype=torch.float32)
-    L = _lib.lib()
     ws = _gemm_workspace(x.device)
-    _lib.check(L.mgnns_matmul_fwd(_p(x), x.shape[0], x.shape[1], _p(w), w.shape[1], _p(y), act, _p(ws), ws.numel(),
-                                  _stream()), "mgnns_matmul_fwd")
+    _lib.call("mgnns_matmul_fwd", _p(x), x.shape[0], x.shape[1], _p(w), w.shape[1], _p(y), act, _p(ws), ws.numel(), _stream())
     return y
 
 
@@ -312,8 +308,7 @@ def gen_adj(A, want_csr=False):
         rp = torch.empty(C + 1, device=A.device, dtype=torch.int32)
         col = torch.empty(C * C, device=A.device, dtype=torch.int32)
         val = torch.empty(C * C, device=A.device, dtype=torch.float32)
-    L = _lib.lib()
-    _lib.check(L.mgnns_gen_adj(_p(A), C, _p(adj), _p(work), _p(rp), _p(col), _p(val), _stream()), "mgnns_gen_adj")
+    _lib.call("mgnns_gen_adj", _p(A), C, _p(adj), _p(work), _p(rp), _p(col), _p(val), _stream())
     return (adj, (rp, col, val)) if want_csr else adj
 
 
@@ -401,14 +396,14 @@ def label_gcn(A, inp, packed, want_packed_g=False, query=None, grid=0, memo=None
             raise ValueError("label_gcn: one memo serves one query (present or absent)")
         st.update(G=G, gh=gh, gl=gl, Q=Q)
         mem = st["state"]
-        _launch("mgnns_label_gcn_fwd", ("mgnns_label_gcn_fwd", C, packed["split"]), L.mgnns_label_gcn_memo_fwd, _p(A), C, _p(inp),
-                packed["K0"], 1 if packed["split"] else 0, _p(packed["w1"][0]), _p(packed["w1"][1]), N1, _p(packed["w2"][0]),
-                _p(packed["w2"][1]), N2, _p(G), _p(gh), _p(gl), _p(lq), nlq, _p(wq), _p(bq), hq, _p(Q), _p(ws), ws.numel(), _p(mem),
-                mem.numel(), int(grid) or LABEL_GCN_GRID, _stream())
+        _launch("mgnns_label_gcn_memo_fwd", _p(A), C, _p(inp), packed["K0"], 1 if packed["split"] else 0, _p(packed["w1"][0]),
+                _p(packed["w1"][1]), N1, _p(packed["w2"][0]), _p(packed["w2"][1]), N2, _p(G), _p(gh), _p(gl), _p(lq), nlq, _p(wq), _p(bq),
+                hq, _p(Q), _p(ws), ws.numel(), _p(mem), mem.numel(), int(grid) or LABEL_GCN_GRID, _stream(), key=(C, packed["split"]),
+                alias="mgnns_label_gcn_fwd")
         return G, ((gh, gl) if want_packed_g else None), Q
-    _launch("mgnns_label_gcn_fwd", ("mgnns_label_gcn_fwd", C, packed["split"]), L.mgnns_label_gcn_fwd, _p(A), C, _p(inp), packed["K0"],
-            1 if packed["split"] else 0, _p(packed["w1"][0]), _p(packed["w1"][1]), N1, _p(packed["w2"][0]), _p(packed["w2"][1]), N2,
-            _p(G), _p(gh), _p(gl), _p(lq), nlq, _p(wq), _p(bq), hq, _p(Q), _p(ws), ws.numel(), int(grid) or LABEL_GCN_GRID, _stream())
+    _launch("mgnns_label_gcn_fwd", _p(A), C, _p(inp), packed["K0"], 1 if packed["split"] else 0, _p(packed["w1"][0]), _p(packed["w1"][1]),
+            N1, _p(packed["w2"][0]), _p(packed["w2"][1]), N2, _p(G), _p(gh), _p(gl), _p(lq), nlq, _p(wq), _p(bq), hq, _p(Q), _p(ws),
+            ws.numel(), int(grid) or LABEL_GCN_GRID, _stream(), key=(C, packed["split"]))
     return G, ((gh, gl) if want_packed_g else None), Q
 
 
@@ -420,8 +415,7 @@ def dense_to_csr(m):
     rp = torch.empty(C + 1, device=m.device, dtype=torch.int32)
     col = torch.empty(C * C, device=m.device, dtype=torch.int32)
     val = torch.empty(C * C, device=m.device, dtype=torch.float32)
-    L = _lib.lib()
-    _lib.check(L.mgnns_dense_to_csr(_p(m), C, _p(rp), _p(col), _p(val), _stream()), "mgnns_dense_to_csr")
+    _lib.call("mgnns_dense_to_csr", _p(m), C, _p(rp), _p(col), _p(val), _stream())
     return rp, col, val
 
 
@@ -440,16 +434,14 @@ def spmm_csr(csr, x, act=ACT_NONE, out=None, bias=None):
         y = _chk(out, "out", ndim=2)
         if tuple(y.shape) != (n, x.shape[1]) or y.data_ptr() == x.data_ptr():
             raise ValueError("out must be a [%d, %d] tensor distinct from x" % (n, x.shape[1]))
-    L = _lib.lib()
     if bias is not None:
         bias = _chk(bias.reshape(-1), "bias", ndim=1)
         if bias.shape[0] != x.shape[1]:
             raise ValueError("bias has %d elements, x has %d features" % (bias.shape[0], x.shape[1]))
-        _launch("mgnns_spmm_csr_fwd", ("mgnns_spmm_csr_bias_fwd", n, x.shape[1]), L.mgnns_spmm_csr_bias_fwd, _p(rp), _p(col), _p(val), n,
-                _p(x), x.shape[1], _p(bias), _p(y), act, _stream())
+        _launch("mgnns_spmm_csr_bias_fwd", _p(rp), _p(col), _p(val), n, _p(x), x.shape[1], _p(bias), _p(y), act, _stream(),
+                key=(n, x.shape[1]), wanted="mgnns_spmm_csr_fwd")
         return y
-    _launch("mgnns_spmm_csr_fwd", ("mgnns_spmm_csr_fwd", n, x.shape[1]), L.mgnns_spmm_csr_fwd, _p(rp), _p(col), _p(val), n,
-            _p(x), x.shape[1], _p(y), act, _stream())
+    _launch("mgnns_spmm_csr_fwd", _p(rp), _p(col), _p(val), n, _p(x), x.shape[1], _p(y), act, _stream(), key=(n, x.shape[1]))
     return y
 
 
@@ -460,7 +452,7 @@ def cast_bf16(x):
     y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
     if x.numel() == 0:
         return y
-    _lib.check(_lib.lib().mgnns_cast_bf16(_p(x), x.numel(), _p(y), _stream()), "mgnns_cast_bf16")
+    _lib.call("mgnns_cast_bf16", _p(x), x.numel(), _p(y), _stream())
     return y
 
 
@@ -575,15 +567,14 @@ def spmm_bf16(adj, x, act=ACT_NONE, out=None, out_dtype=torch.bfloat16, path=Non
     ybf = 1 if y.dtype == torch.bfloat16 else 0
     if path is None:
         path = "tiled" if (adj.avg_nnz >= SparseAdjBf16.TILED_MIN_AVG_NNZ and F % 256 == 0) else "direct"
-    L = _lib.lib()
     if path == "tiled":
         wo, ent, geo = adj.plan(F, geometry)
-        _launch("mgnns_spmm_tiled_bf16_fwd", ("mgnns_spmm_tiled_bf16_fwd", adj.n_rows, F), L.mgnns_spmm_tiled_bf16_fwd,
-                _p(wo), _p(ent), geo[0], geo[1], geo[2], adj.n_rows, adj.n_cols, _p(x), F, _p(y), ybf, act, _stream())
+        _launch("mgnns_spmm_tiled_bf16_fwd", _p(wo), _p(ent), geo[0], geo[1], geo[2], adj.n_rows, adj.n_cols, _p(x), F, _p(y), ybf, act,
+                _stream(), key=(adj.n_rows, F))
     elif path == "direct":
         rp, col, val, rmap = (adj.sorted_for(F) if int(variant) == 0 else None) or (adj.row_ptr, adj.col, adj.val, None)
-        _launch("mgnns_spmm_csr_bf16_fwd", ("mgnns_spmm_csr_bf16_fwd", adj.n_rows, F), L.mgnns_spmm_csr_bf16_fwd,
-                _p(rp), _p(col), _p(val), adj.n_rows, adj.nnz, _p(x), F, _p(y), ybf, act, int(variant), _p(rmap), _stream())
+        _launch("mgnns_spmm_csr_bf16_fwd", _p(rp), _p(col), _p(val), adj.n_rows, adj.nnz, _p(x), F, _p(y), ybf, act, int(variant), _p(rmap),
+                _stream(), key=(adj.n_rows, F))
     else:
         raise ValueError("path must be None, 'direct' or 'tiled'")
     return y
@@ -594,9 +585,7 @@ def embedding(idx, table):
     _chk(idx, "idx", torch.int64)
     _chk(table, "table", ndim=2)
     out = torch.empty(*idx.shape, table.shape[1], device=table.device, dtype=torch.float32)
-    L = _lib.lib()
-    _lib.check(L.mgnns_embedding_fwd(_p(idx), idx.numel(), _p(table), table.shape[0], table.shape[1], _p(out),
-                                     _stream()), "mgnns_embedding_fwd")
+    _lib.call("mgnns_embedding_fwd", _p(idx), idx.numel(), _p(table), table.shape[0], table.shape[1], _p(out), _stream())
     return out
 
 
@@ -639,8 +628,8 @@ def _lstm_table(emb_table, cat0, hidden, cache):
         table = torch.empty(V, 8 * hidden, device=emb_table.device, dtype=torch.float32)
         assert table.numel() * 4 == L.mgnns_bilstm_bf16_table_bytes(V, hidden)
         ws = torch.empty(L.mgnns_bilstm_bf16_fold_workspace_bytes(V), dtype=torch.uint8, device=emb_table.device)
-        _lib.check(L.mgnns_bilstm_bf16_fold_embedding(_p(emb_table), V, E, hidden, _p(cat0[0]), _p(cat0[1]), _p(ws), ws.numel(),
-                                                      _p(table), _stream()), "mgnns_bilstm_bf16_fold_embedding")
+        _lib.call("mgnns_bilstm_bf16_fold_embedding", _p(emb_table), V, E, hidden, _p(cat0[0]), _p(cat0[1]), _p(ws), ws.numel(), _p(table),
+                  _stream())
         return table
     return _lstm_derived(cache, "table", [emb_table, cat0[0], cat0[1]], build)
 
@@ -686,28 +675,24 @@ def bilstm(tok, lens, emb_table, weights, hidden, num_layers, want_bf16=False, r
     if recurrence not in ("f32", "bf16"):
         raise ValueError("recurrence must be 'f32' or 'bf16', got %r" % (recurrence,))
     if recurrence == "f32":
-        _launch("mgnns_bilstm_fwd", ("mgnns_bilstm_fwd",), L.mgnns_bilstm_fwd, _p(tok), _p(lens), B, T, _p(emb_table),
-                emb_table.shape[0], emb_table.shape[1], hidden, num_layers, c_wih, c_bih, c_whh, c_bhh,
-                _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _stream())
+        _launch("mgnns_bilstm_fwd", _p(tok), _p(lens), B, T, _p(emb_table), emb_table.shape[0], emb_table.shape[1], hidden, num_layers,
+                c_wih, c_bih, c_whh, c_bhh, _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _stream())
     else:
         # weight layouts of the bf16 kernels: packed once per weight version, off the per-forward path
         def prepack():
             pre = torch.empty(L.mgnns_bilstm_bf16_prepack_bytes(hidden, num_layers), dtype=torch.uint8, device=tok.device)
-            _lib.check(L.mgnns_bilstm_bf16_prepack(c_wih, c_whh, emb_table.shape[1], hidden, num_layers, _p(pre), _stream()),
-                       "mgnns_bilstm_bf16_prepack")
+            _lib.call("mgnns_bilstm_bf16_prepack", c_wih, c_whh, emb_table.shape[1], hidden, num_layers, _p(pre), _stream())
             return pre
         pre = _lstm_derived(cache, "prepack", [t for tup in weights for t in (tup[0], tup[1])], prepack)
         if fold is None:
             fold = LSTM_FOLD_EMBEDDING and cache is not None
         if fold and B <= 1024 and T <= 1024 and emb_table.shape[1] % 4 == 0 and emb_table.shape[1] <= 320:
             table = _lstm_table(emb_table, cat[0], hidden, cache)
-            _launch("mgnns_bilstm_bf16_table_fwd", ("mgnns_bilstm_bf16_table_fwd",), L.mgnns_bilstm_bf16_table_fwd, _p(tok), _p(lens), B, T,
-                    _p(emb_table), emb_table.shape[0], emb_table.shape[1], hidden, num_layers, c_wih, c_bih, c_whh, c_bhh,
-                    _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _p(table), _stream())
+            _launch("mgnns_bilstm_bf16_table_fwd", _p(tok), _p(lens), B, T, _p(emb_table), emb_table.shape[0], emb_table.shape[1], hidden,
+                    num_layers, c_wih, c_bih, c_whh, c_bhh, _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _p(table), _stream())
         else:
-            _launch("mgnns_bilstm_bf16_fwd", ("mgnns_bilstm_bf16_fwd",), L.mgnns_bilstm_bf16_fwd, _p(tok), _p(lens), B, T, _p(emb_table),
-                    emb_table.shape[0], emb_table.shape[1], hidden, num_layers, c_wih, c_bih, c_whh, c_bhh,
-                    _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _stream())
+            _launch("mgnns_bilstm_bf16_fwd", _p(tok), _p(lens), B, T, _p(emb_table), emb_table.shape[0], emb_table.shape[1], hidden,
+                    num_layers, c_wih, c_bih, c_whh, c_bhh, _p(ws), ws.numel(), _p(out), _p(out_bf), BANK_LD, _p(pre), _stream())
     return (out, out_bf) if want_bf16 else out
 
 
@@ -729,9 +714,8 @@ def textgcn(tok, node_hidden, edge_w, pmi_dev, ngram, max_length=100):
     if rp.shape[0] != V + 1:
         raise ValueError("PMI map has %d rows, vocabulary has %d" % (rp.shape[0] - 1, V))
     out = torch.empty(B, D, device=tok.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_textgcn_fwd", ("mgnns_textgcn_fwd",), L.mgnns_textgcn_fwd, _p(tok), B, T, _p(node_hidden), V, D,
-            _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), int(ngram), int(max_length), _p(out), _stream())
+    _launch("mgnns_textgcn_fwd", _p(tok), B, T, _p(node_hidden), V, D, _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), int(ngram),
+            int(max_length), _p(out), _stream())
     return out
 
 
@@ -743,8 +727,7 @@ def transpose_pad(w, ld):
     """[rows, cols] -> [cols, ld] transposed, zero padded."""
     _chk(w, "w", ndim=2)
     out = torch.empty(w.shape[1], ld, device=w.device, dtype=torch.float32)
-    L = _lib.lib()
-    _lib.check(L.mgnns_transpose_pad(_p(w), w.shape[0], w.shape[1], _p(out), ld, _stream()), "mgnns_transpose_pad")
+    _lib.call("mgnns_transpose_pad", _p(w), w.shape[0], w.shape[1], _p(out), ld, _stream())
     return out
 
 
@@ -759,9 +742,7 @@ def imgbank_pool(feat, wt, bias, n_out, want_pool=True):
         _chk(bias, "bias", ndim=1)
     bank = torch.empty(B, P, n_out, device=feat.device, dtype=torch.float32)
     pooled = torch.empty(B, K, device=feat.device, dtype=torch.float32) if want_pool else None
-    L = _lib.lib()
-    _launch("mgnns_imgbank_pool_fwd", ("mgnns_imgbank_pool_fwd",), L.mgnns_imgbank_pool_fwd, _p(feat), B, K, P,
-            _p(wt), wt.shape[1], _p(bias), n_out, _p(bank), _p(pooled), _stream())
+    _launch("mgnns_imgbank_pool_fwd", _p(feat), B, K, P, _p(wt), wt.shape[1], _p(bias), n_out, _p(bank), _p(pooled), _stream())
     return bank, pooled
 
 
@@ -770,8 +751,7 @@ def pack_imgbank_weights_bf16(w):
     _chk(w, "weight", ndim=2)
     L = _lib.lib()
     buf = torch.empty(L.mgnns_imgbank_packed_weight_bytes(w.shape[1]), dtype=torch.uint8, device=w.device)
-    _lib.check(L.mgnns_imgbank_pack_weights_bf16(_p(w), w.shape[0], w.shape[1], _p(buf), _stream()),
-               "mgnns_imgbank_pack_weights_bf16")
+    _lib.call("mgnns_imgbank_pack_weights_bf16", _p(w), w.shape[0], w.shape[1], _p(buf), _stream())
     return buf
 
 
@@ -786,9 +766,8 @@ def imgbank_pool_bf16(feat, wp, bias, n_out, combine=True):
     bank = torch.empty(B, P, BANK_LD, device=feat.device, dtype=torch.bfloat16)
     pooled = torch.empty(B, K, device=feat.device, dtype=torch.float32)
     work = torch.empty(B, 2, K, device=feat.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_imgbank_pool_bf16_fwd", ("mgnns_imgbank_pool_bf16_fwd",), L.mgnns_imgbank_pool_bf16_fwd, _p(feat),
-            B, K, P, _p(wp), _p(bias), n_out, _p(bank), BANK_LD, _p(pooled) if combine else None, _p(work), _stream())
+    _launch("mgnns_imgbank_pool_bf16_fwd", _p(feat), B, K, P, _p(wp), _p(bias), n_out, _p(bank), BANK_LD, _p(pooled) if combine else None,
+            _p(work), _stream())
     return bank, (pooled if combine else work)
 
 
@@ -800,21 +779,19 @@ def head_diff(o, n_head):
     if o.shape[1] % n_head:
         raise ValueError("attention output width %d is not a multiple of n_head=%d" % (o.shape[1], n_head))
     out = torch.empty(B, device=o.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_head_diff_fwd", ("mgnns_head_diff_fwd",), L.mgnns_head_diff_fwd, _p(o), B, n_head, o.shape[1] // n_head, _p(out),
-            _stream())
+    _launch("mgnns_head_diff_fwd", _p(o), B, n_head, o.shape[1] // n_head, _p(out), _stream())
     return out
 
 
 def textgcn_set_form(form):
     """0 by batch (default) | 1 one 1024-thread launch | 2 two launches (short + long documents) | 3 the lean kernel (tests)."""
-    _lib.check(_lib.lib().mgnns_textgcn_set_form(int(form)), "mgnns_textgcn_set_form")
+    _lib.call("mgnns_textgcn_set_form", int(form))
 
 
 def imgbank_set_form(form):
     """Which bf16 image-bank kernel runs: 0 = chosen by the batch (default), 1 = the stream form (one workgroup per sample),
     2 = the pair form (two workgroups per sample) where its shape limits allow.  Process-wide; tests and measurements."""
-    _lib.check(_lib.lib().mgnns_imgbank_set_form(int(form)), "mgnns_imgbank_set_form")
+    _lib.call("mgnns_imgbank_set_form", int(form))
 
 
 # ---- label attention core ---------------------------------------------------------------------------
@@ -834,10 +811,8 @@ def imgbank_pool_split(feat, w_pair, bias, n_out, want_pool=True, want_f32=True,
     bank = torch.empty(B, P, n_out, device=feat.device, dtype=torch.float32) if want_f32 else None
     split = torch.empty(2, B, P, BANK_LD, device=feat.device, dtype=torch.bfloat16) if want_split else None
     pooled = torch.empty(B, 2, K, device=feat.device, dtype=torch.float32) if want_pool else None
-    L = _lib.lib()
-    _launch("mgnns_imgbank_pool_split_fwd", ("mgnns_imgbank_pool_split_fwd", P), L.mgnns_imgbank_pool_split_fwd, _p(feat), B, K, P,
-            _p(hi), _p(lo), _p(bias), n_out, _p(bank), _p(pooled), _p(split[0]) if want_split else None,
-            _p(split[1]) if want_split else None, _stream())
+    _launch("mgnns_imgbank_pool_split_fwd", _p(feat), B, K, P, _p(hi), _p(lo), _p(bias), n_out, _p(bank), _p(pooled),
+            _p(split[0]) if want_split else None, _p(split[1]) if want_split else None, _stream(), key=(P,))
     return (bank, pooled, split) if want_split else (bank, pooled)
 
 
@@ -852,17 +827,14 @@ def label_attn_core(Q, K, V, n_heads, mask=None):
     if K.shape[1] != hid or V.shape != K.shape or hid % n_heads:
         raise ValueError("label attention shapes Q%s K%s V%s" % (tuple(Q.shape), tuple(K.shape), tuple(V.shape)))
     x = torch.empty(B, NLQ, hid, device=K.device, dtype=torch.float32)
-    L = _lib.lib()
     if mask is not None:
         if mask.device != K.device:
             raise ValueError("mask is on %s, K on %s" % (mask.device, K.device))
         # the byte image of the broadcast mask (layout only: the comparison with 0 and the fill run in the kernel)
         m8 = torch.broadcast_to(mask != 0, (B, NLQ, n_heads, hid // n_heads)).to(torch.uint8).contiguous()
-        _lib.check(L.mgnns_label_attn_core_masked_fwd(_p(Q), _p(K), _p(V), _p(m8), B, NLQ, n_heads, hid // n_heads, _p(x), _stream()),
-                   "mgnns_label_attn_core_masked_fwd")
+        _lib.call("mgnns_label_attn_core_masked_fwd", _p(Q), _p(K), _p(V), _p(m8), B, NLQ, n_heads, hid // n_heads, _p(x), _stream())
         return x
-    _lib.check(L.mgnns_label_attn_core_fwd(_p(Q), _p(K), _p(V), B, NLQ, n_heads, hid // n_heads, _p(x), _stream()),
-               "mgnns_label_attn_core_fwd")
+    _lib.call("mgnns_label_attn_core_fwd", _p(Q), _p(K), _p(V), B, NLQ, n_heads, hid // n_heads, _p(x), _stream())
     return x
 
 
@@ -896,11 +868,9 @@ def label_tail(x, Q, n_heads, packed, pooled=None, g_wp=None, next_q=None):
     if next_q is not None:
         wq, bq, hkn = next_q
         qh = torch.empty(B, hkn, device=Q.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_label_tail_fwd", ("mgnns_label_tail_fwd", C), L.mgnns_label_tail_fwd, _p(x), B, C, _p(pooled), parts, kp,
-            _p(g_wp), _p(Q), NLQ, n_heads, hid // n_heads, _p(packed["wk"]), _p(packed["bk"]), _p(packed["wv"]),
-            _p(packed["bv"]), _p(packed["wc"]), _p(packed["bc"]), packed["n5"], _p(packed["xl"]), _p(packed["bxl"]),
-            packed["n_out"], _p(out), _p(wq), _p(bq), hkn, _p(qh), _stream())
+    _launch("mgnns_label_tail_fwd", _p(x), B, C, _p(pooled), parts, kp, _p(g_wp), _p(Q), NLQ, n_heads, hid // n_heads, _p(packed["wk"]),
+            _p(packed["bk"]), _p(packed["wv"]), _p(packed["bv"]), _p(packed["wc"]), _p(packed["bc"]), packed["n5"], _p(packed["xl"]),
+            _p(packed["bxl"]), packed["n_out"], _p(out), _p(wq), _p(bq), hkn, _p(qh), _stream(), key=(C,))
     return out if next_q is None else (out, qh)
 
 
@@ -944,11 +914,9 @@ def label_tail_bf16(pooled, g_pair, Q, n_heads, packed, next_q=None, terms=3, cl
     if cluster and int(terms) == 3 and B > 0:
         ws = _cluster_scratch(packed, "_cluster_ws", Q.device, (B + 15) // 16, lambda tiles: tiles * 4 * 6144)
         scratch, counters = ws[1], ws[2]
-    L = _lib.lib()
-    _launch("mgnns_label_tail_bf16_fwd", ("mgnns_label_tail_bf16_fwd", packed["C"]), L.mgnns_label_tail_bf16_fwd, _p(pooled), B,
-            parts, kp, packed["C"], int(terms), arr, _p(Q), NLQ, n_heads, hid // n_heads, _p(packed["bk"]), _p(packed["bv"]),
-            _p(packed["bc"]), packed["n5"], _p(packed["bxl"]), packed["n_out"], _p(out), _p(bq), hkn, _p(qh), _p(scratch),
-            _p(counters), _stream())
+    _launch("mgnns_label_tail_bf16_fwd", _p(pooled), B, parts, kp, packed["C"], int(terms), arr, _p(Q), NLQ, n_heads, hid // n_heads,
+            _p(packed["bk"]), _p(packed["bv"]), _p(packed["bc"]), packed["n5"], _p(packed["bxl"]), packed["n_out"], _p(out), _p(bq), hkn,
+            _p(qh), _p(scratch), _p(counters), _stream(), key=(packed["C"],))
     return out if next_q is None else (out, qh)
 
 
@@ -969,10 +937,8 @@ def sq_mha_core(qh, bank, mask, n_head, d_kv, wk, bk, wv, bv, want_attn=True):
             raise ValueError("%s shape %s" % (n, tuple(t.shape)))
     o = torch.empty(B, n_head * d_kv, device=bank.device, dtype=torch.float32)
     attn = torch.empty(n_head * B, 1, L_, device=bank.device, dtype=torch.float32) if want_attn else None
-    L = _lib.lib()
-    _launch("mgnns_sq_mha_core_fwd", ("mgnns_sq_mha_core_fwd", L_, mask is not None), L.mgnns_sq_mha_core_fwd,
-            _p(qh), _p(bank), _p(mask), B, L_, D, n_head, d_kv, _p(wk), _p(bk), _p(wv), _p(bv), _p(o), _p(attn),
-            _stream())
+    _launch("mgnns_sq_mha_core_fwd", _p(qh), _p(bank), _p(mask), B, L_, D, n_head, d_kv, _p(wk), _p(bk), _p(wv), _p(bv), _p(o), _p(attn),
+            _stream(), key=(L_, mask is not None))
     return o, attn
 
 
@@ -992,12 +958,10 @@ def pack_kv_weights_bf16(wk, wv, n_head, d_kv, form=None):
     L = _lib.lib()
     if form == 32:
         buf = torch.empty(L.mgnns_sq_mha32_packed_weight_bytes(n_head), dtype=torch.uint8, device=wk.device)
-        _lib.check(L.mgnns_sq_mha32_pack_weights_bf16(_p(wk), _p(wv), n_head, d_kv, wk.shape[1], _p(buf), _stream()),
-                   "mgnns_sq_mha32_pack_weights_bf16")
+        _lib.call("mgnns_sq_mha32_pack_weights_bf16", _p(wk), _p(wv), n_head, d_kv, wk.shape[1], _p(buf), _stream())
     else:
         buf = torch.empty(L.mgnns_sq_mha_packed_weight_bytes(n_head), dtype=torch.uint8, device=wk.device)
-        _lib.check(L.mgnns_sq_mha_pack_weights_bf16(_p(wk), _p(wv), n_head, d_kv, wk.shape[1], _p(buf), _stream()),
-                   "mgnns_sq_mha_pack_weights_bf16")
+        _lib.call("mgnns_sq_mha_pack_weights_bf16", _p(wk), _p(wv), n_head, d_kv, wk.shape[1], _p(buf), _stream())
     buf._mg_form = form
     return buf
 
@@ -1012,7 +976,7 @@ def sq_mha_plan(mask):
                          "one-workgroup-per-sample core)" % (B, PLAN_MAX_B))
     L = _lib.lib()
     plan = torch.empty(L.mgnns_sq_mha32_plan_ints(B), dtype=torch.int32, device=mask.device)
-    _lib.check(L.mgnns_sq_mha32_plan(_p(mask), B, L_, _p(plan), _stream()), "mgnns_sq_mha32_plan")
+    _lib.call("mgnns_sq_mha32_plan", _p(mask), B, L_, _p(plan), _stream())
     plan._mg_plan_kind = 'packed'
     return plan
 
@@ -1026,8 +990,7 @@ def cast_pad_bf16(x, ld=BANK_LD):
     D = x.shape[-1]
     x2 = _chk(x.reshape(-1, D), "x")
     y = torch.empty(x2.shape[0], ld, dtype=torch.bfloat16, device=x.device)
-    L = _lib.lib()
-    _lib.check(L.mgnns_cast_pad_bf16(_p(x2), x2.shape[0], D, ld, _p(y), _stream()), "mgnns_cast_pad_bf16")
+    _lib.call("mgnns_cast_pad_bf16", _p(x2), x2.shape[0], D, ld, _p(y), _stream())
     return y.view(*x.shape[:-1], ld)
 
 
@@ -1057,15 +1020,13 @@ def sq_mha_core_bf16(qh, bank_bf16, mask, n_head, d_kv, wp, bk, bv, want_attn=Tr
             if getattr(plan, "_mg_plan_kind", 'packed') != 'packed':       # (the grouped split-bf16 core's plan has the same size)
                 raise ValueError("sq_mha_core_bf16 takes the plan sq_mha_plan(mask) returned (got kind %r)"
                                  % plan._mg_plan_kind)
-        _launch("mgnns_sq_mha_core_bf16_fwd", ("mgnns_sq_mha_core_bf16_fwd", L_, mask is not None),
-                L.mgnns_sq_mha32_core_bf16_fwd, _p(qh), _p(bank_bf16), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk),
-                _p(bv), _p(o), _p(attn), _p(plan), _stream())
+        _launch("mgnns_sq_mha32_core_bf16_fwd", _p(qh), _p(bank_bf16), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk), _p(bv), _p(o),
+                _p(attn), _p(plan), _stream(), key=(L_, mask is not None), alias="mgnns_sq_mha_core_bf16_fwd")
         return o, attn
     if plan is not None:
         raise ValueError("a packing plan needs the 32x32x16 form of the packed weights")
-    _launch("mgnns_sq_mha_core_bf16_fwd", ("mgnns_sq_mha_core_bf16_fwd", L_, mask is not None),
-            L.mgnns_sq_mha_core_bf16_fwd, _p(qh), _p(bank_bf16), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk),
-            _p(bv), _p(o), _p(attn), _stream())
+    _launch("mgnns_sq_mha_core_bf16_fwd", _p(qh), _p(bank_bf16), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk), _p(bv), _p(o), _p(attn),
+            _stream(), key=(L_, mask is not None))
     return o, attn
 
 
@@ -1075,8 +1036,7 @@ def pack_kv_weights_split(wk, wv, n_head, d_kv):
     _chk(wv, "w_vs.weight", ndim=2)
     L = _lib.lib()
     buf = torch.empty(L.mgnns_sq_mha_split_packed_weight_bytes(n_head), dtype=torch.uint8, device=wk.device)
-    _lib.check(L.mgnns_sq_mha_pack_weights_split(_p(wk), _p(wv), n_head, d_kv, wk.shape[1], _p(buf), _stream()),
-               "mgnns_sq_mha_pack_weights_split")
+    _lib.call("mgnns_sq_mha_pack_weights_split", _p(wk), _p(wv), n_head, d_kv, wk.shape[1], _p(buf), _stream())
     buf._mg_form = "split"
     return buf
 
@@ -1086,8 +1046,7 @@ def split_pad_bf16(x, ld=BANK_LD):
     D = x.shape[-1]
     x2 = _chk(x.reshape(-1, D), "x")
     y = torch.empty(2, x2.shape[0], ld, dtype=torch.bfloat16, device=x.device)
-    L = _lib.lib()
-    _lib.check(L.mgnns_split_pad_bf16(_p(x2), x2.shape[0], D, ld, _p(y[0]), _p(y[1]), _stream()), "mgnns_split_pad_bf16")
+    _lib.call("mgnns_split_pad_bf16", _p(x2), x2.shape[0], D, ld, _p(y[0]), _p(y[1]), _stream())
     return y.view(2, *x.shape[:-1], ld)
 
 
@@ -1103,7 +1062,7 @@ def sq_mha_split_plan(mask):
         raise ValueError("sq_mha_split_plan: B=%d (<= %d), L=%d (<= %d)" % (B, PLAN_MAX_B, L_, SPLIT_PLAN_MAX_L))
     L = _lib.lib()
     plan = torch.empty(L.mgnns_sq_mha32_plan_ints(B), dtype=torch.int32, device=mask.device)
-    _lib.check(L.mgnns_sq_mha_split_plan(_p(mask), B, L_, _p(plan), _stream()), "mgnns_sq_mha_split_plan")
+    _lib.call("mgnns_sq_mha_split_plan", _p(mask), B, L_, _p(plan), _stream())
     plan._mg_plan_kind = 'grouped'
     return plan
 
@@ -1140,9 +1099,8 @@ def sq_mha_core_split(qh, bank_split, mask, n_head, d_kv, wp, bk, bv, want_attn=
         if getattr(plan, "_mg_plan_kind", None) != 'grouped':
             raise ValueError("sq_mha_core_split takes the plan sq_mha_split_plan(mask) returned (got kind %r)"
                              % getattr(plan, "_mg_plan_kind", None))
-    _launch("mgnns_sq_mha_core_split_fwd", ("mgnns_sq_mha_core_split_fwd", L_, mask is not None), L.mgnns_sq_mha_core_split_fwd,
-            _p(qh), _p(bank_split[0]), _p(bank_split[1]), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk), _p(bv), _p(o),
-            _p(attn), _p(plan), _stream())
+    _launch("mgnns_sq_mha_core_split_fwd", _p(qh), _p(bank_split[0]), _p(bank_split[1]), _p(mask), B, L_, ld, n_head, d_kv, _p(wp), _p(bk),
+            _p(bv), _p(o), _p(attn), _p(plan), _stream(), key=(L_, mask is not None))
     return o, attn
 
 
@@ -1171,9 +1129,8 @@ def sq_mha_folded(qh, bank, mask, n_head, d_kv, wk, wv, bv, want_attn=True):
     L = _lib.lib()
     nbytes = L.mgnns_sq_mha_folded_workspace_bytes(B, D, n_head)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=qh.device)     # per call: stacks run on four streams
-    _launch("mgnns_sq_mha_folded_fwd", ("mgnns_sq_mha_folded_fwd", L_, is_bf16), L.mgnns_sq_mha_folded_fwd,
-            _p(qh), _p(bank), int(is_bf16), ld, _p(mask), B, L_, D, n_head, d_kv, _p(wk), _p(wv), _p(bv), _p(ws), nbytes,
-            _p(o), _p(attn), _stream())
+    _launch("mgnns_sq_mha_folded_fwd", _p(qh), _p(bank), int(is_bf16), ld, _p(mask), B, L_, D, n_head, d_kv, _p(wk), _p(wv), _p(bv), _p(ws),
+            nbytes, _p(o), _p(attn), _stream(), key=(L_, is_bf16))
     return o, attn
 
 
@@ -1196,9 +1153,8 @@ def sq_mha_folded_bf16(u, bank_bf16, mask, n_head, d_kv, want_attn=True):
     ldc = (n_head * D + 31) // 32 * 32
     c = torch.empty(B, ldc, device=u.device, dtype=torch.bfloat16)
     attn = torch.empty(n_head * B, 1, L_, device=u.device, dtype=torch.float32) if want_attn else None
-    L = _lib.lib()
-    _launch("mgnns_sq_mha_folded_bf16_fwd", ("mgnns_sq_mha_folded_bf16_fwd", L_), L.mgnns_sq_mha_folded_bf16_fwd,
-            _p(u), _p(bank_bf16), _p(mask), B, L_, D, n_head, float(1.0 / (d_kv ** 0.5)), _p(c), ldc, _p(attn), _stream())
+    _launch("mgnns_sq_mha_folded_bf16_fwd", _p(u), _p(bank_bf16), _p(mask), B, L_, D, n_head, float(1.0 / (d_kv ** 0.5)), _p(c), ldc,
+            _p(attn), _stream(), key=(L_,))
     return c, attn
 
 
@@ -1207,7 +1163,7 @@ def pack_weight_f32(w):
     _chk(w, "weight", ndim=2)
     L = _lib.lib()
     buf = torch.empty(L.mgnns_packed_f32_weight_bytes(w.shape[0], w.shape[1]) // 4, dtype=torch.float32, device=w.device)
-    _lib.check(L.mgnns_pack_weight_f32(_p(w), w.shape[0], w.shape[1], _p(buf), _stream()), "mgnns_pack_weight_f32")
+    _lib.call("mgnns_pack_weight_f32", _p(w), w.shape[0], w.shape[1], _p(buf), _stream())
     return buf
 
 
@@ -1226,10 +1182,8 @@ def mha_tail(o, q, packed, eps, next_packed=None):
     if next_packed is not None:
         wq, bq, hkn = next_packed
         qh = torch.empty(B, hkn, device=o.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_mha_tail_fwd", ("mgnns_mha_tail_fwd",), L.mgnns_mha_tail_fwd, _p(o), HK, _p(q), B, 300,
-            _p(packed["fc_wp"]), _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]), _p(packed["w1_wp"]),
-            _p(packed["b1"]), _p(packed["w2_wp"]), _p(packed["b2"]), _p(packed["g2"]), _p(packed["be2"]), float(eps),
+    _launch("mgnns_mha_tail_fwd", _p(o), HK, _p(q), B, 300, _p(packed["fc_wp"]), _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]),
+            _p(packed["w1_wp"]), _p(packed["b1"]), _p(packed["w2_wp"]), _p(packed["b2"]), _p(packed["g2"]), _p(packed["be2"]), float(eps),
             _p(out), _p(wq), _p(bq), hkn, _p(qh), _stream())
     return out, qh
 
@@ -1241,8 +1195,7 @@ def pack_weight_bf16_split(w):
     n = L.mgnns_packed_bf16_weight_bytes(w.shape[0], w.shape[1])
     hi = torch.empty(n, dtype=torch.uint8, device=w.device)
     lo = torch.empty(n, dtype=torch.uint8, device=w.device)
-    _lib.check(L.mgnns_pack_weight_bf16_split(_p(w), w.shape[0], w.shape[1], _p(hi), _p(lo), _stream()),
-               "mgnns_pack_weight_bf16_split")
+    _lib.call("mgnns_pack_weight_bf16_split", _p(w), w.shape[0], w.shape[1], _p(hi), _p(lo), _stream())
     return hi, lo
 
 
@@ -1279,10 +1232,9 @@ def mha_tail_bf16(o, q, packed, eps, next_packed=None, terms=3, cluster=0, kspli
         ws = _cluster_scratch(packed, "_cluster_ws_ks", o.device, (B + 15) // 16,
                               lambda tiles: L.mgnns_mha_tail_c16_scratch_floats(16 * tiles, 8))
         scratch, counters = ws[1], ws[2]
-    _launch("mgnns_mha_tail_bf16_fwd", ("mgnns_mha_tail_bf16_fwd",), L.mgnns_mha_tail_bf16_fwd, _p(o), HK, _p(q), B, 300,
-            int(terms), arr, _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]), _p(packed["b1"]), _p(packed["b2"]),
-            _p(packed["g2"]), _p(packed["be2"]), float(eps), _p(out), _p(bq), hkn, _p(qh), int(cluster), _p(scratch), _p(counters),
-            _stream())
+    _launch("mgnns_mha_tail_bf16_fwd", _p(o), HK, _p(q), B, 300, int(terms), arr, _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]),
+            _p(packed["b1"]), _p(packed["b2"]), _p(packed["g2"]), _p(packed["be2"]), float(eps), _p(out), _p(bq), hkn, _p(qh), int(cluster),
+            _p(scratch), _p(counters), _stream())
     if split_proj:
         qh = linear(out, next_linear[0], next_linear[1])
     return out, qh
@@ -1314,10 +1266,9 @@ def mha_tail_c16(c, q, packed, eps, next_packed=None, cluster=0, ksplit=True):
         ws = _cluster_scratch(packed, "_cluster_ws", c.device, (B + 15) // 16,
                               lambda tiles: L.mgnns_mha_tail_c16_scratch_floats(16 * tiles, 8))
         scratch, counters = ws[1], ws[2]
-    _launch("mgnns_mha_tail_c16_fwd", ("mgnns_mha_tail_c16_fwd",), L.mgnns_mha_tail_c16_fwd, _p(c), HC, _p(q), B, 300,
-            arr, _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]), _p(packed["b1"]), _p(packed["b2"]),
-            _p(packed["g2"]), _p(packed["be2"]), float(eps), _p(out), _p(bq), hcn, _p(un), int(cluster), _p(scratch), _p(counters),
-            _stream())
+    _launch("mgnns_mha_tail_c16_fwd", _p(c), HC, _p(q), B, 300, arr, _p(packed["fc_b"]), _p(packed["g1"]), _p(packed["be1"]),
+            _p(packed["b1"]), _p(packed["b2"]), _p(packed["g2"]), _p(packed["be2"]), float(eps), _p(out), _p(bq), hcn, _p(un), int(cluster),
+            _p(scratch), _p(counters), _stream())
     return out, un
 
 
@@ -1327,9 +1278,7 @@ def layernorm(x, gamma, beta, eps=1e-6):
     _chk(gamma, "gamma", ndim=1)
     _chk(beta, "beta", ndim=1)
     y = torch.empty_like(x2)
-    L = _lib.lib()
-    _lib.check(L.mgnns_layernorm_fwd(_p(x2), x2.shape[0], D, _p(gamma), _p(beta), float(eps), _p(y), _stream()),
-               "mgnns_layernorm_fwd")
+    _lib.call("mgnns_layernorm_fwd", _p(x2), x2.shape[0], D, _p(gamma), _p(beta), float(eps), _p(y), _stream())
     return y.view(x.shape)
 
 
@@ -1343,7 +1292,7 @@ def transpose_cast_bf16(x):
     _chk(x, "x", ndim=2)
     K, N = x.shape
     y = torch.empty(N, _kpad(K), dtype=torch.bfloat16, device=x.device)
-    _lib.check(_lib.lib().mgnns_transpose_cast_bf16(_p(x), K, N, y.shape[1], _p(y), _stream()), "mgnns_transpose_cast_bf16")
+    _lib.call("mgnns_transpose_cast_bf16", _p(x), K, N, y.shape[1], _p(y), _stream())
     return y
 
 
@@ -1392,17 +1341,16 @@ def gemm_bf16_nt(a_bf16, bt_bf16, bias=None, act=ACT_NONE, n_valid=None, out=Non
     if transposed_out and ((M + 159) // 160 < 8 or N < 256 or Kp < 320):
         raise ValueError("transposed_out needs ceil(M / 160) >= 8, N >= 256, K >= 320 (M=%d N=%d K=%d)" % (M, N, Kp))
     ws = _gemm_bf16_workspace(a_bf16.device) if (GEMM_BF16_KSPLIT and M * N >= (1 << 20)) else None
-    _lib.check(_lib.lib().mgnns_gemm_bf16_nt_fwd(_p(a_bf16), _p(bt_bf16), M, N, Kp, _p(bias), _p(c), c.stride(0),
-                                                 (1 if c.dtype == torch.bfloat16 else 0) | (2 if transposed_out else 0), act, _p(ws),
-                                                 0 if ws is None else ws.numel(),
-                                                 _stream()), "mgnns_gemm_bf16_nt_fwd")
+    _lib.call("mgnns_gemm_bf16_nt_fwd", _p(a_bf16), _p(bt_bf16), M, N, Kp, _p(bias), _p(c), c.stride(0),
+              (1 if c.dtype == torch.bfloat16 else 0) | (2 if transposed_out else 0), act, _p(ws), 0 if ws is None else ws.numel(),
+              _stream())
     return c
 
 
 def gemm_bf16_set_form(form):
     """Tile shape of gemm_bf16_nt (tests / timings): 0 round 4's kernels only, 1 the 160 x 256 kernel whenever the shape
     fits it, 2 by the launcher's estimate (the default), 3 the 320 x 256 kernel whenever it fits; -1 back to the default."""
-    _lib.check(_lib.lib().mgnns_gemm_bf16_set_form(int(form)), "mgnns_gemm_bf16_set_form")
+    _lib.call("mgnns_gemm_bf16_set_form", int(form))
 
 
 def dense_adj_matmul_bf16(adj_bf16, support, act=ACT_NONE):
@@ -1436,9 +1384,8 @@ def conv_fold_bn(weight, conv_bias=None, bn=None, stem=False):
         _chk(conv_bias, "conv_bias", ndim=1)
     wt = torch.empty(Cout, ld, device=weight.device, dtype=torch.bfloat16)
     bias = torch.empty(Cout, device=weight.device, dtype=torch.float32)
-    _lib.check(_lib.lib().mgnns_conv_fold_bn_bf16(_p(weight), _p(conv_bias), Cout, Cin, KH, KW, _p(g), _p(b), _p(m), _p(v),
-                                                  float(eps), 1 if stem else 0, ld, _p(wt), _p(bias), _stream()),
-               "mgnns_conv_fold_bn_bf16")
+    _lib.call("mgnns_conv_fold_bn_bf16", _p(weight), _p(conv_bias), Cout, Cin, KH, KW, _p(g), _p(b), _p(m), _p(v), float(eps),
+              1 if stem else 0, ld, _p(wt), _p(bias), _stream())
     return wt, bias
 
 
@@ -1453,13 +1400,10 @@ def stem_conv7(img, wt, bias, raw=False):
         raise ValueError("stem expects img [B,3,H,W], wt [64,%d], bias [64]; got %s %s %s"
                          % (STEM_LD, tuple(img.shape), tuple(wt.shape), tuple(bias.shape)))
     y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, device=img.device, dtype=torch.bfloat16)
-    L = _lib.lib()
     if raw:
-        _launch("mgnns_stem_conv7_raw_fwd", ("mgnns_stem_conv7_raw_fwd",), L.mgnns_stem_conv7_raw_fwd, _p(img), B, H, W, _p(wt), _p(y),
-                _stream())
+        _launch("mgnns_stem_conv7_raw_fwd", _p(img), B, H, W, _p(wt), _p(y), _stream())
         return y
-    _launch("mgnns_stem_conv7_fwd", ("mgnns_stem_conv7_fwd",), L.mgnns_stem_conv7_fwd, _p(img), B, H, W, _p(wt), _p(bias),
-            _p(y), _stream())
+    _launch("mgnns_stem_conv7_fwd", _p(img), B, H, W, _p(wt), _p(bias), _p(y), _stream())
     return y
 
 
@@ -1467,9 +1411,7 @@ def maxpool3x3s2_nhwc(x):
     _chk(x, "x", torch.bfloat16, 4)
     B, H, W, C = x.shape
     y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, device=x.device, dtype=torch.bfloat16)
-    L = _lib.lib()
-    _launch("mgnns_maxpool3x3s2_nhwc_fwd", ("mgnns_maxpool3x3s2_nhwc_fwd",), L.mgnns_maxpool3x3s2_nhwc_fwd, _p(x), B, H, W, C,
-            _p(y), _stream())
+    _launch("mgnns_maxpool3x3s2_nhwc_fwd", _p(x), B, H, W, C, _p(y), _stream())
     return y
 
 
@@ -1494,10 +1436,8 @@ def conv_bf16_nhwc(x, wt, bias, ksize, stride=1, pad=0, residual=None, relu=True
         y = torch.empty(B, Cout, OH, OW, device=x.device, dtype=torch.float32)
     else:
         y = torch.empty(B, OH, OW, Cout, device=x.device, dtype=torch.bfloat16)
-    L = _lib.lib()
-    _launch("mgnns_conv_bf16_nhwc_fwd", ("mgnns_conv_bf16_nhwc_fwd", ksize, Cin, Cout, stride, OH), L.mgnns_conv_bf16_nhwc_fwd,
-            _p(x), B, H, W, Cin, _p(wt), _p(bias), Cout, ksize, ksize, stride, pad, _p(residual), 1 if relu else 0,
-            1 if out_nchw_f32 else 0, _p(y), _stream())
+    _launch("mgnns_conv_bf16_nhwc_fwd", _p(x), B, H, W, Cin, _p(wt), _p(bias), Cout, ksize, ksize, stride, pad, _p(residual),
+            1 if relu else 0, 1 if out_nchw_f32 else 0, _p(y), _stream(), key=(ksize, Cin, Cout, stride, OH))
     return y
 
 
@@ -1510,9 +1450,7 @@ def conv_transpose_pack(wt, ksize):
         raise ValueError("wt %s is no %dx%d folded weight" % (tuple(wt.shape), ksize, ksize))
     Cin = K // (ksize * ksize)
     wT = torch.empty(Cin, ksize * ksize * Cout, device=wt.device, dtype=torch.bfloat16)
-    L = _lib.lib()
-    _launch("mgnns_conv_transpose_pack_bf16", ("mgnns_conv_transpose_pack_bf16",), L.mgnns_conv_transpose_pack_bf16, _p(wt), Cout, Cin,
-            ksize, ksize, _p(wT), _stream())
+    _launch("mgnns_conv_transpose_pack_bf16", _p(wt), Cout, Cin, ksize, ksize, _p(wT), _stream())
     return wT
 
 
@@ -1537,9 +1475,8 @@ def conv_dgrad_bf16_nhwc(dy, wT, in_hw, ksize, stride=1, pad=0, mask=None, add=N
             if tuple(t.shape) != (B, H, W, Cin):
                 raise ValueError("%s %s != input %s" % (n, tuple(t.shape), (B, H, W, Cin)))
     dx = torch.empty(B, H, W, Cin, device=dy.device, dtype=torch.bfloat16)
-    L = _lib.lib()
-    _launch("mgnns_conv_dgrad_bf16_nhwc", ("mgnns_conv_dgrad_bf16_nhwc", ksize, Cin, Cout, stride, OH), L.mgnns_conv_dgrad_bf16_nhwc,
-            _p(dy), B, H, W, Cin, _p(wT), Cout, ksize, ksize, stride, pad, _p(mask), _p(add), _p(dx), _stream())
+    _launch("mgnns_conv_dgrad_bf16_nhwc", _p(dy), B, H, W, Cin, _p(wT), Cout, ksize, ksize, stride, pad, _p(mask), _p(add), _p(dx),
+            _stream(), key=(ksize, Cin, Cout, stride, OH))
     return dx
 
 
@@ -1558,9 +1495,8 @@ def conv_wgrad_bf16_nhwc(x, dy, ksize, stride=1, pad=0):
     L = _lib.lib()
     nbytes = L.mgnns_conv_wgrad_workspace_bytes(B, H, W, Cin, Cout, ksize, ksize, stride, pad)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    _launch("mgnns_conv_wgrad_bf16_nhwc", ("mgnns_conv_wgrad_bf16_nhwc", ksize, Cin, Cout, stride, dy.shape[1]),
-            L.mgnns_conv_wgrad_bf16_nhwc, _p(x), _p(dy), B, H, W, Cin, Cout, ksize, ksize, stride, pad, _p(dW), _p(db), _p(ws), nbytes,
-            _stream())
+    _launch("mgnns_conv_wgrad_bf16_nhwc", _p(x), _p(dy), B, H, W, Cin, Cout, ksize, ksize, stride, pad, _p(dW), _p(db), _p(ws), nbytes,
+            _stream(), key=(ksize, Cin, Cout, stride, dy.shape[1]))
     return dW, db
 
 
@@ -1582,9 +1518,8 @@ def conv_bn_unfold(dwp, dbp, weight, bn, want=(True, True, True)):
     dW = torch.empty_like(weight) if want[0] else None
     dg = torch.empty(Cout, device=weight.device, dtype=torch.float32) if want[1] else None
     dbeta = torch.empty(Cout, device=weight.device, dtype=torch.float32) if want[2] else None
-    L = _lib.lib()
-    _launch("mgnns_conv_bn_unfold", ("mgnns_conv_bn_unfold",), L.mgnns_conv_bn_unfold, _p(dwp), _p(dbp), _p(weight), _p(g), _p(m), _p(v),
-            float(eps), Cout, Cin, KH, KW, _p(dW), _p(dg), _p(dbeta), _stream())
+    _launch("mgnns_conv_bn_unfold", _p(dwp), _p(dbp), _p(weight), _p(g), _p(m), _p(v), float(eps), Cout, Cin, KH, KW, _p(dW), _p(dg),
+            _p(dbeta), _stream())
     return dW, dg, dbeta
 
 
@@ -1597,9 +1532,7 @@ def map_grad_relu_nhwc(fmap, dmap):
         raise ValueError("map %s / dmap %s" % (tuple(fmap.shape), tuple(dmap.shape)))
     B, C, h, w = fmap.shape
     g = torch.empty(B, h, w, C, device=fmap.device, dtype=torch.bfloat16)
-    L = _lib.lib()
-    _launch("mgnns_map_grad_relu_nhwc_bf16", ("mgnns_map_grad_relu_nhwc_bf16",), L.mgnns_map_grad_relu_nhwc_bf16, _p(fmap), _p(dmap), B, C,
-            h * w, _p(g), _stream())
+    _launch("mgnns_map_grad_relu_nhwc_bf16", _p(fmap), _p(dmap), B, C, h * w, _p(g), _stream())
     return g
 
 
@@ -1645,8 +1578,8 @@ def bn_stats_bf16_nhwc(z, eps, running=None, momentum=0.1, want_var=False):
     L = _lib.lib()
     nbytes = L.mgnns_bn_stats_workspace_bytes(M, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
-    _launch("mgnns_bn_stats_bf16", ("mgnns_bn_stats_bf16", M, C), L.mgnns_bn_stats_bf16, _p(z), M, C, float(eps), m, _p(mean), _p(rstd),
-            _p(var), _p(rm), _p(rv), _p(ws), nbytes, _stream())
+    _launch("mgnns_bn_stats_bf16", _p(z), M, C, float(eps), m, _p(mean), _p(rstd), _p(var), _p(rm), _p(rv), _p(ws), nbytes, _stream(),
+            key=(M, C))
     if rm is not None:                                  # written in place through their addresses: what derives from them is stale
         torch.autograd.graph.increment_version(rm)
         torch.autograd.graph.increment_version(rv)
@@ -1672,9 +1605,8 @@ def bn_apply_bf16_nhwc(z, mean, rstd, gamma, beta, residual=None, relu=True, out
         y = torch.empty(B, C, OH, OW, device=z.device, dtype=torch.float32)
     else:
         y = torch.empty_like(z)
-    L = _lib.lib()
-    _launch("mgnns_bn_apply_bf16", ("mgnns_bn_apply_bf16", M, C, bool(out_nchw_f32)), L.mgnns_bn_apply_bf16, _p(z), M, C, _p(mean),
-            _p(rstd), _p(gamma), _p(beta), _p(residual), 1 if relu else 0, 1 if out_nchw_f32 else 0, P, _p(y), _stream())
+    _launch("mgnns_bn_apply_bf16", _p(z), M, C, _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), 1 if relu else 0,
+            1 if out_nchw_f32 else 0, P, _p(y), _stream(), key=(M, C, bool(out_nchw_f32)))
     return y
 
 
@@ -1694,8 +1626,8 @@ def bn_backward_bf16_nhwc(g, z, mean, rstd, gamma, want=(True, True)):
     L = _lib.lib()
     nbytes = L.mgnns_bn_backward_workspace_bytes(M, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=z.device)
-    _launch("mgnns_bn_backward_bf16", ("mgnns_bn_backward_bf16", M, C), L.mgnns_bn_backward_bf16, _p(g), _p(z), M, C, _p(mean), _p(rstd),
-            _p(gamma), _p(gz), _p(dgamma), _p(dbeta), _p(ws), nbytes, _stream())
+    _launch("mgnns_bn_backward_bf16", _p(g), _p(z), M, C, _p(mean), _p(rstd), _p(gamma), _p(gz), _p(dgamma), _p(dbeta), _p(ws), nbytes,
+            _stream(), key=(M, C))
     return gz, dgamma, dbeta
 
 
@@ -1717,8 +1649,7 @@ def stem_wgrad(img, g):
     L = _lib.lib()
     nbytes = L.mgnns_stem_wgrad_workspace_bytes(B, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device) if nbytes else None
-    _launch("mgnns_stem_wgrad", ("mgnns_stem_wgrad", H, W), L.mgnns_stem_wgrad, _p(img), _p(g), B, H, W, _p(dW), _p(db), _p(ws), nbytes,
-            _stream())
+    _launch("mgnns_stem_wgrad", _p(img), _p(g), B, H, W, _p(dW), _p(db), _p(ws), nbytes, _stream(), key=(H, W))
     return dW, db
 
 
@@ -1734,9 +1665,7 @@ def maxpool3x3s2_bwd_nhwc(x, g_y, relu_mask=False):
     if H == 0 or W == 0 or tuple(g_y.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C):
         raise ValueError("g_y %s does not match the pooled shape of x %s" % (tuple(g_y.shape), tuple(x.shape)))
     g_x = torch.empty_like(x)
-    L = _lib.lib()
-    _launch("mgnns_maxpool3x3s2_nhwc_bwd", ("mgnns_maxpool3x3s2_nhwc_bwd", bool(relu_mask)), L.mgnns_maxpool3x3s2_nhwc_bwd, _p(x), _p(g_y),
-            B, H, W, C, 1 if relu_mask else 0, _p(g_x), _stream())
+    _launch("mgnns_maxpool3x3s2_nhwc_bwd", _p(x), _p(g_y), B, H, W, C, 1 if relu_mask else 0, _p(g_x), _stream(), key=(bool(relu_mask),))
     return g_x
 
 
@@ -1819,9 +1748,8 @@ def image_prep(pixels, desc, desc_dev, plan_table, plan_table_dev, plan_data, lu
         _chk(out, "out", ndim=4)
         if tuple(out.shape) != (B, 3, size_h, size_w) or out.device != pixels.device:
             raise ValueError("out must be [%d,3,%d,%d] on %s, got %s on %s" % (B, size_h, size_w, pixels.device, tuple(out.shape), out.device))
-    L = _lib.lib()
-    _launch("mgnns_image_prep_fwd", ("mgnns_image_prep_fwd", size_h, size_w), L.mgnns_image_prep_fwd, _p(pixels), pixels.numel(),
-            _p(desc_dev), B, _p(plan_table_dev), P, _p(plan_data), plan_data.numel(), _p(lut), size_h, size_w, _p(out), _stream())
+    _launch("mgnns_image_prep_fwd", _p(pixels), pixels.numel(), _p(desc_dev), B, _p(plan_table_dev), P, _p(plan_data), plan_data.numel(),
+            _p(lut), size_h, size_w, _p(out), _stream(), key=(size_h, size_w))
     return out
 
 
@@ -1915,10 +1843,9 @@ def jpeg_decode(data, img, img_dev, seg, seg_dev, tables, pixels, stages=7, chec
         raise ValueError("the batch needs a coefficient workspace of %d int16 -- decode it in smaller batches" % coef_elems)
     coef = torch.empty(max(coef_elems, 64), dtype=torch.int16, device=data.device)
     planes = torch.empty(max(plane_bytes, 64), dtype=torch.uint8, device=data.device)
-    L = _lib.lib()
-    _launch("mgnns_jpeg_decode_fwd", ("mgnns_jpeg_decode_fwd", B, S), L.mgnns_jpeg_decode_fwd, _p(data), data.numel(), _p(img_dev), B,
-            _p(seg_dev), S, _p(tables), n_sets, _p(coef), coef.numel(), _p(planes), planes.numel(), _p(pixels), pixels.numel(),
-            max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1), int(stages), _p(status), _stream())
+    _launch("mgnns_jpeg_decode_fwd", _p(data), data.numel(), _p(img_dev), B, _p(seg_dev), S, _p(tables), n_sets, _p(coef), coef.numel(),
+            _p(planes), planes.numel(), _p(pixels), pixels.numel(), max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1),
+            int(stages), _p(status), _stream(), key=(B, S))
     if check:
         st = status.cpu()                      # one small D2H on the current stream; it also ends the workspaces' use
         bad = st.nonzero().flatten().tolist()
@@ -1951,14 +1878,15 @@ def stamp(name):
     if len(names) >= slots.numel():
         raise RuntimeError("timeline full")
     names.append(name)
-    _lib.check(_lib.lib().mgnns_debug_stamp(_p(slots), len(names) - 1, _stream()), "mgnns_debug_stamp")
+    _lib.call("mgnns_debug_stamp", _p(slots), len(names) - 1, _stream())
 
 
 # ---- training mode of the fusion layers (csrc/mha_train.hip; fp32, GPU only) ----------------------------------------------
 # dropout sites of the counter-based masks: (seed, site, element index) -> keep
 DROP_ATTN, DROP_FC, DROP_FFN = 0, 1, 2
-DROP_LABEL_ATTN, DROP_HEAD = 3, 4          # the label Attention's probabilities, the classifier's dropout (model training)
-ELT_ADD, ELT_RELU_BWD, ELT_LRELU2_BWD = 0, 1, 2
+# the label Attention's probabilities, the classifier's dropout (model training)
+DROP_LABEL_ATTN, DROP_HEAD = _C["MGNNS_DROP_LABEL_ATTN"], _C["MGNNS_DROP_HEAD"]
+ELT_ADD, ELT_RELU_BWD, ELT_LRELU2_BWD = _C["MGNNS_ELT_ADD"], _C["MGNNS_ELT_RELU_BWD"], _C["MGNNS_ELT_LRELU2_BWD"]
 TRAIN_MAX_L, TRAIN_MAX_D, TRAIN_MAX_H = 208, 320, 8
 
 
@@ -2005,10 +1933,8 @@ def mha_attn_train(qh, bank, mask, n_head, d_kv, wk, wv, bv, seed, rate, return_
     Z = torch.empty(n_head, B, D, device=dev, dtype=f32)
     SP = torch.empty(n_head, B, device=dev, dtype=f32)
     o = torch.empty(B, n_head * d_kv, device=dev, dtype=f32)
-    L = _lib.lib()
-    _launch("mgnns_mha_train_fwd", ("mgnns_mha_train_fwd", L_), L.mgnns_mha_train_fwd, _p(qh), _p(bank), _p(mask), B, L_, D,
-            n_head, d_kv, _p(wk), _p(wv), _p(bv), _seed64(seed), rate, _p(U), _p(P), _p(attn), _p(keep), _p(Z), _p(SP), _p(o),
-            _stream())
+    _launch("mgnns_mha_train_fwd", _p(qh), _p(bank), _p(mask), B, L_, D, n_head, d_kv, _p(wk), _p(wv), _p(bv), _seed64(seed), rate, _p(U),
+            _p(P), _p(attn), _p(keep), _p(Z), _p(SP), _p(o), _stream(), key=(L_,))
     saved = dict(U=U, P=P, attn=attn, keep=keep, Z=Z, SP=SP, rate=rate, n_head=n_head, d_kv=d_kv)
     if return_masks:
         return o, attn, saved, keep.bool()
@@ -2035,9 +1961,9 @@ def mha_attn_train_backward(dO, qh, bank, mask, wk, wv, bv, saved, want_dbank=Tr
     nbytes = L.mgnns_mha_train_bwd_workspace_bytes(B, D, H, dk)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     s = saved
-    _launch("mgnns_mha_train_bwd", ("mgnns_mha_train_bwd", L_), L.mgnns_mha_train_bwd, _p(dO), _p(qh), _p(bank), _p(mask), B, L_,
-            D, H, dk, _p(wk), _p(wv), _p(bv), s["rate"], _p(s["U"]), _p(s["P"]), _p(s["attn"]), _p(s["keep"]), _p(s["Z"]),
-            _p(s["SP"]), _p(dqh), _p(dWk), _p(dWv), _p(dbv), _p(dbank), _p(ws), nbytes, _stream())
+    _launch("mgnns_mha_train_bwd", _p(dO), _p(qh), _p(bank), _p(mask), B, L_, D, H, dk, _p(wk), _p(wv), _p(bv), s["rate"], _p(s["U"]),
+            _p(s["P"]), _p(s["attn"]), _p(s["keep"]), _p(s["Z"]), _p(s["SP"]), _p(dqh), _p(dWk), _p(dWv), _p(dbv), _p(dbank), _p(ws),
+            nbytes, _stream(), key=(L_,))
     return dqh, dWk, dWv, dbv, dbank
 
 
@@ -2054,8 +1980,7 @@ def wgrad(dy, x, bias=True):
     L = _lib.lib()
     nbytes = L.mgnns_wgrad_workspace_bytes(M, N, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
-    _launch("mgnns_wgrad_fwd", ("mgnns_wgrad_fwd", M, N, K), L.mgnns_wgrad_fwd, _p(dy), M, N, _p(x), K, _p(dW), _p(db), _p(ws),
-            nbytes, _stream())
+    _launch("mgnns_wgrad_fwd", _p(dy), M, N, _p(x), K, _p(dW), _p(db), _p(ws), nbytes, _stream(), key=(M, N, K))
     return dW, db
 
 
@@ -2076,9 +2001,8 @@ def dropout_residual_layernorm(x, res, gamma, beta, eps, seed, site, rate, retur
     xhat = torch.empty_like(x2)
     sig = torch.empty(rows, device=x.device, dtype=torch.float32)
     keep = torch.empty(rows, D, device=x.device, dtype=torch.uint8)
-    L = _lib.lib()
-    _launch("mgnns_drop_res_ln_fwd", ("mgnns_drop_res_ln_fwd", D), L.mgnns_drop_res_ln_fwd, _p(x2), _p(r2), rows, D, _p(gamma),
-            _p(beta), float(eps), _seed64(seed), int(site), rate, _p(y), _p(xhat), _p(sig), _p(keep), _stream())
+    _launch("mgnns_drop_res_ln_fwd", _p(x2), _p(r2), rows, D, _p(gamma), _p(beta), float(eps), _seed64(seed), int(site), rate, _p(y),
+            _p(xhat), _p(sig), _p(keep), _stream(), key=(D,))
     saved = dict(xhat=xhat, sig=sig, keep=keep, rate=rate, eps=float(eps))
     y = y.view(x.shape)
     if return_masks:
@@ -2097,10 +2021,8 @@ def dropout_residual_layernorm_backward(dy, gamma, saved, dy2=None):
     dx = torch.empty_like(xhat)
     dg = torch.empty(D, device=xhat.device, dtype=torch.float32)
     db = torch.empty(D, device=xhat.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_drop_res_ln_bwd", ("mgnns_drop_res_ln_bwd", D), L.mgnns_drop_res_ln_bwd, _p(dy), _p(dy2), _p(xhat),
-            _p(saved["sig"]), _p(saved["keep"]), rows, D, _p(gamma), saved["eps"], saved["rate"], _p(dres), _p(dx), _p(dg), _p(db),
-            _stream())
+    _launch("mgnns_drop_res_ln_bwd", _p(dy), _p(dy2), _p(xhat), _p(saved["sig"]), _p(saved["keep"]), rows, D, _p(gamma), saved["eps"],
+            saved["rate"], _p(dres), _p(dx), _p(dg), _p(db), _stream(), key=(D,))
     return dres, dx, dg, db
 
 
@@ -2112,9 +2034,7 @@ def train_eltwise(op, a, b):
     if a.shape != b.shape:
         raise ValueError("train_eltwise shapes %s / %s" % (tuple(a.shape), tuple(b.shape)))
     y = torch.empty_like(a)
-    L = _lib.lib()
-    _launch("mgnns_train_eltwise", ("mgnns_train_eltwise", op), L.mgnns_train_eltwise, int(op), _p(a), _p(b), a.numel(), _p(y),
-            _stream())
+    _launch("mgnns_train_eltwise", int(op), _p(a), _p(b), a.numel(), _p(y), _stream(), key=(op,))
     return y
 
 
@@ -2135,7 +2055,7 @@ def imgbank_wgrad(feat, dbank, split=False):
     name = "mgnns_imgbank_wgrad_split" if split else "mgnns_imgbank_wgrad"
     nbytes = getattr(L, name + "_workspace_bytes")(B, K, P, N)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
-    _launch(name, (name, B, P), getattr(L, name), _p(feat), _p(dbank), B, K, P, N, _p(dW), _p(db), _p(ws), nbytes, _stream())
+    _launch(name, _p(feat), _p(dbank), B, K, P, N, _p(dW), _p(db), _p(ws), nbytes, _stream(), key=(B, P))
     return dW, db
 
 
@@ -2147,7 +2067,7 @@ def map_argmax(feat):
     if K <= 0 or P <= 0:
         raise ValueError("feature map %s: need K, P > 0" % (tuple(feat.shape),))
     arg = torch.empty(B, K, device=feat.device, dtype=torch.int32)
-    _launch("mgnns_map_argmax", ("mgnns_map_argmax", B, P), _lib.lib().mgnns_map_argmax, _p(feat), B, K, P, _p(arg), _stream())
+    _launch("mgnns_map_argmax", _p(feat), B, K, P, _p(arg), _stream(), key=(B, P))
     return arg
 
 
@@ -2190,11 +2110,10 @@ def imgbank_dgrad(dbank, weight, dpooled=None, arg=None, positions=None, out=Non
     if split and dbank is not None:
         nbytes = L.mgnns_imgbank_dgrad_split_workspace_bytes(B, K, P, N)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-        _launch("mgnns_imgbank_dgrad_split", ("mgnns_imgbank_dgrad_split", B, P), L.mgnns_imgbank_dgrad_split, _p(dbank), _p(weight),
-                _p(dpooled), _p(arg), B, K, P, N, _p(dX), _p(ws), nbytes, _stream())
+        _launch("mgnns_imgbank_dgrad_split", _p(dbank), _p(weight), _p(dpooled), _p(arg), B, K, P, N, _p(dX), _p(ws), nbytes, _stream(),
+                key=(B, P))
         return dX
-    _launch("mgnns_imgbank_dgrad", ("mgnns_imgbank_dgrad", B, P), L.mgnns_imgbank_dgrad, _p(dbank), _p(weight), _p(dpooled),
-            _p(arg), B, K, P, N, _p(dX), _stream())
+    _launch("mgnns_imgbank_dgrad", _p(dbank), _p(weight), _p(dpooled), _p(arg), B, K, P, N, _p(dX), _stream(), key=(B, P))
     return dX
 
 
@@ -2216,9 +2135,7 @@ def label_attn_train(Q, K, V, n_heads, seed, rate, return_masks=False):
     x = torch.empty(B, NLQ, hid, device=K.device, dtype=torch.float32)
     P = torch.empty_like(x)
     keep = torch.empty(B, NLQ, hid, device=K.device, dtype=torch.uint8)
-    L = _lib.lib()
-    _launch("mgnns_label_attn_train_fwd", ("mgnns_label_attn_train_fwd",), L.mgnns_label_attn_train_fwd, _p(Q), _p(K), _p(V), B, NLQ,
-            n_heads, dh, _seed64(seed), rate, _p(x), _p(P), _p(keep), _stream())
+    _launch("mgnns_label_attn_train_fwd", _p(Q), _p(K), _p(V), B, NLQ, n_heads, dh, _seed64(seed), rate, _p(x), _p(P), _p(keep), _stream())
     saved = dict(P=P, keep=keep, rate=rate, n_heads=n_heads)
     if return_masks:
         return x, saved, keep.bool()
@@ -2237,8 +2154,8 @@ def label_attn_train_backward(dx, Q, K, V, saved):
     L = _lib.lib()
     nbytes = L.mgnns_label_attn_train_bwd_workspace_bytes(B, NLQ, H, hid // H)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=K.device)
-    _launch("mgnns_label_attn_train_bwd", ("mgnns_label_attn_train_bwd",), L.mgnns_label_attn_train_bwd, _p(dx), _p(Q), _p(K), _p(V),
-            _p(saved["P"]), _p(saved["keep"]), B, NLQ, H, hid // H, saved["rate"], _p(dQ), _p(dK), _p(dV), _p(ws), nbytes, _stream())
+    _launch("mgnns_label_attn_train_bwd", _p(dx), _p(Q), _p(K), _p(V), _p(saved["P"]), _p(saved["keep"]), B, NLQ, H, hid // H,
+            saved["rate"], _p(dQ), _p(dK), _p(dV), _p(ws), nbytes, _stream())
     return dQ, dK, dV
 
 
@@ -2248,9 +2165,7 @@ def dropout(x, seed, site, rate, return_masks=False):
     rate = _chk_rate(rate)
     y = torch.empty_like(x)
     keep = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
-    L = _lib.lib()
-    _launch("mgnns_dropout_fwd", ("mgnns_dropout_fwd",), L.mgnns_dropout_fwd, _p(x), x.numel(), _seed64(seed), int(site), rate, _p(y),
-            _p(keep), _stream())
+    _launch("mgnns_dropout_fwd", _p(x), x.numel(), _seed64(seed), int(site), rate, _p(y), _p(keep), _stream())
     if return_masks:
         return y, keep, keep.bool()
     return y, keep
@@ -2263,9 +2178,7 @@ def dropout_backward(dy, keep, rate):
     if dy.shape != keep.shape:
         raise ValueError("dropout_backward shapes %s / %s" % (tuple(dy.shape), tuple(keep.shape)))
     dx = torch.empty_like(dy)
-    L = _lib.lib()
-    _launch("mgnns_dropout_bwd", ("mgnns_dropout_bwd",), L.mgnns_dropout_bwd, _p(dy), _p(keep), dy.numel(), _chk_rate(rate), _p(dx),
-            _stream())
+    _launch("mgnns_dropout_bwd", _p(dy), _p(keep), dy.numel(), _chk_rate(rate), _p(dx), _stream())
     return dx
 
 
@@ -2274,14 +2187,13 @@ def dropout_mask(seed, site, rate, shape, device):
     how tests and tools rebuild a training forward's dropout from the seeds the modules keep (`last_dropout_seed`).  Sites index
     their tensors flat: DROP_ATTN [H*B, 1, L], DROP_FC / DROP_FFN [B, D], DROP_LABEL_ATTN [B, NLQ, hid], DROP_HEAD [B, D]."""
     keep = torch.empty(tuple(shape), device=device, dtype=torch.uint8)
-    L = _lib.lib()
-    _launch("mgnns_dropout_mask", ("mgnns_dropout_mask",), L.mgnns_dropout_mask, _seed64(seed), int(site), _chk_rate(rate),
-            keep.numel(), _p(keep), _stream())
+    _launch("mgnns_dropout_mask", _seed64(seed), int(site), _chk_rate(rate), keep.numel(), _p(keep), _stream())
     return keep.bool()
 
 
 # ---- training mode of the text encoders (csrc/text_train.hip; fp32, GPU only) ---------------------------------------------
-DROP_LSTM, DROP_TEXT_GCN = 5, 6            # the BiLSTM's inter-layer dropout [B, T, 2H], the text GCN's dropout [B, D]
+# the BiLSTM's inter-layer dropout [B, T, 2H], the text GCN's dropout [B, D]
+DROP_LSTM, DROP_TEXT_GCN = _C["MGNNS_DROP_LSTM"], _C["MGNNS_DROP_TEXT_GCN"]
 
 
 def bilstm_train(tok, lens, emb_table, weights, hidden, num_layers, seed, rate):
@@ -2313,10 +2225,10 @@ def bilstm_train(tok, lens, emb_table, weights, hidden, num_layers, seed, rate):
     L = _lib.lib()
     nbytes = L.mgnns_bilstm_train_workspace_bytes(B, T, hidden)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    _launch("mgnns_bilstm_train_fwd", ("mgnns_bilstm_train_fwd",), L.mgnns_bilstm_train_fwd, _p(tok), _p(lens), B, T, _p(emb_table),
-            emb_table.shape[0], emb_table.shape[1], hidden, num_layers, arr([c[0].data_ptr() for c in cat]),
-            arr([c[1].data_ptr() for c in cat]), arr([w[1].data_ptr() for w in weights]), arr([w[3].data_ptr() for w in weights]),
-            _seed64(seed), rate, _p(meta), rows, _p(gates), _p(cells), _p(mid), _p(mid_d), _p(out), _p(ws), ws.numel(), _stream())
+    _launch("mgnns_bilstm_train_fwd", _p(tok), _p(lens), B, T, _p(emb_table), emb_table.shape[0], emb_table.shape[1], hidden, num_layers,
+            arr([c[0].data_ptr() for c in cat]), arr([c[1].data_ptr() for c in cat]), arr([w[1].data_ptr() for w in weights]),
+            arr([w[3].data_ptr() for w in weights]), _seed64(seed), rate, _p(meta), rows, _p(gates), _p(cells), _p(mid), _p(mid_d), _p(out),
+            _p(ws), ws.numel(), _stream())
     saved = dict(tok=tok, lens=lens, B=B, T=T, rows=rows, n_rows=int(lens.clamp(0, T).sum().item()), hidden=hidden,
                  num_layers=num_layers, seed=seed, rate=rate, meta=meta, gates=gates, cells=cells, mid=mid, mid_d=mid_d, out=out,
                  cat=cat)
@@ -2334,9 +2246,7 @@ def gather_rows(src, idx, M):
     _chk(src, "src", ndim=2)
     _chk(idx, "idx", torch.int32)
     dst = torch.empty(M, src.shape[1], device=src.device, dtype=torch.float32)
-    L = _lib.lib()
-    _launch("mgnns_gather_rows", ("mgnns_gather_rows",), L.mgnns_gather_rows, _p(src), src.shape[0], src.shape[1], _p(idx), M, _p(dst),
-            _stream())
+    _launch("mgnns_gather_rows", _p(src), src.shape[0], src.shape[1], _p(idx), M, _p(dst), _stream())
     return dst
 
 
@@ -2353,9 +2263,8 @@ def keyed_row_sum(keys, values, n_out, skip_below=0):
     if keys.numel() == 0:
         return out
     sk, perm = torch.sort(keys, stable=True)
-    L = _lib.lib()
-    _launch("mgnns_keyed_row_sum", ("mgnns_keyed_row_sum",), L.mgnns_keyed_row_sum, _p(sk.contiguous()), _p(perm.contiguous()), keys.numel(),
-            _p(values), D, values.shape[0], int(skip_below), _p(out), n_out, _stream())
+    _launch("mgnns_keyed_row_sum", _p(sk.contiguous()), _p(perm.contiguous()), keys.numel(), _p(values), D, values.shape[0],
+            int(skip_below), _p(out), n_out, _stream())
     return out
 
 
@@ -2367,7 +2276,6 @@ def bilstm_train_backward(dout, saved, weights, emb_table, need_emb=True):
     B, T, H, nl, M = s["B"], s["T"], s["hidden"], s["num_layers"], s["n_rows"]
     G = 4 * H
     pack_tok, pack_pos = _bilstm_meta(s)
-    L = _lib.lib()
     grads = [None] * (2 * nl)
     demb = torch.zeros_like(emb_table) if need_emb else None
     if M == 0:
@@ -2377,13 +2285,11 @@ def bilstm_train_backward(dout, saved, weights, emb_table, need_emb=True):
     dcur = _chk(dout.contiguous(), "dbank")
     for layer in range(nl - 1, -1, -1):
         dz = torch.empty(M, 2 * G, device=dout.device, dtype=torch.float32)
-        _launch("mgnns_bilstm_train_bwd_rec", ("mgnns_bilstm_train_bwd_rec",), L.mgnns_bilstm_train_bwd_rec, _p(dcur), _p(s["lens"]), B, T,
-                _p(s["meta"]), s["rows"], _p(s["gates"][layer]), _p(s["cells"][layer]), _p(weights[2 * layer][1]),
-                _p(weights[2 * layer + 1][1]), _p(dz), _stream())
+        _launch("mgnns_bilstm_train_bwd_rec", _p(dcur), _p(s["lens"]), B, T, _p(s["meta"]), s["rows"], _p(s["gates"][layer]),
+                _p(s["cells"][layer]), _p(weights[2 * layer][1]), _p(weights[2 * layer + 1][1]), _p(dz), _stream())
         hout = s["out"] if layer == nl - 1 else s["mid"]
         hprev = torch.empty(M, 2 * H, device=dout.device, dtype=torch.float32)
-        _launch("mgnns_bilstm_train_hprev", ("mgnns_bilstm_train_hprev",), L.mgnns_bilstm_train_hprev, _p(hout), _p(s["lens"]), B, T,
-                _p(s["meta"]), M, _p(hprev), _stream())
+        _launch("mgnns_bilstm_train_hprev", _p(hout), _p(s["lens"]), B, T, _p(s["meta"]), M, _p(hprev), _stream())
         x = gather_rows(emb_table, pack_tok, M) if layer == 0 else gather_rows(s["mid_d"].view(B * T, 2 * H), pack_pos, M)
         dwih, dbih = wgrad(dz, x)
         dwhh = wgrad(dz, hprev, bias=False)[0]
@@ -2394,8 +2300,7 @@ def bilstm_train_backward(dout, saved, weights, emb_table, need_emb=True):
         if layer > 0:
             dx = matmul(dz, s["cat"][layer][0])
             dprev = torch.zeros(B, T, 2 * H, device=dout.device, dtype=torch.float32)
-            _launch("mgnns_bilstm_train_unpack_drop", ("mgnns_bilstm_train_unpack_drop",), L.mgnns_bilstm_train_unpack_drop, _p(dx),
-                    _p(pack_pos), M, B, T, _seed64(s["seed"]), s["rate"], _p(dprev), _stream())
+            _launch("mgnns_bilstm_train_unpack_drop", _p(dx), _p(pack_pos), M, B, T, _seed64(s["seed"]), s["rate"], _p(dprev), _stream())
             dcur = dprev
         elif need_emb:
             dx = matmul(dz, s["cat"][0][0])
@@ -2420,10 +2325,8 @@ def textgcn_train(tok, node_hidden, edge_w, pmi_dev, ngram, max_length, seed, ra
     presum = torch.empty(B, D, device=tok.device, dtype=torch.float32)
     win = torch.empty(B, Tm, D, device=tok.device, dtype=torch.int16)
     if B:
-        L = _lib.lib()
-        _launch("mgnns_textgcn_train_fwd", ("mgnns_textgcn_train_fwd",), L.mgnns_textgcn_train_fwd, _p(tok), B, T, _p(node_hidden), V, D,
-                _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), int(ngram), int(max_length), _seed64(seed), rate, _p(out), _p(presum),
-                _p(win), _stream())
+        _launch("mgnns_textgcn_train_fwd", _p(tok), B, T, _p(node_hidden), V, D, _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), int(ngram),
+                int(max_length), _seed64(seed), rate, _p(out), _p(presum), _p(win), _stream())
     return out, dict(presum=presum, win=win, seed=seed, rate=rate, ngram=int(ngram), max_length=int(max_length))
 
 
@@ -2446,10 +2349,9 @@ def textgcn_train_backward(dy, tok, node_hidden, edge_w, pmi_dev, saved, need_no
     keyR = torch.empty(B, Tm, device=tok.device, dtype=torch.int32)
     Eg = torch.empty(B, Tm, W, device=tok.device, dtype=torch.float32)
     keyE = torch.empty(B, Tm, W, device=tok.device, dtype=torch.int32)
-    L = _lib.lib()
-    _launch("mgnns_textgcn_train_bwd", ("mgnns_textgcn_train_bwd",), L.mgnns_textgcn_train_bwd, _p(tok), B, T, _p(node_hidden), V, D,
-            _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), g, saved["max_length"], _seed64(saved["seed"]), saved["rate"], _p(dy),
-            _p(saved["presum"]), _p(saved["win"]), _p(R), _p(keyR), _p(Eg), _p(keyE), _stream())
+    _launch("mgnns_textgcn_train_bwd", _p(tok), B, T, _p(node_hidden), V, D, _p(ew), ew.shape[0], _p(rp), _p(col), _p(eid), g,
+            saved["max_length"], _seed64(saved["seed"]), saved["rate"], _p(dy), _p(saved["presum"]), _p(saved["win"]), _p(R), _p(keyR),
+            _p(Eg), _p(keyE), _stream())
     if need_nodes:
         dn = keyed_row_sum(keyR, R.view(B * Tm, D), V)
     if need_edges:

@@ -17,11 +17,10 @@ _cache = {}
 
 def _concurrent(a, b, slots, spin_us=150):
     """True iff a kernel on stream b can run while stream a is busy."""
-    L = _lib.lib()
     slots.zero_()
     torch.cuda.synchronize()
-    _lib.check(L.mgnns_debug_spin(spin_us, slots.data_ptr(), 0, a.cuda_stream), "mgnns_debug_spin")
-    _lib.check(L.mgnns_debug_stamp(slots.data_ptr(), 1, b.cuda_stream), "mgnns_debug_stamp")
+    _lib.call("mgnns_debug_spin", spin_us, slots.data_ptr(), 0, a.cuda_stream)
+    _lib.call("mgnns_debug_stamp", slots.data_ptr(), 1, b.cuda_stream)
     torch.cuda.synchronize()
     end_a, at_b = slots.cpu().tolist()[:2]
     return at_b < end_a
@@ -42,7 +41,7 @@ def independent_streams(device, n=3, candidates=16):
         # a stream is bound to its hardware queue (and the queue created) at its FIRST launch, which takes 0.1-5 ms:
         # touch every candidate before timing anything
         for c in [main] + pool:
-            _lib.check(_lib.lib().mgnns_debug_stamp(slots.data_ptr(), 2, c.cuda_stream), "mgnns_debug_stamp")
+            _lib.call("mgnns_debug_stamp", slots.data_ptr(), 2, c.cuda_stream)
         torch.cuda.synchronize(device)
         for c in pool:
             if len(chosen) == n:

@@ -281,12 +281,11 @@ def text_case(n):
     t_eval = timeit(lambda: ops.bilstm(tok, lens, emb, ws, 150, 2, recurrence="f32"), n)
     dbank = torch.randn_like(bank)
     t_bwd = timeit(lambda: ops.bilstm_train_backward(dbank, saved, ws, emb), n)
-    L = ops._lib.lib()
     dz = torch.empty(rows, 1200, device=DEV)
 
     def rec():
-        ops._launch("x", "x", L.mgnns_bilstm_train_bwd_rec, ops._p(dbank), ops._p(lens), B, T, ops._p(saved["meta"]), saved["rows"],
-                    ops._p(saved["gates"][1]), ops._p(saved["cells"][1]), ops._p(ws[2][1]), ops._p(ws[3][1]), ops._p(dz), ops._stream())
+        ops._lib.call("mgnns_bilstm_train_bwd_rec", ops._p(dbank), ops._p(lens), B, T, ops._p(saved["meta"]), saved["rows"],
+                      ops._p(saved["gates"][1]), ops._p(saved["cells"][1]), ops._p(ws[2][1]), ops._p(ws[3][1]), ops._p(dz), ops._stream())
     t_rec = timeit(rec, n)
     res["bilstm"] = {"rows": rows, "eval_fwd_us": round(t_eval, 1), "train_fwd_us": round(t_fwd, 1), "bwd_us": round(t_bwd, 1),
                      "bwd_rec_one_layer_us": round(t_rec, 1),

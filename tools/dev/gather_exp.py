@@ -6,7 +6,6 @@ import torch
 from mgnns_amd import _lib, stress
 from tools.dev.slabcopy_exp_lib import time_graph
 dev = "cuda:0"; n = 10000
-L = _lib.lib()
 for pitch in (2048, 4096):
     kk = max(4, -(-stress.COLD_BYTES // (n * pitch)))
     xs = [torch.randint(0, 255, (n, pitch), device=dev, dtype=torch.uint8) for _ in range(kk)]
@@ -16,7 +15,7 @@ for pitch in (2048, 4096):
             for wgx in (128, 256, 512):
                 m = 3 | (k << 12)
                 def run(x):
-                    _lib.check(L.mgnns_debug_slabcopy(x.data_ptr(), y.data_ptr(), n, pitch, piece, m, wgx, torch.cuda.current_stream().cuda_stream), "slabcopy")
+                    _lib.call("mgnns_debug_slabcopy", x.data_ptr(), y.data_ptr(), n, pitch, piece, m, wgx, torch.cuda.current_stream().cuda_stream)
                 warm = time_graph(run, [(xs[0],)] * 8)
                 cold = time_graph(run, [(x,) for x in xs])
                 by = n * pitch * k

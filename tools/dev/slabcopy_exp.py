@@ -5,7 +5,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch
 from mgnns_amd import _lib, stress
 dev = "cuda:0"; n = 10000
-L = _lib.lib()
 def time_graph(fn, arg_sets, reps=5):
     for a in arg_sets: fn(*a)
     torch.cuda.synchronize()
@@ -34,7 +33,7 @@ for pitch in (2048, 4096):
             for wgx in (64, 128, 256, 512):
                 m = mode | (256 if lin else 0)
                 def run(x, y):
-                    _lib.check(L.mgnns_debug_slabcopy(x.data_ptr(), y.data_ptr(), n, pitch, piece, m, wgx, torch.cuda.current_stream().cuda_stream), "slabcopy")
+                    _lib.call("mgnns_debug_slabcopy", x.data_ptr(), y.data_ptr(), n, pitch, piece, m, wgx, torch.cuda.current_stream().cuda_stream)
                 ms = time_graph(run, list(zip(xs, ys)))
                 by = n * pitch * (2 if name.startswith("copy") else 1)
                 print(json.dumps({"pitch": pitch, "what": name, "piece": piece, "linear": lin, "wgx": wgx, "us": round(ms * 1e3, 2), "GBps": round(by / ms / 1e6)}), flush=True)
