@@ -680,11 +680,7 @@ class Multi_GCN_Multihead_Att(nn.Module):
             if isinstance(trunk, _NoTrunk):
                 raise RuntimeError("%s holds [B,3,H,W] images but the model was built without that CNN trunk: pass a trunk to "
                                    "Multi_GCN_Multihead_Att or feed precomputed [B,2048,h,w] feature maps" % name)
-            if self.trunk_train_stem:
-                return trunk.forward_train(x, self.trunk_train_stages, batchnorm=self.trunk_train_batchnorm, stem=True)
-            if self.trunk_train_batchnorm == 'frozen':
-                return trunk.forward_train(x, self.trunk_train_stages)
-            return trunk.forward_train(x, self.trunk_train_stages, batchnorm=self.trunk_train_batchnorm)
+            return trunk.forward_train(x, self.trunk_train_stages, batchnorm=self.trunk_train_batchnorm, stem=self.trunk_train_stem)
         if not (x.dim() == 4 and x.shape[1] == 2048):
             raise NotImplementedError("training mode takes precomputed [B,2048,h,w] feature maps for %s (the CNN trunks do not "
                                       "train); got %s" % (name, tuple(x.shape)))

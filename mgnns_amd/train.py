@@ -9,17 +9,21 @@ generator per training forward (kept as `last_dropout_seed`), so torch.manual_se
 The rest of the model trains through the Functions below the fusion layers' (csrc/model_train.hip): the image memory banks
 (their weight gradient is the backward's hot path), the label GCN (propagated back with the transposed adjacency), the label
 attention with dropout on its probabilities, the channel tails and the classifier with its dropout.  The text encoders train
-through the Functions at the end of this file once unfrozen.  Feature maps that require a gradient get one (ImgBankFunction,
+through their own Functions below once unfrozen.  Feature maps that require a gradient get one (ImgBankFunction,
 csrc/map_grad.hip), so a torch trunk in front of the model fine-tunes through torch's own backward; the trunks of
-mgnns_amd.trunk fine-tune their trailing bottleneck stages with frozen BatchNorm statistics through TrunkStageFunction
-(csrc/conv_train.hip, model.unfreeze_trunks()), or with the statistics of the batch -- the reference's semantics -- through
-TrunkStageBatchNormFunction (csrc/bn_train.hip, model.unfreeze_trunks(batchnorm='batch')).  With all four stages trainable the
-stem -- conv1, bn1, ReLU, max-pool -- trains too, through TrunkStemFunction / TrunkStemBatchNormFunction (csrc/stem_train.hip,
-model.unfreeze_trunks(4, stem=True)): nothing of a trunk is then left frozen.
+mgnns_amd.trunk fine-tune their trailing bottleneck stages through TrunkStageFunction, at the end of this file: in mode 'frozen'
+with frozen BatchNorm statistics (csrc/conv_train.hip, model.unfreeze_trunks()), in mode 'batch' with the statistics of the
+batch -- the reference's semantics -- (csrc/bn_train.hip, model.unfreeze_trunks(batchnorm='batch')).  With all four stages
+trainable the stem -- conv1, bn1, ReLU, max-pool -- trains too, through TrunkStemFunction in the same two modes
+(csrc/stem_train.hip, model.unfreeze_trunks(4, stem=True)): nothing of a trunk is then left frozen.  Both walk a bottleneck once
+forward (trunk.run_block) and once backward; the modes differ in one step per layer (_stage_step, _layer_backward), and what a
+forward keeps for its backward is one named record (save_record / saved_record).
 """
+from types import SimpleNamespace
+
 import torch
 
-from . import ops
+from . import ops, trunk
 
 
 def draw_seed():
@@ -386,21 +390,111 @@ def bilstm_train_forward(lstm, embedding, text, text_lens, rate):
                                      *flat)
 
 
-# ---- the CNN trunks' trailing stages (csrc/conv_train.hip) ------------------------------------------------------------------
+# ---- the CNN trunks: stages and stem (csrc/conv_train.hip, bn_train.hip, stem_train.hip) ------------------------
+TRUNK_BATCHNORM_MODES = ('frozen', 'batch')
+_PACK_KIND = {'frozen': 'folded', 'batch': 'raw'}
+
+
+class _Saved(int):
+    """Where a record's tensor sits among ctx.saved_tensors."""
+
+
+def _map_record(node, leaf):
+    if isinstance(node, SimpleNamespace):
+        return SimpleNamespace(**{k: _map_record(v, leaf) for k, v in vars(node).items()})
+    if isinstance(node, list):
+        return [_map_record(v, leaf) for v in node]
+    return leaf(node)
+
+
+def save_record(ctx, rec):
+    """Keep a record -- SimpleNamespaces and lists, nested -- for the backward.  Its tensors go through ctx.save_for_backward (so
+    autograd's version check guards parameters and running statistics); what is not a tensor stays where it is."""
+    flat = []
+
+    def leaf(v):
+        if not torch.is_tensor(v):
+            return v
+        flat.append(v)
+        return _Saved(len(flat) - 1)
+    ctx.record = _map_record(rec, leaf)
+    ctx.save_for_backward(*flat)
+
+
+def saved_record(ctx):
+    """The record save_record kept, rebuilt over ctx.saved_tensors."""
+    st = ctx.saved_tensors
+    return _map_record(ctx.record, lambda v: st[v] if isinstance(v, _Saved) else v)
+
+
+def _batch_norm(z, bn, gamma, beta, **kw):
+    """Training-mode BatchNorm of z: the statistics of the batch (ops.bn_stats_bf16_nhwc, which also moves running_mean /
+    running_var; num_batches_tracked goes up by one), then gamma, beta, the residual and the ReLU in one sweep
+    (ops.bn_apply_bf16_nhwc) -> (activation, mean, rstd)."""
+    running = (bn.running_mean, bn.running_var) if bn.track_running_stats and bn.running_mean is not None else None
+    mean, rstd = ops.bn_stats_bf16_nhwc(z, bn.eps, running=running, momentum=bn.momentum)
+    if running is not None and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return ops.bn_apply_bf16_nhwc(z, mean, rstd, gamma.detach(), beta.detach(), **kw), mean, rstd
+
+
+def _layer_backward(mode, layer, g, wgrad):
+    """The one step of a backward that depends on the mode: from g, the gradient of a layer's output (masked by its ReLU), to the
+    gradient of its convolution's output, leaving layer.grads = (dW, dgamma, dbeta) for those of layer.want.  wgrad(gz) ->
+    (dW', db') in the pack's layout.  'frozen': BatchNorm is folded into the pack, so the convolution's gradient is g itself and
+    ops.conv_bn_unfold takes (dW', db') to the fp32 parameters through the running statistics.  'batch':
+    ops.bn_backward_bf16_nhwc differentiates through the statistics of the batch, and dW' of the raw pack is the weight's own
+    gradient up to its layout."""
+    layer.grads = (None, None, None)
+    if mode == 'frozen':
+        if any(layer.want):
+            layer.grads = ops.conv_bn_unfold(*wgrad(g), layer.w, (layer.gamma, layer.mean, layer.var, layer.eps), want=layer.want)
+        return g
+    gz, dgamma, dbeta = ops.bn_backward_bf16_nhwc(g, layer.z, layer.mean, layer.rstd, layer.gamma, want=layer.want[1:])
+    dw = None
+    if layer.want[0]:
+        dw = wgrad(gz)[0]
+        dw = dw.view(dw.shape[0], layer.k, layer.k, -1).permute(0, 3, 1, 2).contiguous()
+    layer.grads = (dw, dgamma, dbeta)
+    return gz
+
+
+def _stage_step(mode, packs, layers, bns, acts):
+    """trunk.run_block's step for one block of the stage Function: layer j's activation, kept in acts[j].  'frozen': the eval
+    forward's step on the folded packs.  'batch': the raw convolution z, kept in the layer's record with (mean, rstd), then
+    _batch_norm."""
+    conv = trunk.conv_step(packs)                                    # layer j's convolution on its pack, either kind
+
+    def step(j, t, relu=True, **kw):
+        if mode == 'frozen':
+            acts[j] = conv(j, t, relu=relu, **kw)
+        else:
+            layer = layers[j]
+            layer.z = conv(j, t, relu=False)
+            acts[j], layer.mean, layer.rstd = _batch_norm(layer.z, bns[j], layer.gamma, layer.beta, relu=relu, **kw)
+        return acts[j]
+    return step
+
+
 class TrunkStageFunction(torch.autograd.Function):
-    """map [B, C, h, w] fp32 = a chain of bottlenecks out = relu(conv3(o2) + idn(x)), o2 = relu(conv2(o1)), o1 = relu(conv1(x)), run by
-    the eval forward's kernels on the folded bf16 weights (BatchNorm keeps its running statistics) with x, o1, o2 of every block
-    and the map kept for the backward.  x: NHWC bf16, or NCHW fp32 (converted, as is its gradient).  blocks: the Bottlenecks;
-    packs: trunk.block_packs of each; keep: None or a list that receives the saved activations {"x", "blocks": [(o1, o2, out)]}
-    (what tests compute their reference from); params: (conv.weight, bn.weight, bn.bias) per trunk.block_layers of each block.
-    Backward: dmap is masked by the map and rounded to bf16 NHWC, then per block, last to first: weight
-    gradients of conv3 and the downsample from g_out; g_o2 = dgrad_conv3(g_out) masked by o2; wgrad conv2; g_o1 =
-    dgrad_conv2(g_o2) masked by o1; wgrad conv1; g_x = dgrad_conv1(g_o1) + (g_out or dgrad_down(g_out)), masked by x where x is a
-    block's output.  Gradients travel in bf16, accumulate in fp32 and reach the fp32 parameters through ops.conv_bn_unfold;
-    a parameter gets one iff it requires one, and so does x."""
+    """map [B, C, h, w] fp32 = a chain of bottlenecks out = relu(layer3(o2) + idn(x)), o2 = relu(layer2(o1)), o1 = relu(layer1(x)),
+    walked by trunk.run_block.  x: NHWC bf16, or NCHW fp32 (converted, as is its gradient).  blocks: the Bottlenecks; params:
+    (conv.weight, bn.weight, bn.bias) per trunk.block_layers of each block.
+    mode 'frozen' (DESIGN.md 13): a layer is the eval forward's convolution on the folded bf16 weights (packs: trunk.block_packs of
+    each block), BatchNorm keeping its running statistics.  keep: None or a list that receives {"x", "blocks": [(o1, o2, out)]}.
+    mode 'batch' (DESIGN.md 14), the reference's model.train() semantics: a layer is z = conv(x; bf16(conv.weight)) without a bias
+    (packs: trunk.block_packs_raw) and _batch_norm(z).  keep receives {"x", "blocks": [{"z": [z1, z2, z3(, z_d)], "stats":
+    [(mean, rstd), ...] -- both in trunk.block_layers order --, "o1", "o2", "out", "idn"}]}.
+    Kept for the backward, as one record (save_record): x; per block o1, o2, out; per layer its transposed pack and parameters and
+    the running statistics ('frozen') or z, mean, rstd ('batch').
+    Backward: dmap is masked by the map and rounded to bf16 NHWC, then per block, last to first, with ' = _layer_backward (which
+    also leaves the layer's parameter gradients): g3 = layer3'(g_out), g_d = down'(g_out); g2 = layer2'(dgrad3(g3) masked by o2);
+    g1 = layer1'(dgrad2(g2) masked by o1); g_x = dgrad1(g1) + (g_out or dgrad_d(g_d)), masked by x where x is a block's output.
+    Gradients travel in bf16 and every sum is fp32; the bf16 roundings of the weights and of z are straight-through.  A parameter
+    gets a gradient iff it requires one, and so does x."""
 
     @staticmethod
-    def forward(ctx, x, blocks, packs, keep, *params):
+    def forward(ctx, x, blocks, packs, keep, mode, *params):
         nchw = x.dtype == torch.float32
         if nchw:
             xh = x.detach().permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
@@ -408,323 +502,136 @@ class TrunkStageFunction(torch.autograd.Function):
             xh = x.detach().contiguous()
         else:
             raise TypeError("TrunkStageFunction: x must be NHWC bfloat16 or NCHW float32, got %s" % x.dtype)
-        y, acts, stats = xh, [], []
+        params = iter(params)
+        y, rec, kept = xh, SimpleNamespace(x=xh, blocks=[]), []
         for i, (blk, pk) in enumerate(zip(blocks, packs)):
-            last = i == len(blocks) - 1
-            idn = y
-            if len(pk) == 4:
-                wt, bias, _, k, s, p = pk[3]
-                idn = ops.conv_bf16_nhwc(y, wt, bias, k, s, p, relu=False)
-            wt, bias, _, k, s, p = pk[0]
-            o1 = ops.conv_bf16_nhwc(y, wt, bias, k, s, p)
-            wt, bias, _, k, s, p = pk[1]
-            o2 = ops.conv_bf16_nhwc(o1, wt, bias, k, s, p)
-            wt, bias, _, k, s, p = pk[2]
-            y = ops.conv_bf16_nhwc(o2, wt, bias, k, s, p, residual=idn, out_nchw_f32=last)
-            acts += [o1, o2, y]
-            stats += [t for _, bn in _block_layers(blk) for t in (bn.running_mean, bn.running_var)]
-        if keep is not None:
-            keep.append({"x": xh, "blocks": [tuple(acts[3 * i:3 * i + 3]) for i in range(len(blocks))]})
-        ctx.nchw, ctx.nblk = nchw, len(blocks)
-        ctx.geom = [[(k, s, p) for _, _, _, k, s, p in pk] for pk in packs]
-        ctx.eps = [[bn.eps for _, bn in _block_layers(blk)] for blk in blocks]
-        wTs = [c[2] for pk in packs for c in pk]
-        ctx.save_for_backward(xh, *acts, *wTs, *stats, *params)
-        return y
-
-    @staticmethod
-    def backward(ctx, dmap):
-        st = ctx.saved_tensors
-        nb = ctx.nblk
-        nconv = [len(g) for g in ctx.geom]
-        total = sum(nconv)
-        xh, acts = st[0], st[1:1 + 3 * nb]
-        wTs, stats, params = st[1 + 3 * nb:1 + 3 * nb + total], st[1 + 3 * nb + total:1 + 3 * nb + 3 * total], st[1 + 3 * nb + 3 * total:]
-        need = ctx.needs_input_grad[4:]
-        grads = [None] * len(params)
-        base = [sum(nconv[:i]) for i in range(nb)]
-
-        def weight_grads(bi, ci, x_in, g):
-            j = base[bi] + ci
-            want = tuple(need[3 * j:3 * j + 3])
-            if not any(want):
-                return
-            k, s, p = ctx.geom[bi][ci]
-            dwp, dbp = ops.conv_wgrad_bf16_nhwc(x_in, g, k, s, p)
-            grads[3 * j:3 * j + 3] = ops.conv_bn_unfold(dwp, dbp, params[3 * j], (params[3 * j + 1], stats[2 * j], stats[2 * j + 1],
-                                                                               ctx.eps[bi][ci]), want=want)
-
-        def data_grad(bi, ci, g, x_in, mask=None, add=None):
-            k, s, p = ctx.geom[bi][ci]
-            return ops.conv_dgrad_bf16_nhwc(g, wTs[base[bi] + ci], tuple(x_in.shape[1:3]), k, s, p, mask=mask, add=add)
-
-        g = ops.map_grad_relu_nhwc(acts[3 * nb - 1], dmap.contiguous().float())
-        for bi in range(nb - 1, -1, -1):
-            x_in = acts[3 * bi - 1] if bi else xh
-            o1, o2 = acts[3 * bi], acts[3 * bi + 1]
-            down = nconv[bi] == 4
-            weight_grads(bi, 2, o2, g)
-            if down:
-                weight_grads(bi, 3, x_in, g)
-            g2 = data_grad(bi, 2, g, o2, mask=o2)
-            weight_grads(bi, 1, o1, g2)
-            g1 = data_grad(bi, 1, g2, o1, mask=o1)
-            weight_grads(bi, 0, x_in, g1)
-            if bi == 0 and not ctx.needs_input_grad[0]:
-                g = None
-                break
-            other = data_grad(bi, 3, g, x_in) if down else g
-            g = data_grad(bi, 0, g1, x_in, mask=x_in if bi else None, add=other)
-        if g is not None and ctx.nchw:
-            g = g.float().permute(0, 3, 1, 2).contiguous()
-        return (g, None, None, None, *grads)
-
-
-class TrunkStageBatchNormFunction(torch.autograd.Function):
-    """TrunkStageFunction with batch statistics, the reference's model.train() semantics for the stages it runs: every
-    convolution is z = conv(x; bf16(conv.weight)) without a bias (packs: trunk.block_packs_raw), every BatchNorm normalises z with
-    the statistics of the batch (ops.bn_stats_bf16_nhwc, which also moves running_mean / running_var; num_batches_tracked goes up by
-    one) and applies gamma, beta, the residual and the ReLU in one sweep (ops.bn_apply_bf16_nhwc); the last block's output is the
-    fp32 NCHW map.  Kept for the backward: x, per block z1, o1, z2, o2, z3, out (and the downsample's z_d), and (mean, rstd) per
-    layer.  keep: None or a list that receives {"x", "blocks": [{"z": [z1, z2, z3(, z_d)], "stats": [(mean, rstd), ...] -- both in
-    trunk.block_layers order --, "o1", "o2", "out", "idn"}]}.  params: (conv.weight, bn.weight, bn.bias) per layer.
-    Backward: dmap is masked by the map and rounded to bf16 NHWC; then per block, last to first, with bn' = ops.bn_backward_bf16_nhwc
-    (which differentiates through the statistics): g_z3 = bn3'(g_out), g_zd = bn_d'(g_out), dW3 = wgrad(o2, g_z3), dWd = wgrad(x, g_zd),
-    g_o2 = dgrad3(g_z3) masked by o2, g_z2 = bn2'(g_o2), dW2 = wgrad(o1, g_z2), g_o1 = dgrad2(g_z2) masked by o1, g_z1 = bn1'(g_o1),
-    dW1 = wgrad(x, g_z1), g_x = dgrad1(g_z1) + (g_out or dgrad_d(g_zd)), masked by x where x is a block's output.  The bf16 roundings of
-    the weight and of z are straight-through; gradients travel in bf16 and every sum is fp32; dW of the raw pack is the weight's own
-    gradient up to its layout.  A parameter gets a gradient iff it requires one, and so does x."""
-
-    @staticmethod
-    def forward(ctx, x, blocks, packs, keep, *params):
-        nchw = x.dtype == torch.float32
-        if nchw:
-            xh = x.detach().permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
-        elif x.dtype == torch.bfloat16:
-            xh = x.detach().contiguous()
-        else:
-            raise TypeError("TrunkStageBatchNormFunction: x must be NHWC bfloat16 or NCHW float32, got %s" % x.dtype)
-
-        def bn_layer(z, bn, residual=None, relu=True, out_nchw_f32=False):
-            running = (bn.running_mean, bn.running_var) if bn.track_running_stats and bn.running_mean is not None else None
-            mean, rstd = ops.bn_stats_bf16_nhwc(z, bn.eps, running=running, momentum=bn.momentum)
-            if running is not None and bn.num_batches_tracked is not None:
-                bn.num_batches_tracked.add_(1)
-            y = ops.bn_apply_bf16_nhwc(z, mean, rstd, bn.weight.detach(), bn.bias.detach(), residual=residual, relu=relu,
-                                       out_nchw_f32=out_nchw_f32)
-            return y, (mean, rstd)
-
-        y, acts, stats, kept = xh, [], [], []
-        for i, (blk, pk) in enumerate(zip(blocks, packs)):
-            layers = _block_layers(blk)
-            raw = lambda t, j: ops.conv_bf16_nhwc(t, pk[j][0], pk[j][1], *pk[j][3:], relu=False)
-            idn, zd, st_d = y, None, None
-            if len(pk) == 4:
-                zd = raw(y, 3)
-                idn, st_d = bn_layer(zd, layers[3][1], relu=False)
-            z1 = raw(y, 0)
-            o1, st1 = bn_layer(z1, layers[0][1])
-            z2 = raw(o1, 1)
-            o2, st2 = bn_layer(z2, layers[1][1])
-            z3 = raw(o2, 2)
-            y, st3 = bn_layer(z3, layers[2][1], residual=idn, out_nchw_f32=i == len(blocks) - 1)
-            zs, sts = [z1, z2, z3], [st1, st2, st3]
-            if zd is not None:
-                zs.append(zd)
-                sts.append(st_d)
-            acts += [o1, o2, y] + zs
-            stats += [t for s_ in sts for t in s_]
-            kept.append({"z": zs, "stats": sts, "o1": o1, "o2": o2, "out": y, "idn": idn})
+            bns = [bn for _, bn in trunk.block_layers(blk)]
+            layers = [SimpleNamespace(wT=wT, k=k, s=s, p=p, w=next(params), gamma=next(params), beta=next(params))
+                      for _, _, wT, k, s, p in pk]
+            if mode == 'frozen':
+                for layer, bn in zip(layers, bns):
+                    layer.mean, layer.var, layer.eps = bn.running_mean, bn.running_var, bn.eps
+            acts = {}
+            y, idn = trunk.run_block(y, len(pk) == 4, _stage_step(mode, pk, layers, bns, acts), last=i == len(blocks) - 1)
+            rec.blocks.append(SimpleNamespace(layers=layers, o1=acts[0], o2=acts[1], out=y))
+            if mode == 'frozen':
+                kept.append((acts[0], acts[1], y))
+            else:
+                kept.append({"z": [layer.z for layer in layers], "stats": [(layer.mean, layer.rstd) for layer in layers],
+                             "o1": acts[0], "o2": acts[1], "out": y, "idn": idn})
         if keep is not None:
             keep.append({"x": xh, "blocks": kept})
-        ctx.nchw = nchw
-        ctx.geom = [[(k, s, p) for _, _, _, k, s, p in pk] for pk in packs]
-        wTs = [c[2] for pk in packs for c in pk]
-        ctx.save_for_backward(xh, *acts, *stats, *wTs, *params)
+        ctx.nchw, ctx.mode = nchw, mode
+        save_record(ctx, rec)
         return y
 
     @staticmethod
     def backward(ctx, dmap):
-        st = list(ctx.saved_tensors)
-        nconv = [len(g) for g in ctx.geom]
-        nb, total = len(nconv), sum(nconv)
-        xh = st.pop(0)
-        blk_acts = []
-        for n in nconv:
-            blk_acts.append((st[0], st[1], st[2], st[3:3 + n]))            # o1, o2, out, [z per layer]
-            del st[:3 + n]
-        stats, wTs, params = st[:2 * total], st[2 * total:3 * total], st[3 * total:]
-        need = ctx.needs_input_grad[4:]
-        grads = [None] * len(params)
-        base = [sum(nconv[:i]) for i in range(nb)]
+        rec = saved_record(ctx)
+        need = iter(ctx.needs_input_grad[5:])
+        for blk in rec.blocks:
+            for layer in blk.layers:
+                layer.want = (next(need), next(need), next(need))
 
-        def bn_back(bi, ci, g):
-            j = base[bi] + ci
-            gz, grads[3 * j + 1], grads[3 * j + 2] = ops.bn_backward_bf16_nhwc(
-                g, blk_acts[bi][3][ci], stats[2 * j], stats[2 * j + 1], params[3 * j + 1], want=(need[3 * j + 1], need[3 * j + 2]))
-            return gz
+        def through(layer, x_in, g):
+            return _layer_backward(ctx.mode, layer, g, lambda gz: ops.conv_wgrad_bf16_nhwc(x_in, gz, layer.k, layer.s, layer.p))
 
-        def weight_grad(bi, ci, x_in, gz):
-            j = base[bi] + ci
-            if need[3 * j]:
-                k, s, p = ctx.geom[bi][ci]
-                dw = ops.conv_wgrad_bf16_nhwc(x_in, gz, k, s, p)[0]
-                grads[3 * j] = dw.view(dw.shape[0], k, k, -1).permute(0, 3, 1, 2).contiguous()
+        def dgrad(layer, g, x_in, mask=None, add=None):
+            return ops.conv_dgrad_bf16_nhwc(g, layer.wT, tuple(x_in.shape[1:3]), layer.k, layer.s, layer.p, mask=mask, add=add)
 
-        def data_grad(bi, ci, g, x_in, mask=None, add=None):
-            k, s, p = ctx.geom[bi][ci]
-            return ops.conv_dgrad_bf16_nhwc(g, wTs[base[bi] + ci], tuple(x_in.shape[1:3]), k, s, p, mask=mask, add=add)
-
-        g = ops.map_grad_relu_nhwc(blk_acts[-1][2], dmap.contiguous().float())
-        for bi in range(nb - 1, -1, -1):
-            x_in = blk_acts[bi - 1][2] if bi else xh
-            o1, o2 = blk_acts[bi][0], blk_acts[bi][1]
-            down = nconv[bi] == 4
-            gz3 = bn_back(bi, 2, g)
-            weight_grad(bi, 2, o2, gz3)
-            gzd = None
-            if down:
-                gzd = bn_back(bi, 3, g)
-                weight_grad(bi, 3, x_in, gzd)
-            gz2 = bn_back(bi, 1, data_grad(bi, 2, gz3, o2, mask=o2))
-            weight_grad(bi, 1, o1, gz2)
-            gz1 = bn_back(bi, 0, data_grad(bi, 1, gz2, o1, mask=o1))
-            weight_grad(bi, 0, x_in, gz1)
+        g = ops.map_grad_relu_nhwc(rec.blocks[-1].out, dmap.contiguous().float())
+        for bi in range(len(rec.blocks) - 1, -1, -1):
+            blk = rec.blocks[bi]
+            x_in = rec.blocks[bi - 1].out if bi else rec.x
+            l1, l2, l3 = blk.layers[:3]
+            down = blk.layers[3] if len(blk.layers) == 4 else None
+            g3 = through(l3, blk.o2, g)
+            gd = through(down, x_in, g) if down is not None else None
+            g2 = through(l2, blk.o1, dgrad(l3, g3, blk.o2, mask=blk.o2))
+            g1 = through(l1, x_in, dgrad(l2, g2, blk.o1, mask=blk.o1))
             if bi == 0 and not ctx.needs_input_grad[0]:
                 g = None
                 break
-            other = data_grad(bi, 3, gzd, x_in) if down else g
-            g = data_grad(bi, 0, gz1, x_in, mask=x_in if bi else None, add=other)
+            other = dgrad(down, gd, x_in) if down is not None else g
+            g = dgrad(l1, g1, x_in, mask=x_in if bi else None, add=other)
         if g is not None and ctx.nchw:
             g = g.float().permute(0, 3, 1, 2).contiguous()
-        return (g, None, None, None, *grads)
-
-
-TRUNK_BATCHNORM_MODES = ('frozen', 'batch')
-
-
-# ---- the CNN trunks' stem (csrc/stem_train.hip, DESIGN.md 15) -----------------------------------------------------------------
-def _stem_gy(g_y, y0):
-    if g_y.dtype != torch.bfloat16:
-        raise TypeError("the stem's backward takes the stage Function's bf16 NHWC input gradient, got %s" % g_y.dtype)
-    return ops.maxpool3x3s2_bwd_nhwc(y0, g_y.contiguous(), relu_mask=True)
+        return (g, None, None, None, None, *[t for blk in rec.blocks for layer in blk.layers for t in layer.grads])
 
 
 class TrunkStemFunction(torch.autograd.Function):
-    """y [B, OH/2, OW/2, 64] bf16 NHWC = maxpool(y0), y0 = relu(bn1(conv1(img))) with frozen statistics: the eval stem, bit for bit
-    (ops.stem_conv7 on the folded pack `pack` = (wt, bias) of ops.conv_fold_bn(..., stem=True), then ops.maxpool3x3s2_nhwc).  Kept for
-    the backward: the fp32 image and y0.  keep: None or a list that receives {"img": the image as bf16 (what the convolution
-    multiplied), "y0", "y"}.  Backward, from g_y (bf16 NHWC, the stage Function's unmasked input gradient): g_y0 =
-    ops.maxpool3x3s2_bwd_nhwc(y0, g_y, relu_mask=True) -- the pool's first-maximum routing and the ReLU's mask in one rounding --,
-    (dW', db') = ops.stem_wgrad(img, g_y0), and ops.conv_bn_unfold gives the gradients of conv1.weight, bn1.weight and bn1.bias; each
-    gets one iff it requires one.  The image never gets a gradient (None): no kernel here differentiates the stem with respect to
-    its input."""
+    """y [B, OH/2, OW/2, 64] bf16 NHWC = maxpool(y0), y0 = relu(bn1(conv1(img))), the stem of a trunk.
+    mode 'frozen': the eval stem, bit for bit (ops.stem_conv7 on the folded pack `pack` = (wt, bias) of trunk.layer_pack(..., stem=True),
+    then ops.maxpool3x3s2_nhwc).  keep: None or a list that receives {"img": the image as bf16 (what the convolution multiplied),
+    "y0", "y"}.
+    mode 'batch': z0 = conv1(bf16(img); bf16(conv1.weight)) without bias or ReLU (ops.stem_conv7(raw=True) on the raw pack) and
+    y0 = _batch_norm(z0), which moves bn1's running buffers.  keep receives "z0" and "stats": (mean, rstd) as well.
+    Backward, from g_y (bf16 NHWC, the stage Function's unmasked input gradient): g_y0 = ops.maxpool3x3s2_bwd_nhwc(y0, g_y,
+    relu_mask=True) -- the pool's first-maximum routing and the ReLU's mask in one rounding --, then _layer_backward over
+    ops.stem_wgrad(img, .) gives the gradients of conv1.weight, bn1.weight and bn1.bias; each gets one iff it requires one.  The image
+    never gets a gradient (None): no kernel here differentiates the stem with respect to its input."""
 
     @staticmethod
-    def forward(ctx, img, bn, pack, keep, conv_w, gamma, beta):
+    def forward(ctx, img, bn, pack, keep, mode, conv_w, gamma, beta):
         imgc = img.detach().contiguous()
-        y0 = ops.stem_conv7(imgc, *pack)
+        if mode == 'frozen':
+            y0, kept = ops.stem_conv7(imgc, *pack), {}
+            layer = SimpleNamespace(w=conv_w, gamma=gamma, mean=bn.running_mean, var=bn.running_var, eps=bn.eps)
+        else:
+            z0 = ops.stem_conv7(imgc, *pack, raw=True)
+            y0, mean, rstd = _batch_norm(z0, bn, gamma, beta)
+            kept = {"z0": z0, "stats": (mean, rstd)}
+            layer = SimpleNamespace(k=7, gamma=gamma, z=z0, mean=mean, rstd=rstd)
         y = ops.maxpool3x3s2_nhwc(y0)
         if keep is not None:
-            keep.append({"img": imgc.to(torch.bfloat16), "y0": y0, "y": y})
-        ctx.eps = bn.eps
-        ctx.save_for_backward(imgc, y0, bn.running_mean, bn.running_var, conv_w, gamma)
+            keep.append({"img": imgc.to(torch.bfloat16), "y0": y0, "y": y, **kept})
+        ctx.mode = mode
+        save_record(ctx, SimpleNamespace(img=imgc, y0=y0, layer=layer))
         return y
 
     @staticmethod
     def backward(ctx, g_y):
-        img, y0, mean, var, conv_w, gamma = ctx.saved_tensors
-        want = tuple(ctx.needs_input_grad[4:7])
+        want = tuple(ctx.needs_input_grad[5:8])
         if not any(want):
-            return (None,) * 7
-        dwp, dbp = ops.stem_wgrad(img, _stem_gy(g_y, y0))
-        return (None, None, None, None, *ops.conv_bn_unfold(dwp, dbp, conv_w, (gamma, mean, var, ctx.eps), want=want))
-
-
-class TrunkStemBatchNormFunction(torch.autograd.Function):
-    """TrunkStemFunction with batch statistics: z0 = conv1(bf16(img); bf16(conv1.weight)) without bias or ReLU (ops.stem_conv7(raw=True)
-    on `pack` = ops.conv_fold_bn(w, None, None, stem=True)), (mean, rstd) of z0 over the batch (ops.bn_stats_bf16_nhwc, which moves
-    bn1.running_mean / running_var; num_batches_tracked goes up by one), y0 = relu(gamma (z0 - mean) rstd + beta)
-    (ops.bn_apply_bf16_nhwc), y = maxpool(y0).  Kept: the image, z0, y0, (mean, rstd); keep receives {"img" (bf16), "z0", "y0", "y",
-    "stats": (mean, rstd)}.  Backward: g_y0 as in TrunkStemFunction, (g_z0, dgamma, dbeta) = ops.bn_backward_bf16_nhwc(g_y0, z0, ...)
-    through the statistics, dW = ops.stem_wgrad(img, g_z0)[0] re-laid out as conv1.weight (the bf16 rounding of the weight is
-    straight-through).  A parameter gets a gradient iff it requires one; the image never does."""
-
-    @staticmethod
-    def forward(ctx, img, bn, pack, keep, conv_w, gamma, beta):
-        imgc = img.detach().contiguous()
-        z0 = ops.stem_conv7(imgc, *pack, raw=True)
-        running = (bn.running_mean, bn.running_var) if bn.track_running_stats and bn.running_mean is not None else None
-        mean, rstd = ops.bn_stats_bf16_nhwc(z0, bn.eps, running=running, momentum=bn.momentum)
-        if running is not None and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-        y0 = ops.bn_apply_bf16_nhwc(z0, mean, rstd, gamma.detach(), beta.detach())
-        y = ops.maxpool3x3s2_nhwc(y0)
-        if keep is not None:
-            keep.append({"img": imgc.to(torch.bfloat16), "z0": z0, "y0": y0, "y": y, "stats": (mean, rstd)})
-        ctx.save_for_backward(imgc, z0, y0, mean, rstd, gamma)
-        return y
-
-    @staticmethod
-    def backward(ctx, g_y):
-        img, z0, y0, mean, rstd, gamma = ctx.saved_tensors
-        want = tuple(ctx.needs_input_grad[4:7])
-        if not any(want):
-            return (None,) * 7
-        gz, dgamma, dbeta = ops.bn_backward_bf16_nhwc(_stem_gy(g_y, y0), z0, mean, rstd, gamma, want=want[1:])
-        dw = None
-        if want[0]:
-            dw = ops.stem_wgrad(img, gz)[0].view(64, 7, 7, 3).permute(0, 3, 1, 2).contiguous()
-        return (None, None, None, None, dw, dgamma, dbeta)
-
-
-def stem_pack_raw(conv):
-    """(bf16(conv1.weight) in the stem's [64, 160] layout, a zero bias): the pack of batch-statistics fine-tuning, kept on the module
-    and rebuilt when the weight changes."""
-    from .derived import derived
-    store = conv.__dict__.setdefault("_train_packs_raw", {})
-    return derived(store, "stem", (conv.weight,), lambda: ops.conv_fold_bn(conv.weight.detach().contiguous(), None, None, stem=True))
+            return (None,) * 8
+        rec = saved_record(ctx)
+        if g_y.dtype != torch.bfloat16:
+            raise TypeError("the stem's backward takes the stage Function's bf16 NHWC input gradient, got %s" % g_y.dtype)
+        rec.layer.want = want
+        _layer_backward(ctx.mode, rec.layer, ops.maxpool3x3s2_bwd_nhwc(rec.y0, g_y.contiguous(), relu_mask=True),
+                        lambda gz: ops.stem_wgrad(rec.img, gz))
+        return (None, None, None, None, None, *rec.layer.grads)
 
 
 def trunk_stem_forward(conv, bn, img, pack=None, keep=None, batchnorm='frozen'):
     """The stem of a trunk -- conv (7x7 / 2 / 3, 3 -> 64, no bias), bn, ReLU, MaxPool2d(3, 2, 1) -- over img [B,3,H,W] fp32 with
     autograd: -> [B, h, w, 64] bf16 NHWC, which requires a gradient iff one of conv.weight, bn.weight, bn.bias does.  pack: the folded
-    stem pack if the caller has it (frozen mode), else it is built here."""
+    stem pack if the caller has it (frozen mode), else the conv module's own (trunk.layer_pack)."""
     if batchnorm not in TRUNK_BATCHNORM_MODES:
         raise ValueError("batchnorm must be one of %s, got %r" % (TRUNK_BATCHNORM_MODES, batchnorm))
     if not img.is_cuda:
         raise RuntimeError("img is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % img.device)
     if conv.bias is not None:
         raise NotImplementedError("trunk fine-tuning: convolutions with a bias are not supported (torchvision's have none)")
-    if batchnorm == 'batch':
-        return TrunkStemBatchNormFunction.apply(img, bn, stem_pack_raw(conv), keep, conv.weight, bn.weight, bn.bias)
-    if pack is None:
-        from .trunk import ResNetFeatures
-        pack = ResNetFeatures._fold(conv, bn, stem=True)
-    return TrunkStemFunction.apply(img, bn, pack, keep, conv.weight, bn.weight, bn.bias)
-
-
-def _block_layers(blk):
-    from .trunk import block_layers
-    return block_layers(blk)
+    if pack is None or batchnorm == 'batch':
+        pack = trunk.layer_pack(conv, bn, _PACK_KIND[batchnorm], stem=True)
+    return TrunkStemFunction.apply(img, bn, pack[:2], keep, batchnorm, conv.weight, bn.weight, bn.bias)
 
 
 def trunk_stage_forward(stages, x, keep=None, batchnorm='frozen'):
     """The feature map of `stages` -- an nn.Sequential of trunk.Bottleneck, or a list of such stages run one after the other -- over
-    x (NHWC bf16 or NCHW fp32) with autograd.  batchnorm='frozen' (TrunkStageFunction): BatchNorm uses and keeps its running
-    statistics.  batchnorm='batch' (TrunkStageBatchNormFunction): BatchNorm normalises with the statistics of the batch, moves its
-    running buffers and is differentiated through the statistics, whatever the blocks' .training flags say."""
-    from .trunk import Bottleneck, block_packs, block_packs_raw
+    x (NHWC bf16 or NCHW fp32) with autograd (TrunkStageFunction).  batchnorm='frozen': BatchNorm uses and keeps its running
+    statistics.  batchnorm='batch': BatchNorm normalises with the statistics of the batch, moves its running buffers and is
+    differentiated through the statistics, whatever the blocks' .training flags say."""
     if batchnorm not in TRUNK_BATCHNORM_MODES:
         raise ValueError("batchnorm must be one of %s, got %r" % (TRUNK_BATCHNORM_MODES, batchnorm))
     if not x.is_cuda:
         raise RuntimeError("x is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % x.device)
-    if isinstance(stages, torch.nn.Sequential) and all(isinstance(b, Bottleneck) or hasattr(b, "conv3") for b in stages):
+    if isinstance(stages, torch.nn.Sequential) and all(isinstance(b, trunk.Bottleneck) or hasattr(b, "conv3") for b in stages):
         stages = [stages]
     blocks = [b for st in stages for b in st]
     if not blocks:
         raise ValueError("trunk_stage_forward: no bottleneck blocks")
-    params = [t for b in blocks for conv, bn in _block_layers(b) for t in (conv.weight, bn.weight, bn.bias)]
-    if batchnorm == 'batch':
-        return TrunkStageBatchNormFunction.apply(x, blocks, [block_packs_raw(b) for b in blocks], keep, *params)
-    return TrunkStageFunction.apply(x, blocks, [block_packs(b) for b in blocks], keep, *params)
+    params = [t for b in blocks for conv, bn in trunk.block_layers(b) for t in (conv.weight, bn.weight, bn.bias)]
+    packs = [trunk.block_packs_raw(b) if batchnorm == 'batch' else trunk.block_packs(b) for b in blocks]
+    return TrunkStageFunction.apply(x, blocks, packs, keep, batchnorm, *params)

@@ -9,17 +9,21 @@ on the 3x3 convolution) with torchvision's parameter names, which is what makes 
 
   ResNet / Bottleneck   parameter containers with torchvision's state_dict surface (conv1, bn1, layer{1..4}.{i}.conv{1..3},
                         bn{1..3}, downsample.{0,1}, fc).  Their own forward() raises: there is no PyTorch compute path.
-  block_packs           the folded weights of one Bottleneck plus the transposed packs its backward reads (derived packs,
-                        rebuilt when a parameter or a running statistic changes): what frozen-statistics fine-tuning runs on
-                        (ResNetFeatures.forward_train, train.TrunkStageFunction).
-  block_packs_raw       the same for batch-statistics fine-tuning: bf16(conv.weight) with nothing folded in, BatchNorm being an
-                        operator of its own there (train.TrunkStageBatchNormFunction, csrc/bn_train.hip).
+  layer_pack            the bf16 weight and fp32 bias of one (conv, bn) pair, the stem's included: 'folded' with the running
+                        statistics folded in (the eval forward and frozen-statistics fine-tuning read the same tensor) or 'raw'
+                        (batch-statistics fine-tuning, BatchNorm being an operator of its own there: csrc/bn_train.hip,
+                        DESIGN.md 14).  One derived pack per layer, kept on the conv module, rebuilt when a tensor it derives
+                        from changes and parked while a captured graph may hold its address.
+  block_packs(_raw)     the layer packs of one Bottleneck plus the transposed packs its backward reads: what fine-tuning runs
+                        on (ResNetFeatures.forward_train, train.TrunkStageFunction).
+  run_block             the forward of one bottleneck, written once: the eval forward and both fine-tuning modes walk it with
+                        their own per-layer step.
   (the stem)            with all four stages trainable the stem trains too: ResNetFeatures.forward_train(img, 4, stem=True),
-                        train.TrunkStemFunction / TrunkStemBatchNormFunction, csrc/stem_train.hip, DESIGN.md 15.
+                        train.TrunkStemFunction, csrc/stem_train.hip, DESIGN.md 15.
   ResNetFeatures        the reference's 8-entry nn.Sequential (same child indices -> same `object_features.4.0.conv1.weight`
-                        keys), whose forward runs the HIP trunk: BatchNorm folded into bf16 weights once per parameter
-                        version, NHWC bf16 activations, every convolution an implicit GEMM on the bf16 MFMA, the last
-                        one writing the [B, 2048, h, w] fp32 NCHW map the fusion path consumes.
+                        keys), whose forward runs the HIP trunk: BatchNorm folded into bf16 weights once per version of a
+                        layer's parameters, NHWC bf16 activations, every convolution an implicit GEMM on the bf16 MFMA, the
+                        last one writing the [B, 2048, h, w] fp32 NCHW map the fusion path consumes.
 
 Any module with the same attribute structure (e.g. a torchvision ResNet on a machine that has torchvision) can be
 wrapped: ResNetFeatures reads the geometry (stride / padding) from the nn.Conv2d children it is given.
@@ -114,43 +118,63 @@ def block_layers(blk):
     return layers
 
 
-def block_packs(blk):
-    """[(wt, bias, wT, k, stride, pad)] per block_layers(blk): the eval forward's folded bf16 weight and fp32 bias
-    (ops.conv_fold_bn) and the data gradient's transposed pack (ops.conv_transpose_pack), kept on the block and rebuilt when
-    one of the five tensors they derive from changes."""
-    store = blk.__dict__.setdefault("_train_packs", {})
+def layer_pack(conv, bn, kind='folded', stem=False, name="bottleneck"):
+    """(wt, bias, k, stride, pad) of one convolution and its BatchNorm: the bf16 weight and fp32 bias every kernel reads.
+    kind='folded': ops.conv_fold_bn with bn's running statistics folded in (the eval forward and frozen-statistics fine-tuning share
+    this one tensor).  kind='raw': bf16(conv.weight) with nothing folded in and a zero bias (batch-statistics fine-tuning, where
+    BatchNorm is an operator of its own).  stem=True: the 7x7 stem's [64, 160] layout.  A derived pack, kept in a store on the
+    conv module and rebuilt when one of the tensors it derives from changes; the superseded one is parked while a capture lives."""
+    k, s, p = (7, 2, 3) if stem else _conv_geometry(conv, name)
+    if kind == 'folded':
+        sources, extra = (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), (bn.eps,)
+        build = lambda: ResNetFeatures._fold(conv, bn, stem=stem)
+    else:
+        sources, extra = (conv.weight,), ()
+        build = lambda: ops.conv_fold_bn(conv.weight.detach().contiguous(), None, None, stem=stem)
+    store = conv.__dict__.setdefault("_packs", {})
+    wt, bias = derived(store, "stem." + kind if stem else kind, sources, build, extra=extra, park=ops.retire)
+    return wt, bias, k, s, p
+
+
+def _train_packs(blk, kind):
     out = []
-    for slot, (conv, bn) in enumerate(block_layers(blk)):
-        k, s, p = _conv_geometry(conv, "bottleneck")
+    for conv, bn in block_layers(blk):
         if conv.bias is not None:
             raise NotImplementedError("trunk fine-tuning: convolutions with a bias are not supported (torchvision's have none)")
-
-        def build(conv=conv, bn=bn, k=k):
-            wt, bias = ResNetFeatures._fold(conv, bn)
-            return wt, bias, ops.conv_transpose_pack(wt, k)
-        wt, bias, wT = derived(store, slot, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), build,
-                               extra=(bn.eps,))
+        wt, bias, k, s, p = layer_pack(conv, bn, kind)
+        # the data gradient's transposed pack derives from wt alone, in a slot of its own: only a backward asks for it
+        wT = derived(conv._packs, kind + ".T", (wt,), lambda: ops.conv_transpose_pack(wt, k), park=ops.retire)
         out.append((wt, bias, wT, k, s, p))
     return out
+
+
+def block_packs(blk):
+    """[(wt, bias, wT, k, stride, pad)] per block_layers(blk) for frozen-statistics fine-tuning: the folded layer_pack of each layer
+    and its transposed pack (ops.conv_transpose_pack), which the data gradient reads."""
+    return _train_packs(blk, 'folded')
 
 
 def block_packs_raw(blk):
-    """[(wt, zero bias, wT, k, stride, pad)] per block_layers(blk) for batch-statistics fine-tuning (train.TrunkStageBatchNormFunction,
-    DESIGN.md 14): wt = bf16(conv.weight) without a BatchNorm folded in, a zero fp32 bias, and wt's transposed pack; kept on the
-    block and rebuilt when conv.weight changes."""
-    store = blk.__dict__.setdefault("_train_packs_raw", {})
-    out = []
-    for slot, (conv, _) in enumerate(block_layers(blk)):
-        k, s, p = _conv_geometry(conv, "bottleneck")
-        if conv.bias is not None:
-            raise NotImplementedError("trunk fine-tuning: convolutions with a bias are not supported (torchvision's have none)")
+    """[(wt, zero bias, wT, k, stride, pad)] per block_layers(blk) for batch-statistics fine-tuning: the raw
+    layer_pack of each layer and its transposed pack."""
+    return _train_packs(blk, 'raw')
 
-        def build(conv=conv, k=k):
-            wt, bias = ops.conv_fold_bn(conv.weight.detach().contiguous(), None, None)
-            return wt, bias, ops.conv_transpose_pack(wt, k)
-        wt, bias, wT = derived(store, slot, (conv.weight,), build)
-        out.append((wt, bias, wT, k, s, p))
-    return out
+
+def run_block(y, down, step, last=False):
+    """The forward of one bottleneck, for every mode: (relu(layer3(layer2(layer1(y))) + idn), idn) with idn = the downsample layer
+    of y if the block has one (`down`), else y.  step(j, x, relu=, residual=, out_nchw_f32=) runs layer j of block_layers on x and
+    returns its activation; whatever a backward needs, the step records.  last: the output is the fp32 NCHW map.  Nothing but the
+    running activation is held here: o1 is released before the third layer allocates its output."""
+    idn = step(3, y, relu=False) if down else y
+    o = step(0, y)
+    o = step(1, o)
+    return step(2, o, residual=idn, out_nchw_f32=last), idn
+
+
+def conv_step(packs):
+    """run_block's step that is one launch: layer j's convolution on packs[j] (layer_pack's or block_packs') with its bias,
+    residual and ReLU -- the whole layer on a folded pack."""
+    return lambda j, x, **kw: ops.conv_bf16_nhwc(x, packs[j][0], packs[j][1], *packs[j][-3:], **kw)
 
 
 class ResNetFeatures(nn.Sequential):
@@ -165,61 +189,42 @@ class ResNetFeatures(nn.Sequential):
             raise ValueError("trunk stem must be Conv2d(3, 64, 7, stride 2, padding 3), got %s" % (c,))
         if (_one(mp.kernel_size), _one(mp.stride), _one(mp.padding)) != (3, 2, 1) or getattr(mp, "ceil_mode", False):
             raise ValueError("trunk max-pool must be MaxPool2d(3, 2, 1), got %s" % (mp,))
-        self._plan = None
-        self._plan_key = None
-
-    # ---- one-off weight preparation, redone when a parameter or a running statistic changes ----
-    def _tensors(self):
-        return [t for t in list(self.parameters()) + list(self.buffers()) if t.is_floating_point()]
 
     @staticmethod
     def _fold(conv, bn, stem=False):
         return ops.conv_fold_bn(conv.weight.detach().contiguous(), None if conv.bias is None else conv.bias.detach(),
                                 (bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps), stem=stem)
 
-    def _prepare(self):
-        key = tuple((t.data_ptr(), t._version) for t in self._tensors())
-        if self._plan is not None and key == self._plan_key:
-            return self._plan
-        stem = self._fold(self[0], self[1], stem=True)
+    def _prepare(self, stop=8):
+        """(the stem's folded pack, [[layer_pack per block_layers(blk)] per block of the stages self[4:stop]]): the eval plan.
+        Every entry is the layer's own derived pack, so a changed parameter refolds its layer and nothing else."""
         blocks = []
-        for li in range(4, 8):
+        for li in range(4, stop):
             for bi, blk in enumerate(self[li]):
                 name = "%d.%d" % (li, bi)
-                convs = []
-                for conv, bn in ((blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3)):
-                    convs.append(self._fold(conv, bn) + _conv_geometry(conv, name))
-                down = None
-                if blk.downsample is not None:
-                    dconv, dbn = blk.downsample[0], blk.downsample[1]
-                    down = self._fold(dconv, dbn) + _conv_geometry(dconv, name + ".downsample")
-                blocks.append((convs, down))
-        self._plan, self._plan_key = (stem, blocks), key
-        return self._plan
+                blocks.append([layer_pack(conv, bn, name=name + ".downsample" if j == 3 else name)
+                               for j, (conv, bn) in enumerate(block_layers(blk))])
+        return layer_pack(self[0], self[1], stem=True), blocks
 
-    @staticmethod
-    def _run_block(y, convs, down, last=False):
-        idn = y
-        if down is not None:
-            w, b, k, s, p = down
-            idn = ops.conv_bf16_nhwc(y, w, b, k, s, p, relu=False)
-        w, b, k, s, p = convs[0]
-        o = ops.conv_bf16_nhwc(y, w, b, k, s, p)
-        w, b, k, s, p = convs[1]
-        o = ops.conv_bf16_nhwc(o, w, b, k, s, p)
-        w, b, k, s, p = convs[2]
-        return ops.conv_bf16_nhwc(o, w, b, k, s, p, residual=idn, out_nchw_f32=last)
+    def _eval(self, img, stop=8):
+        """The stem, the max-pool and the stages self[4:stop] on the folded packs -> bf16 NHWC, or after layer4 the fp32 NCHW map."""
+        stem, blocks = self._prepare(stop)
+        y = ops.stem_conv7(img.contiguous(), *stem[:2])
+        y = ops.maxpool3x3s2_nhwc(y)
+        for i, packs in enumerate(blocks):
+            y = run_block(y, len(packs) == 4, conv_step(packs), last=stop == 8 and i == len(blocks) - 1)[0]
+        return y
 
     def forward_train(self, img, stages=1, batchnorm='frozen', stem=False):
         """Fine-tuning forward: img [B,3,H,W] -> the [B,2048,h,w] fp32 map under autograd, with gradients for the parameters of
         the last `stages` bottleneck stages that require one.  The stem, the max-pool and the stages below run as in forward(),
         without a graph and with their running statistics, so the module itself must be in eval mode (model.unfreeze_trunks()
-        puts it there).  batchnorm='frozen' (train.TrunkStageFunction): the trainable stages keep their running statistics too.
-        batchnorm='batch' (train.TrunkStageBatchNormFunction): their BatchNorm layers normalise with the statistics of the batch,
-        move running_mean / running_var / num_batches_tracked and are differentiated through the statistics.
+        puts it there).  batchnorm='frozen': the trainable stages keep their running statistics too.  batchnorm='batch': their
+        BatchNorm layers normalise with the statistics of the batch, move running_mean / running_var / num_batches_tracked and
+        are differentiated through the statistics (train.TrunkStageFunction, either way).
         stem=True (needs stages=4): the stem trains too -- conv1.weight, bn1.weight and bn1.bias get gradients if they require one
-        (train.TrunkStemFunction), and in 'batch' mode bn1 uses and moves batch statistics like every other BatchNorm
-        (train.TrunkStemBatchNormFunction).  The image itself never gets a gradient."""
+        (train.TrunkStemFunction), and in 'batch' mode bn1 uses and moves batch statistics like every other BatchNorm.  The image
+        itself never gets a gradient."""
         from . import train as _train
         if batchnorm not in _train.TRUNK_BATCHNORM_MODES:
             raise ValueError("batchnorm must be one of %s, got %r" % (_train.TRUNK_BATCHNORM_MODES, batchnorm))
@@ -234,20 +239,12 @@ class ResNetFeatures(nn.Sequential):
             raise ValueError("trunk input must be [B, 3, H, W], got %s" % (tuple(img.shape),))
         if not img.is_cuda:
             raise RuntimeError("img is on %s: mgnns_amd operators run on the GPU only (no CPU path)" % img.device)
-        if stem:
-            pack = None
-            if batchnorm == 'frozen':
-                with torch.no_grad():
-                    pack = self._prepare()[0]
-            y = _train.trunk_stem_forward(self[0], self[1], img, pack=pack, batchnorm=batchnorm)
-            return _train.trunk_stage_forward([self[li] for li in range(4, 8)], y, batchnorm=batchnorm)
         first = 8 - int(stages)
-        with torch.no_grad():
-            stem, blocks = self._prepare()
-            y = ops.stem_conv7(img.detach().contiguous(), *stem)
-            y = ops.maxpool3x3s2_nhwc(y)
-            for convs, down in blocks[:sum(len(self[li]) for li in range(4, first))]:
-                y = self._run_block(y, convs, down)
+        if stem:
+            y = _train.trunk_stem_forward(self[0], self[1], img, batchnorm=batchnorm)
+        else:
+            with torch.no_grad():
+                y = self._eval(img.detach(), first)
         return _train.trunk_stage_forward([self[li] for li in range(first, 8)], y, batchnorm=batchnorm)
 
     def forward(self, img):
@@ -255,12 +252,7 @@ class ResNetFeatures(nn.Sequential):
             raise RuntimeError("ResNetFeatures: eval-mode forward only on the HIP path (BatchNorm uses running statistics); call .eval()")
         if img.dim() != 4 or img.shape[1] != 3:
             raise ValueError("trunk input must be [B, 3, H, W], got %s" % (tuple(img.shape),))
-        stem, blocks = self._prepare()
-        y = ops.stem_conv7(img.contiguous(), *stem)
-        y = ops.maxpool3x3s2_nhwc(y)
-        for i, (convs, down) in enumerate(blocks):
-            y = self._run_block(y, convs, down, last=i == len(blocks) - 1)
-        return y
+        return self._eval(img)
 
 
 def features_flops(feats, size):

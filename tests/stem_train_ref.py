@@ -6,7 +6,7 @@ convolution's input is the kept bf16 image, and in batch mode the BatchNorm sees
 Two forms: R1 carries the gradients between layers in fp64; R2 (round=True) rounds them to bf16 where the kernels round: g_y0 after
 the pool's backward and the mask, and g_z0 after the BatchNorm's backward.  Sums (dW, dgamma, dbeta) are never rounded.
 
-`saved` is what train.TrunkStemFunction / TrunkStemBatchNormFunction hand to keep=: {"img": [B,3,H,W] bf16, "y0", "y": NHWC bf16} and,
+`saved` is what train.TrunkStemFunction hands to keep=: {"img": [B,3,H,W] bf16, "y0", "y": NHWC bf16} and,
 in batch mode, {"z0": NHWC bf16, "stats": (mean, rstd)}."""
 import torch
 import torch.nn.functional as F

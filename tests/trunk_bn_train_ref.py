@@ -7,7 +7,7 @@ Two forms: R1 carries the gradients between layers in fp64; R2 (round=True) roun
 map gradient at the entry, every g_z a BatchNorm backward returns, and every data gradient after its add and mask (the downsample's
 data gradient on its own, before it is added).  Sums (dgamma, dbeta, dW) are never rounded.
 
-`saved` is what train.TrunkStageBatchNormFunction hands to keep=: {"x", "blocks": [{"z": [...], "stats": [(mean, rstd), ...],
+`saved` is what train.TrunkStageFunction hands to keep= in 'batch' mode: {"x", "blocks": [{"z": [...], "stats": [(mean, rstd), ...],
 "o1", "o2", "out", "idn"}]}, z and stats in block_layers order."""
 import torch
 import torch.nn.functional as F
