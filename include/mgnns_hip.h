@@ -722,7 +722,8 @@ int mgnns_transpose_cast_bf16(const float* x, int rows, int cols, int ld, void* 
  * cut the same way.  NULL: every tile is computed whole by the 256 x 128 kernel. */
 size_t mgnns_gemm_bf16_workspace_bytes(void);
 /* c_bf16 (round 6: two bits): bit 0 = C is bf16 (else fp32); bit 1 = TRANSPOSED store: C is C^T [N, ldc >= M] (a product with a small M runs as
- * its transpose and still leaves the K-contiguous operand the next product needs; the 160 x 256 kernel only: ceil(M / 160) >= 8, N >= 256, K >= 320). */
+ * its transpose and still leaves the K-contiguous operand the next product needs; the 160 x 256 kernel only: ceil(M / 160) >= 8, N >= 256, K >= 320).
+ * M == 0: nothing is launched, A and C may be NULL. */
 int mgnns_gemm_bf16_nt_fwd(const void* A, const void* Bt, int M, int N, int Kp, const float* bias, void* C, int ldc,
                            int c_bf16, int act, void* workspace, size_t workspace_bytes, mgnns_stream_t stream);
 /* Which tile shape mgnns_gemm_bf16_nt_fwd runs (tests and A/B timings; production leaves it alone; process-wide): 0 round 4's kernels
@@ -756,6 +757,8 @@ int mgnns_softmax_argmax_fwd(const float* logits, int B, int NL, float* probs, i
  *                            pad <= K/2, Cin a power of two >= 64, Cout % 8 == 0; residual [B,OH,OW,Cout] bf16 or NULL;
  *                            y [B,OH,OW,Cout] bf16, or -- out_nchw_f32 != 0 -- [B,Cout,OH,OW] fp32, the feature-map
  *                            layout mgnns_imgbank_pool_* read.
+ *  B == 0 (the three forward entries above and mgnns_stem_conv7_raw_fwd): nothing is launched, and the activations (img / x / y / z)
+ *  may be NULL -- an empty tensor has no address; the arguments are validated all the same.
  */
 int mgnns_conv_fold_bn_bf16(const float* w, const float* conv_bias, int Cout, int Cin, int KH, int KW,
                             const float* gamma, const float* beta, const float* mean, const float* var, float eps,

@@ -521,7 +521,7 @@ extern "C" int mgnns_conv_fold_bn_bf16(const float* w, const float* conv_bias, i
 
 extern "C" int mgnns_stem_conv7_fwd(const float* img, int B, int H, int W, const void* wt, const float* bias, void* y,
                                     mgnns_stream_t stream) {
-    MG_REQUIRE(img && wt && bias && y, "mgnns_stem_conv7_fwd: null pointer");
+    MG_REQUIRE(((img && y) || B == 0) && wt && bias, "mgnns_stem_conv7_fwd: null pointer");     // (an empty batch has no address)
     MG_REQUIRE(B >= 0 && H >= 7 && W >= 7 && B <= 65535, "mgnns_stem_conv7_fwd: bad dims B=%d H=%d W=%d", B, H, W);
     MG_REQUIRE(mg_aligned16(wt) && mg_aligned16(bias) && mg_aligned16(y), "mgnns_stem_conv7_fwd: operands must be 16-byte aligned");
     if (B == 0) return 0;
@@ -534,7 +534,7 @@ extern "C" int mgnns_stem_conv7_fwd(const float* img, int B, int H, int W, const
 }
 
 extern "C" int mgnns_stem_conv7_raw_fwd(const float* img, int B, int H, int W, const void* wt, void* z, mgnns_stream_t stream) {
-    MG_REQUIRE(img && wt && z, "mgnns_stem_conv7_raw_fwd: null pointer");
+    MG_REQUIRE(((img && z) || B == 0) && wt, "mgnns_stem_conv7_raw_fwd: null pointer");
     MG_REQUIRE(B >= 0 && H >= 7 && W >= 7 && B <= 65535, "mgnns_stem_conv7_raw_fwd: bad dims B=%d H=%d W=%d", B, H, W);
     MG_REQUIRE(mg_aligned16(wt) && mg_aligned16(z), "mgnns_stem_conv7_raw_fwd: operands must be 16-byte aligned");
     if (B == 0) return 0;
@@ -547,7 +547,7 @@ extern "C" int mgnns_stem_conv7_raw_fwd(const float* img, int B, int H, int W, c
 }
 
 extern "C" int mgnns_maxpool3x3s2_nhwc_fwd(const void* x, int B, int H, int W, int C, void* y, mgnns_stream_t stream) {
-    MG_REQUIRE(x && y, "mgnns_maxpool3x3s2_nhwc_fwd: null pointer");
+    MG_REQUIRE((x && y) || B == 0, "mgnns_maxpool3x3s2_nhwc_fwd: null pointer");
     MG_REQUIRE(B >= 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "mgnns_maxpool3x3s2_nhwc_fwd: need C %% 8 == 0 (B=%d H=%d W=%d C=%d)", B, H, W, C);
     MG_REQUIRE(mg_aligned16(x) && mg_aligned16(y), "mgnns_maxpool3x3s2_nhwc_fwd: operands must be 16-byte aligned");
     if (B == 0) return 0;
@@ -564,7 +564,7 @@ extern "C" int mgnns_maxpool3x3s2_nhwc_fwd(const void* x, int B, int H, int W, i
 extern "C" int mgnns_conv_bf16_nhwc_fwd(const void* x, int B, int H, int W, int Cin, const void* wt, const float* bias, int Cout,
                                         int KH, int KW, int stride, int pad, const void* residual, int relu, int out_nchw_f32,
                                         void* y, mgnns_stream_t stream) {
-    MG_REQUIRE(x && wt && bias && y, "mgnns_conv_bf16_nhwc_fwd: null pointer");
+    MG_REQUIRE(((x && y) || B == 0) && wt && bias, "mgnns_conv_bf16_nhwc_fwd: null pointer");   // (an empty batch has no address)
     MG_REQUIRE(B >= 0 && H > 0 && W > 0, "mgnns_conv_bf16_nhwc_fwd: bad dims B=%d H=%d W=%d", B, H, W);
     MG_REQUIRE(Cin >= 64 && (Cin & (Cin - 1)) == 0, "mgnns_conv_bf16_nhwc_fwd: C_in must be a power of two >= 64 (got %d)", Cin);
     MG_REQUIRE(Cout > 0 && Cout % 8 == 0, "mgnns_conv_bf16_nhwc_fwd: C_out %% 8 != 0 (got %d)", Cout);

@@ -1063,7 +1063,7 @@ extern "C" int mgnns_gemm_bf16_pick_form(int M, int N, int Kp, int with_workspac
 // is read on the device and M is only its upper bound
 int mg_launch_gemm_bf16(const void* A, const void* Bt, int M, int N, int Kp, const float* bias, float* C, int ldc, int act,
                         const int32_t* m_dev, hipStream_t stream, int c_bf16, void* workspace, size_t workspace_bytes) {
-    MG_REQUIRE(A && Bt && C, "mgnns_gemm_bf16_nt_fwd: null pointer");
+    MG_REQUIRE(((A && C) || M == 0) && Bt, "mgnns_gemm_bf16_nt_fwd: null pointer");     // (a product without rows has no address)
     const bool c_tr = (c_bf16 & 2) != 0;                           // C^T [N, ldc >= M] instead of C [M, ldc >= N]
     MG_REQUIRE(M >= 0 && N > 0 && N % 4 == 0 && Kp > 0 && Kp % BK == 0 && ldc >= (c_tr ? M : N) && (c_tr || ldc % 4 == 0),
                "mgnns_gemm_bf16_nt_fwd: need N %% 4 == 0, Kp %% %d == 0, ldc %% 4 == 0 (M=%d N=%d Kp=%d ldc=%d)", BK, M, N, Kp, ldc);

@@ -1588,18 +1588,30 @@ def test_imgbank_pool_split_vs_fp64(B, P, N):
         assert none is None and torch.equal(sp4, sp) and torch.equal(p4, pooled)
 
 
-@pytest.mark.parametrize("M,N,K", [(10000, 1024, 320), (5000, 512, 704), (2600, 128, 192), (512, 10000, 256), (300, 260, 64)])
+K_SPLIT_SHAPES = [(2048, 5120, 2048), (1800, 4100, 4096), (1024, 8320, 4096), (1792, 4300, 4096)]
+
+
+@pytest.mark.parametrize("M,N,K", [(10000, 1024, 320), (5000, 512, 704), (2600, 128, 192), (512, 10000, 256), (300, 260, 64)] + K_SPLIT_SHAPES)
 def test_gemm_bf16_nt_last_round_k_split_equals_whole_tiles(M, N, K):
-    """Dense bf16 GEMM with the workspace (a last, at most quarter-full round of tiles cut along K over the idle workgroups, partial
-    sums added in part order by the fix-up launch) against the same GEMM without it: shapes whose XCDs end on a partial round
-    (10 000 x 1024: 40 tiles on 32 workgroups per XCD), ragged row blocks, the column-split map (512 rows), bias + activation +
-    bf16 output through the fix-up path; fp32 partial sums in another order only (<= 1e-6 of the output scale), repeatable bits."""
+    """The 256 x 128 kernel (form 0: the two older kernels only) with the workspace against the same kernel without it, bias + activation,
+    fp32 and bf16 output, repeatable bits.  K_SPLIT_SHAPES end on a last round that is at most a quarter full and have K >= 2048, so with
+    the workspace that round is cut along K over the idle workgroups and the fix-up launch adds the partial sums in part order (the row
+    map with 4 and 8 parts, the column-split map, an XCD that splits without a full round before it, one with whole tiles only and an
+    empty one -- asserted through the launcher's restatement on 256 CUs): fp32 partial sums in another order only (<= 1e-6 of the output
+    scale).  The first five shapes do NOT split -- K <= 704 leaves a part fewer than eight slices, and two of them are below the 2^20
+    outputs at which the wrapper passes the workspace: there the workspace must change nothing within the same bound.
+    tests/test_matrix_pipe_edges_gpu.py compares the split with fp64."""
+    from tests import matrix_pipe_cases as MP
+    if (M, N, K) in K_SPLIT_SHAPES and torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        plan = MP.gemm_plan(M, N, K, MP.ops_gives_workspace(M, N), form=0)
+        assert plan["kernel"] == MP.K128 and plan["fixup"] and any(f > 0 for _, _, _, f in plan["xcds"]), plan
     rs = np.random.RandomState(M + N + K)
     a = ops.cast_pad_bf16(dev(rs.standard_normal((M, K)).astype(np.float32) * 0.1), ld=K)
     bt = ops.cast_pad_bf16(dev(rs.standard_normal((N, K)).astype(np.float32) * 0.1), ld=K)
     bias = dev(rs.standard_normal(N).astype(np.float32))
     old = ops.GEMM_BF16_KSPLIT
     try:
+        ops.gemm_bf16_set_form(0)
         for dt in (torch.float32, torch.bfloat16):
             ops.GEMM_BF16_KSPLIT = False
             ref = ops.gemm_bf16_nt(a, bt, bias, ops.ACT_LRELU2, out_dtype=dt)
@@ -1612,6 +1624,7 @@ def test_gemm_bf16_nt_last_round_k_split_equals_whole_tiles(M, N, K):
             assert float((got.float() - ref.float()).abs().max()) <= tol * scale, (dt, M, N, K)
     finally:
         ops.GEMM_BF16_KSPLIT = old
+        ops.gemm_bf16_set_form(-1)
 
 
 @pytest.mark.parametrize("form", [1, 3])
@@ -1684,11 +1697,17 @@ def test_gemm_bf16_nt_transposed_store(M, N, K):
 def test_gemm_bf16_nt_256_tiles(M, N, K):
     """Products with at least a full round of 256 x 256 tiles on every XCD and K >= 4096 run
     csrc/gemm_bf16.hip::gemm_bf16_nt_256_kernel (whole tiles round robin, the left-over tiles of an XCD cut along K and finished by
-    the fix-up launch) when the workspace is there: 32 / 40 / 45 tiles per XCD = no remainder / 8 left-over tiles in 4 parts / 13
-    in 2 parts; against the 256 x 128 kernel without workspace (fp32 sums in another order only), against fp64 on sampled entries,
-    ragged M / N / K, bias + activation + bf16 output, repeatable bits."""
+    the fix-up launch) when the workspace is there and the launcher is held to the two older kernels (form 0; by its default estimate
+    the 320 x 256 kernel takes the last two shapes): 32 / 40 / 45 tiles per XCD = no remainder / 8 left-over tiles in 4 parts / 13
+    in 2 parts -- asserted through the launcher's restatement on 256 CUs; against the 256 x 128 kernel without workspace (fp32 sums in
+    another order only), against fp64 on sampled entries, ragged M / N / K, bias + activation + bf16 output, repeatable bits."""
+    from tests import matrix_pipe_cases as MP
     rs = np.random.RandomState(M + N + K)
     kp = (K + 63) // 64 * 64
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        plan = MP.gemm_plan(M, N, kp, True, form=0)
+        assert plan["kernel"] == MP.K256 and MP.gemm_plan(M, N, kp, False, form=0)["kernel"] == MP.K128, plan
+        assert (M, N, K) == (8192, 2048, 4096) or any(f >= 2 for _, _, _, f in plan["xcds"]), plan
     a32 = rs.standard_normal((M, K)).astype(np.float32) * 0.1
     b32 = rs.standard_normal((N, K)).astype(np.float32) * 0.1
     a = ops.cast_pad_bf16(dev(a32), ld=kp)
@@ -1696,6 +1715,7 @@ def test_gemm_bf16_nt_256_tiles(M, N, K):
     bias = dev(rs.standard_normal(N).astype(np.float32))
     old = ops.GEMM_BF16_KSPLIT
     try:
+        ops.gemm_bf16_set_form(0)
         for dt in (torch.float32, torch.bfloat16):
             ops.GEMM_BF16_KSPLIT = False
             ref = ops.gemm_bf16_nt(a, bt, bias, ops.ACT_LRELU2, out_dtype=dt)
@@ -1713,6 +1733,7 @@ def test_gemm_bf16_nt_256_tiles(M, N, K):
         assert float((got - ref64).abs().max()) <= 1e-5 * max(1.0, float(ref64.abs().max()))
     finally:
         ops.GEMM_BF16_KSPLIT = old
+        ops.gemm_bf16_set_form(-1)
 
 
 def test_xcd_probe_confirms_the_block_index_placement():
