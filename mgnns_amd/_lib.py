@@ -1,4 +1,4 @@
-"""ctypes binding of libmgnns_hip.so, derived from include/mgnns_hip.h.
+"""ctypes binding of libmgnns_hip.so, derived from include/mgnns_hip.h and its extension headers.
 
 The header is the one place an entry point's signature is written down: the compiler checks every definition against it (each
 .hip includes it), and this module parses it at import into the argtypes, restypes and integer constants of the binding.
@@ -13,6 +13,9 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGNNS_LIB") or os.path.join(_HERE, "libmgnns_hip.so")   # MGNNS_LIB: an instrumented build (tools/)
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mgnns_hip.h")
+# Extension headers: entry points added without an ABI bump are declared beside mgnns_hip.h, which stays the surface of the ABI as it
+# stood.  They are parsed by the same rules into tables of their own (EXTENSION_SIGNATURES / EXTENSION_SIZE_GETTERS).
+EXTENSION_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_progressive.h"),)
 
 
 class MgnnsLibraryError(RuntimeError):
@@ -81,13 +84,36 @@ _UNCHECKED = ("mgnns_last_error", "mgnns_abi_version", "mgnns_source_fingerprint
 SIGNATURES = {n: a for n, (r, a) in _DECLS.items() if r is ctypes.c_int and n not in _UNCHECKED}
 SIZE_GETTERS = {n: a for n, (r, a) in _DECLS.items() if r is ctypes.c_size_t}
 
+
+def _read_extensions(paths, base):
+    """{name: (restype, [argtypes])} of the extension headers; a name mgnns_hip.h or another extension declares is an error."""
+    out = {}
+    for path in paths:
+        try:
+            with open(path) as f:
+                decls, _ = parse_header(f.read(), path)
+        except OSError as e:
+            raise MgnnsLibraryError("cannot read the C header %s (%s): the binding is derived from it" % (path, e))
+        if not decls:
+            raise MgnnsLibraryError("%s declares no mgnns_* entry point" % path)
+        for n in decls:
+            if n in base or n in out:
+                raise MgnnsLibraryError("%s declares %s a second time" % (path, n))
+        out.update(decls)
+    return out
+
+
+_EXT_DECLS = _read_extensions(EXTENSION_HEADERS, _DECLS)
+EXTENSION_SIGNATURES = {n: a for n, (r, a) in _EXT_DECLS.items() if r is ctypes.c_int}
+EXTENSION_SIZE_GETTERS = {n: a for n, (r, a) in _EXT_DECLS.items() if r is ctypes.c_size_t}
+
 _lib = None
 _bound = {}          # name -> bound function: call() does no getattr on the CDLL per launch
 
 
 def _bind(L, name):
     fn = getattr(L, name)          # AttributeError if the symbol is missing
-    fn.restype, fn.argtypes = _DECLS[name]
+    fn.restype, fn.argtypes = _DECLS[name] if name in _DECLS else _EXT_DECLS[name]
 
 
 def lib():
@@ -104,7 +130,7 @@ def lib():
         _bind(L, name)
     if L.mgnns_abi_version() != ABI_VERSION:
         raise MgnnsLibraryError("libmgnns_hip.so ABI %d != binding ABI %d; rebuild" % (L.mgnns_abi_version(), ABI_VERSION))
-    for name in _DECLS:
+    for name in list(_DECLS) + list(_EXT_DECLS):
         _bind(L, name)
     _lib = L
     _register_status_word(L)

@@ -11,14 +11,23 @@
 // The decoder body and the sample arithmetic live in jpeg_entropy.hpp / jpeg_pixels.hpp as host + device functions: the CPU run of
 // tools/dev/jpeg_host_check.cpp under the sanitizers executes the same code.  Every record is re-checked on the device (a record
 // buffer can change under a captured graph): a bad one gives status MG_JPEG_SEG_BAD_RECORD and writes nothing.
+//
+// Progressive files (SOF2; mgnns_jpeg_decode_progressive_fwd, DESIGN.md 17, "Progressive files") share the workspace, the pixel layout and stages 2
+// and 3.  Their entropy stage is jpeg_progressive_kernel (jpeg_progressive.hpp), one lane per segment of one SCAN, launched once
+// per LEVEL of the batch: scans of one level touch different (component, coefficient) pairs, so their lanes write different int16
+// elements of a block and need neither atomics nor a fence; the stream orders the levels.
 #include "common.hpp"
+#include "../../include/mgnns_jpeg_progressive.h"
 #include "jpeg_parse.hpp"
 #include "jpeg_pixels.hpp"
+#include "jpeg_progressive.hpp"
 
 namespace {
 
 constexpr int IMG = 16;         // int64 per image record
 constexpr int SEG = 5;          // int64 per segment record
+constexpr int PSEG = 12;        // int64 per segment record of a progressive scan
+constexpr int QSET = 3 * 64;    // bytes of one latched quantisation set: a table per component
 constexpr int MAXEXT = 8192;
 constexpr int NT = 256;
 constexpr int IDCT_BLOCKS = NT / 8;
@@ -33,11 +42,13 @@ struct Img {
     long long nmcu, blocks0, blocks;      // MCUs; blocks of component 0; blocks of all components
 };
 
+// kind 0: pixels staged by the host; 1: baseline; 2: progressive -- `set` then counts the latched quantisation sets (n_q of them),
+// a table per component, and the table ids are not read
 __device__ __forceinline__ bool load_img(const int64_t* __restrict__ r, int n_sets, size_t coef_elems, size_t plane_bytes,
-                                         size_t pixel_bytes, Img& m) {
+                                         size_t pixel_bytes, Img& m, int n_q = 0) {
     const long long kind = r[0], W = r[1], H = r[2], nc = r[3], hs = r[4], vs = r[5], mcux = r[6], mcuy = r[7], set = r[11];
     m.coef_off = r[12], m.plane_off = r[13], m.pix_off = r[14], m.pix_end = r[15];
-    if (kind != 0 && kind != 1) return false;
+    if (kind != 0 && kind != 1 && !(kind == 2 && n_q > 0)) return false;
     if (W < 1 || W > MAXEXT || H < 1 || H > MAXEXT) return false;
     if (m.pix_off < 0 || (m.pix_off & 15) || m.pix_end < m.pix_off || (unsigned long long)m.pix_end > pixel_bytes ||
         W * H * 3 > m.pix_end - m.pix_off)
@@ -46,7 +57,7 @@ __device__ __forceinline__ bool load_img(const int64_t* __restrict__ r, int n_se
     if (kind == 0) return true;                 // pixels staged by the host: nothing else is read
     if (!((nc == 1 && hs == 1 && vs == 1) || (nc == 3 && ((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))))) return false;
     if (mcux != (W + 8 * hs - 1) / (8 * hs) || mcuy != (H + 8 * vs - 1) / (8 * vs)) return false;
-    if (set < 0 || set >= n_sets) return false;
+    if (set < 0 || set >= (kind == 2 ? n_q : n_sets)) return false;
     m.ncomp = (int)nc, m.hs = (int)hs, m.vs = (int)vs, m.mcux = (int)mcux, m.mcuy = (int)mcuy, m.set = (int)set;
     m.nmcu = mcux * mcuy;
     m.blocks0 = m.nmcu * hs * vs;
@@ -98,12 +109,48 @@ __global__ __launch_bounds__(ENT_NT) void jpeg_entropy_kernel(const uint8_t* __r
     status[s] = st;
 }
 
+// One lane per segment of a progressive scan, segments [first, first + count) of pseg: one level of the batch.  A record:
+// image, begin, end (bytes in the data buffer), first unit, units, component mask, Ss, Se, Ah, Al, the pool indices of the DC tables
+// of components 0..2 and of the AC table (16 bits each, 0xFFFF = none), the scan's number in its file (not read here).  The tables
+// are read from global memory: the lanes of a level use many different ones, and one look-ahead table is 1 KB that stays in the
+// lane's cache lines.
+__global__ __launch_bounds__(ENT_NT) void jpeg_progressive_kernel(const uint8_t* __restrict__ data, size_t data_bytes,
+                                    const int64_t* __restrict__ img, int B, const int64_t* __restrict__ pseg, int first, int count, int lanes,
+                                    const MgJpegHuff* __restrict__ pool, int n_pool, int n_sets, int n_q,
+                                    int16_t* __restrict__ coef, size_t coef_elems, size_t plane_bytes, size_t pixel_bytes,
+                                    int32_t* __restrict__ status) {
+    const long long s = (long long)blockIdx.x * lanes + threadIdx.x;
+    if ((int)threadIdx.x >= lanes || s >= count) return;
+    const int64_t* const r = pseg + (first + s) * PSEG;
+    const long long im = r[0], b = r[1], e = r[2], unit0 = r[3], nunits = r[4], comps = r[5], ss = r[6], se = r[7], ah = r[8], al = r[9], tabs = r[10];
+    Img m;
+    int st = MG_JPEG_SEG_BAD_RECORD;
+    const int t0 = (int)(tabs & 0xFFFF), t1 = (int)((tabs >> 16) & 0xFFFF), t2 = (int)((tabs >> 32) & 0xFFFF), ta = (int)((tabs >> 48) & 0xFFFF);
+    auto table_ok = [&](int t) { return t == 0xFFFF || t < n_pool; };
+    if (im >= 0 && im < B && b >= 0 && b <= e && (unsigned long long)e <= data_bytes && unit0 >= 0 && nunits >= 1 && unit0 <= 0x7fffffffLL &&
+        nunits <= 0x7fffffffLL && comps >= 1 && comps <= 7 && ss >= 0 && ss <= 63 && se >= 0 && se <= 63 && ah >= 0 && ah <= 14 && al >= 0 &&
+        al <= 13 && table_ok(t0) && table_ok(t1) && table_ok(t2) && table_ok(ta) &&
+        load_img(img + im * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m, n_q) && m.kind == 2) {
+        MgJpegProgSegment g;
+        g.ncomp = m.ncomp, g.hs = m.hs, g.vs = m.vs, g.W = m.W, g.H = m.H, g.mcux = m.mcux, g.mcuy = m.mcuy;
+        g.comps = (int)comps, g.ss = (int)ss, g.se = (int)se, g.ah = (int)ah, g.al = (int)al, g.unit0 = (int)unit0, g.nunits = (int)nunits;
+        int16_t* const c0 = coef + m.coef_off;
+        int16_t* const c1 = c0 + m.blocks0 * 64;
+        int16_t* const c2 = c1 + m.nmcu * 64;
+        auto table = [&](int t) -> const MgJpegHuff* { return t == 0xFFFF ? nullptr : pool + t; };
+        // (the function checks the unit range against the scan's own count, the tables it needs against null, and the rest of g)
+        st = mg_jpeg_decode_progressive_segment(data + b, data + e, table(t0), table(t1), table(t2), table(ta), g, c0, c1, c2);
+    }
+    status[first + s] = st;
+}
+
 __global__ __launch_bounds__(NT) void jpeg_idct_kernel(const int64_t* __restrict__ img, const MgJpegTables* __restrict__ tables, int n_sets,
                                                        const int16_t* __restrict__ coef, size_t coef_elems, uint8_t* __restrict__ planes,
-                                                       size_t plane_bytes, size_t pixel_bytes) {
+                                                       size_t plane_bytes, size_t pixel_bytes, const uint8_t* __restrict__ qsets = nullptr,
+                                                       int n_q = 0) {
     __shared__ int32_t s_ws[IDCT_BLOCKS][8][9];
     Img m;
-    const bool ok = load_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) && m.kind == 1;   // (block-uniform)
+    const bool ok = load_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m, n_q) && m.kind != 0;   // (block-uniform)
     if (!ok || (long long)blockIdx.x * IDCT_BLOCKS >= m.blocks) return;
     const int lb = threadIdx.x >> 3, t = threadIdx.x & 7;
     const long long gb = (long long)blockIdx.x * IDCT_BLOCKS + lb;
@@ -111,7 +158,8 @@ __global__ __launch_bounds__(NT) void jpeg_idct_kernel(const int64_t* __restrict
     const int c = gb < m.blocks0 ? 0 : (gb < m.blocks0 + m.nmcu ? 1 : 2);
     if (live) {
         int32_t ws[8];
-        mg_jpeg_idct_column(coef + m.coef_off + gb * 64, tables[m.set].quant[c == 0 ? m.tq[0] : (c == 1 ? m.tq[1] : m.tq[2])], t, ws);
+        const uint8_t* const q = m.kind == 2 ? qsets + (size_t)m.set * QSET + 64 * c : tables[m.set].quant[c == 0 ? m.tq[0] : (c == 1 ? m.tq[1] : m.tq[2])];
+        mg_jpeg_idct_column(coef + m.coef_off + gb * 64, q, t, ws);
 #pragma unroll
         for (int r = 0; r < 8; ++r) s_ws[lb][r][t] = ws[r];
     }
@@ -136,9 +184,9 @@ __global__ __launch_bounds__(NT) void jpeg_idct_kernel(const int64_t* __restrict
 
 __global__ __launch_bounds__(NT) void jpeg_colour_kernel(const int64_t* __restrict__ img, int n_sets, size_t coef_elems,
                                                          const uint8_t* __restrict__ planes, size_t plane_bytes, uint8_t* __restrict__ pixels,
-                                                         size_t pixel_bytes) {
+                                                         size_t pixel_bytes, int n_q = 0) {
     Img m;
-    const bool ok = load_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) && m.kind == 1;
+    const bool ok = load_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m, n_q) && m.kind != 0;
     if (!ok) return;
     const long long npix = (long long)m.W * m.H, p = (long long)blockIdx.x * NT + threadIdx.x;
     if (blockIdx.x == 0) {                              // the padding up to the next image's start (behind the last: the slack too)
@@ -158,7 +206,13 @@ __global__ __launch_bounds__(NT) void jpeg_colour_kernel(const int64_t* __restri
     const uint8_t* const p1 = p0 + m.blocks0 * 64, * const p2 = p1 + m.nmcu * 64;
     const int dw = (m.W + m.hs - 1) / m.hs, dh = (m.H + m.vs - 1) / m.vs, pitch = 8 * m.mcux;
     uint8_t rgb[3];
-    mg_jpeg_rgb(Y, mg_jpeg_chroma(p1, pitch, dw, dh, m.hs, m.vs, x, y), mg_jpeg_chroma(p2, pitch, dw, dh, m.hs, m.vs, x, y), rgb);
+    int cb, cr;
+    if (m.kind == 2 && dw <= 2) {                       // (uniform over the image's workgroups; baseline images: never)
+        cb = mg_jpeg_chroma(p1, pitch, dw, dh, m.hs, m.vs, x, y, true), cr = mg_jpeg_chroma(p2, pitch, dw, dh, m.hs, m.vs, x, y, true);
+    } else {
+        cb = mg_jpeg_chroma(p1, pitch, dw, dh, m.hs, m.vs, x, y), cr = mg_jpeg_chroma(p2, pitch, dw, dh, m.hs, m.vs, x, y);
+    }
+    mg_jpeg_rgb(Y, cb, cr, rgb);
     o[0] = rgb[0];
     o[1] = rgb[1];
     o[2] = rgb[2];
@@ -217,6 +271,89 @@ extern "C" int mgnns_jpeg_decode_fwd(const void* data, size_t data_bytes, const 
         hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + NT - 1) / NT), (unsigned)B), dim3(NT), 0, st, img, n_sets,
                            coef_elems, (const uint8_t*)planes, plane_bytes, (uint8_t*)pixels, pixel_bytes);
         MG_CHECK_LAUNCH("mgnns_jpeg_decode_fwd (colour)");
+    }
+    return 0;
+}
+
+extern "C" size_t mgnns_jpeg_huff_bytes(void) { return sizeof(MgJpegHuff); }
+
+extern "C" int mgnns_jpeg_parse_progressive(const void* data, size_t bytes, int max_extent, int32_t* info, int64_t* scans, int64_t* seg,
+                                            size_t seg_cap, void* pool, void* quant) {
+    MG_REQUIRE(info && scans && pool && quant && (seg || seg_cap == 0) && (data || bytes == 0), "mgnns_jpeg_parse_progressive: null pointer");
+    MG_REQUIRE(max_extent >= 1 && max_extent <= MAXEXT, "mgnns_jpeg_parse_progressive: max_extent=%d (1..%d)", max_extent, MAXEXT);
+    static const uint8_t none = 0;
+    mg_jpeg_parse_progressive(data ? (const uint8_t*)data : &none, bytes, max_extent, info, scans, seg, seg_cap, (MgJpegHuff*)pool, (uint8_t*)quant);
+    return 0;
+}
+
+extern "C" int mgnns_jpeg_decode_progressive_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
+                                                 const void* tables, int n_sets, const int64_t* pseg, const int32_t* level_counts, int n_levels,
+                                                 const void* pool, int n_pool, const void* qsets, int n_q, void* coef, size_t coef_elems,
+                                                 void* planes, size_t plane_bytes, void* pixels, size_t pixel_bytes, long long max_blocks,
+                                                 long long max_pixels, int stages, int32_t* status, mgnns_stream_t stream) {
+    MG_REQUIRE(stages >= 1 && stages <= 7, "mgnns_jpeg_decode_progressive_fwd: stages=%d is no mask of 1 (entropy), 2 (IDCT), 4 (colour)", stages);
+    MG_REQUIRE(B >= 0 && B <= 65535 && S >= 0 && n_levels >= 0 && n_levels <= 64, "mgnns_jpeg_decode_progressive_fwd: B=%d (0..65535), S=%d, n_levels=%d (0..64)",
+               B, S, n_levels);
+    MG_REQUIRE(n_sets >= 0 && n_pool >= 0 && n_q >= 0, "mgnns_jpeg_decode_progressive_fwd: n_sets=%d, n_pool=%d, n_q=%d", n_sets, n_pool, n_q);
+    MG_REQUIRE(n_levels == 0 || level_counts, "mgnns_jpeg_decode_progressive_fwd: null level_counts");
+    long long P = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        MG_REQUIRE(level_counts[l] >= 0, "mgnns_jpeg_decode_progressive_fwd: level_counts[%d]=%d", l, level_counts[l]);
+        P += level_counts[l];
+    }
+    MG_REQUIRE(S + P <= 0x7fffffffLL, "mgnns_jpeg_decode_progressive_fwd: %lld segments", S + P);
+    if (B == 0 || S + P == 0) return 0;            // nothing to decode (every image staged by the host, or none at all)
+    MG_REQUIRE(data && img && coef && planes && pixels && status, "mgnns_jpeg_decode_progressive_fwd: null pointer");
+    MG_REQUIRE(S == 0 || (seg && tables && n_sets >= 1), "mgnns_jpeg_decode_progressive_fwd: baseline segments without a table set");
+    MG_REQUIRE(P == 0 || (pseg && pool && n_pool >= 1 && n_pool < 0xFFFF && qsets && n_q >= 1),
+               "mgnns_jpeg_decode_progressive_fwd: progressive segments without a table pool or quantisation sets");
+    MG_REQUIRE(mg_aligned16(coef) && mg_aligned16(planes) && mg_aligned16(pixels) && mg_aligned16(tables) && mg_aligned16(pool),
+               "mgnns_jpeg_decode_progressive_fwd: coef, planes, pixels, tables and pool must be 16-byte aligned");
+    MG_REQUIRE(max_blocks >= 1 && max_blocks <= 6LL * (MAXEXT / 8) * (MAXEXT / 8) && max_pixels >= 1 && max_pixels <= (long long)MAXEXT * MAXEXT,
+               "mgnns_jpeg_decode_progressive_fwd: max_blocks=%lld, max_pixels=%lld", max_blocks, max_pixels);
+    hipStream_t st = (hipStream_t)stream;
+    if (stages & 1) {
+        hipError_t e = hipMemsetAsync(coef, 0, coef_elems * sizeof(int16_t), st);
+        if (e != hipSuccess) {
+            mgnns_set_error("mgnns_jpeg_decode_progressive_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
+            return MGNNS_ERR_LAUNCH;
+        }
+    }
+    const int cus = mg_cu_count();
+    if (cus <= 0) return MGNNS_ERR_LAUNCH;
+    auto lanes_for = [&](long long n) {            // one lane per wave until every SIMD (4 per CU) has one
+        int lanes = 1;
+        while (lanes < 64 && (long long)lanes * 4 * cus < n) lanes *= 2;
+        return lanes;
+    };
+    if ((stages & 1) && S > 0) {
+        const int lanes = lanes_for(S);
+        hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((S + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
+                           data_bytes, img, B, seg, S, lanes, (const MgJpegTables*)tables, n_sets, (int16_t*)coef, coef_elems, plane_bytes,
+                           pixel_bytes, status);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (baseline entropy)");
+    }
+    int first = 0;
+    for (int l = 0; (stages & 1) && l < n_levels; ++l) {
+        const int count = level_counts[l];
+        if (count == 0) continue;
+        const int lanes = lanes_for(count);
+        hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)((count + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
+                           data_bytes, img, B, pseg, first, count, lanes, (const MgJpegHuff*)pool, n_pool, n_sets, n_q, (int16_t*)coef, coef_elems,
+                           plane_bytes, pixel_bytes, status + S);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (progressive entropy)");
+        first += count;
+    }
+    if (stages & 2) {
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)B), dim3(NT), 0, st, img,
+                           (const MgJpegTables*)tables, n_sets, (const int16_t*)coef, coef_elems, (uint8_t*)planes, plane_bytes, pixel_bytes,
+                           (const uint8_t*)qsets, n_q);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (idct)");
+    }
+    if (stages & 4) {
+        hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + NT - 1) / NT), (unsigned)B), dim3(NT), 0, st, img, n_sets, coef_elems,
+                           (const uint8_t*)planes, plane_bytes, (uint8_t*)pixels, pixel_bytes, n_q);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (colour)");
     }
     return 0;
 }

@@ -286,3 +286,317 @@ inline int mg_jpeg_parse(const uint8_t* data, size_t n, int max_extent, int32_t*
     range[1] = (int64_t)ecs_end;
     return MG_JPEG_OK;
 }
+
+// ---- progressive files (SOF2) ---------------------------------------------------------------------------------------------------
+// further reason codes, of mg_jpeg_parse_progressive alone
+enum {
+    MG_JPEG_INCOMPLETE_PROGRESSION = 14,   // at EOI / the end of the file a coefficient has not reached Al = 0; detail = 64 c + k
+    MG_JPEG_ILLEGAL_PROGRESSION = 15,      // Ss / Se / Ah / Al contradict T.81 G.1.1.1.1 or the scans before; detail = the scan
+    MG_JPEG_TOO_MANY_SCANS = 16,           // more than MG_JPEG_MAX_SCANS scans
+};
+// further fields of info[] (the baseline fields TQ / TD / TA / RI / RESTARTS stay zero: they are per scan here; NSEG counts the
+// segments of all scans)
+enum { MG_JPEG_I_NSCANS = 21, MG_JPEG_I_NTABLES = 22, MG_JPEG_I_NLEVELS = 23 };
+// fields of one scan record, int64 scan[MG_JPEG_SCAN_INTS]
+enum {
+    MG_JPEG_S_NS = 0,                      // components in the scan
+    MG_JPEG_S_COMPS = 1,                   // mask of the frame's components in it (bit c)
+    MG_JPEG_S_SS = 2, MG_JPEG_S_SE, MG_JPEG_S_AH, MG_JPEG_S_AL,
+    MG_JPEG_S_RI = 6,                      // the restart interval in force at its SOS, in units (MCUs, or blocks of its one component)
+    MG_JPEG_S_LEVEL = 7,
+    MG_JPEG_S_DC = 8,                      // 3: index into the table pool of the frame component's DC table, -1 = none read
+    MG_JPEG_S_AC = 11,                     // index of the AC table, -1 = none read
+    MG_JPEG_S_SEG0 = 12, MG_JPEG_S_NSEG,   // its segments in seg[]
+    MG_JPEG_S_UNITS = 14,                  // units of the whole scan
+    MG_JPEG_S_BEGIN = 15, MG_JPEG_S_END,   // [begin, end) of its entropy-coded data
+    MG_JPEG_S_RESTARTS = 17,               // RSTn markers found in it
+    MG_JPEG_SCAN_INTS = 18,
+};
+constexpr int MG_JPEG_MAX_SCANS = 32;
+constexpr int MG_JPEG_POOL_TABLES = 3 * MG_JPEG_MAX_SCANS;     // no file needs more: a scan reads at most three tables
+
+// Parse one progressive file: SOF2, 8 bit, Huffman, the baseline decoder's component layouts, any legal progression script of at
+// most 32 scans with DHT / DQT / DRI between them.  A file that is not SOF2 gets the reason mg_jpeg_parse gives it (a baseline
+// file: MG_JPEG_UNSUPPORTED_SOF with detail 0xC0 -- parse it with mg_jpeg_parse).
+//  info   as mg_jpeg_parse, with the fields above.
+//  scan   [MG_JPEG_MAX_SCANS][MG_JPEG_SCAN_INTS] int64, in file order.  The LEVEL of a scan is 0 if no earlier scan touches a
+//         (component, coefficient) it touches, else 1 + the largest level among those that do; an AC scan also counts as touching
+//         what the component's first DC scan did (T.81 orders them so).  Scans of one level write different int16 elements.
+//  seg    [seg_cap][4] int64: begin, end (bytes), first unit, units of every independent segment, scan after scan; as many as fit
+//         (info[NSEG] says how many there are).  With fewer restart markers than the interval asks for, the last segments are empty.
+//  pool   [MG_JPEG_POOL_TABLES] MgJpegHuff: the distinct tables the scans read; info[NTABLES] of them are filled, the rest is zero.
+//  quant  [3][64]: per component, in natural order, the quantisation table in force at the component's first scan.
+// After the first scan, anything that cannot be read as a marker segment ends the file, as EOI does.
+inline int mg_jpeg_parse_progressive(const uint8_t* data, size_t n, int max_extent, int32_t* info, int64_t* scan, int64_t* seg,
+                                     size_t seg_cap, MgJpegHuff* pool, uint8_t* quant_out) {
+    using namespace mgjpeg;
+    const Reader R{data, n};
+    memset(info, 0, sizeof(int32_t) * MG_JPEG_INFO_INTS);
+    memset(scan, 0, sizeof(int64_t) * MG_JPEG_MAX_SCANS * MG_JPEG_SCAN_INTS);
+    memset(pool, 0, sizeof(MgJpegHuff) * MG_JPEG_POOL_TABLES);
+    memset(quant_out, 0, 3 * 64);
+    auto refuse = [&](int reason, long long detail) {
+        info[MG_JPEG_I_REASON] = reason;
+        info[MG_JPEG_I_DETAIL] = (int32_t)(detail > 0x7fffffffLL ? 0x7fffffffLL : detail);
+        return reason;
+    };
+    if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return refuse(MG_JPEG_NOT_JPEG, 0);
+
+    uint8_t quant[4][64];
+    uint8_t hbits[2][4][16], hvals[2][4][256];
+    int hcount[2][4], hpool[2][4];                   // hpool: where the table in force lies in the pool, -1 = not derived yet
+    bool have_q[4] = {false, false, false, false}, have_h[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    bool have_frame = false, latched[3] = {false, false, false};
+    int width = 0, height = 0, ncomp = 0, comp_id[3] = {0, 0, 0}, comp_h[3] = {1, 1, 1}, comp_v[3] = {1, 1, 1}, comp_tq[3] = {0, 0, 0};
+    int ri = 0, adobe = -1, nscans = 0, ntables = 0, nlevels = 0;
+    int bits_left[3][64], level_of[3][64], dc_level[3] = {-1, -1, -1};      // Al a coefficient stands at (-1: never sent); last level
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 64; ++k) bits_left[c][k] = level_of[c][k] = -1;
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 4; ++b) hpool[a][b] = -1, hcount[a][b] = 0;
+    long long nseg_total = 0;
+    static const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    // the table (tc, th) in force, as a pool index: derived once, shared with an earlier table of the same content; -1 = no prefix code
+    auto pooled = [&](int tc, int th) -> int {
+        if (hpool[tc][th] >= 0) return hpool[tc][th];
+        if (ntables >= MG_JPEG_POOL_TABLES) return -1;
+        MgJpegHuff* const h = pool + ntables;
+        if (!derive(hbits[tc][th], hvals[tc][th], hcount[tc][th], h)) {
+            memset(h, 0, sizeof(*h));
+            return -1;
+        }
+        for (int i = 0; i < ntables; ++i)
+            if (memcmp(pool + i, h, sizeof(*h)) == 0) {
+                memset(h, 0, sizeof(*h));
+                return hpool[tc][th] = i;
+            }
+        return hpool[tc][th] = ntables++;
+    };
+    size_t pos = 2;
+    for (;;) {
+        // ---- the next marker segment; after the first scan, what cannot be read ends the file ----
+        if (!R.has(pos, 2) || data[pos] != 0xFF) {
+            if (nscans) break;
+            return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        }
+        while (pos + 1 < n && data[pos + 1] == 0xFF) ++pos;                  // fill bytes
+        if (!R.has(pos, 2)) {
+            if (nscans) break;
+            return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        }
+        const int m = data[pos + 1];
+        pos += 2;
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;    // stand-alone markers
+        if (m == 0xD9) {
+            if (nscans) break;
+            return refuse(MG_JPEG_MALFORMED, (long long)pos);                // EOI before any scan
+        }
+        if (!R.has(pos, 2) || R.u16(pos) < 2 || !R.has(pos, (size_t)R.u16(pos))) {
+            if (nscans) break;
+            return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        }
+        const int ln = R.u16(pos);
+        const size_t body = pos + 2, end = pos + (size_t)ln;
+        if (m == 0xDB) {
+            size_t p = body;
+            while (p < end) {
+                const int pq = data[p] >> 4, tq = data[p] & 15;
+                if (pq != 0) return refuse(MG_JPEG_PRECISION, 16);
+                if (tq > 3 || p + 65 > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                for (int k = 0; k < 64; ++k) quant[tq][ZIGZAG[k]] = data[p + 1 + k];
+                have_q[tq] = true;
+                p += 65;
+            }
+        } else if (m == 0xC4) {
+            size_t p = body;
+            while (p < end) {
+                if (p + 17 > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                const int tc = data[p] >> 4, th = data[p] & 15;
+                int cnt = 0;
+                for (int i = 0; i < 16; ++i) cnt += data[p + 1 + i];
+                if (tc > 1 || th > 3 || cnt > 256 || p + 17 + (size_t)cnt > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                int code = 0;
+                for (int l = 1; l <= 16; ++l) {
+                    code += data[p + l];
+                    if (code > (1 << l)) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                    code <<= 1;
+                }
+                memcpy(hbits[tc][th], data + p + 1, 16);
+                memcpy(hvals[tc][th], data + p + 17, (size_t)cnt);
+                hcount[tc][th] = cnt;
+                have_h[tc][th] = true;
+                hpool[tc][th] = -1;
+                p += 17 + (size_t)cnt;
+            }
+        } else if (m == 0xDD) {
+            if (ln != 4) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            ri = R.u16(body);
+        } else if (m == 0xCC || (m >= 0xC9 && m <= 0xCF)) {
+            return refuse(MG_JPEG_ARITHMETIC, m);
+        } else if (m == 0xC0 || m == 0xC1 || m == 0xC3 || m == 0xC5 || m == 0xC6 || m == 0xC7 || m == 0xC8) {
+            return refuse(MG_JPEG_UNSUPPORTED_SOF, m);
+        } else if (m == 0xC2) {
+            if (have_frame || ln < 8) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int prec = data[body], nf = data[body + 5];
+            height = R.u16(body + 1);
+            width = R.u16(body + 3);
+            if (prec != 8) return refuse(MG_JPEG_PRECISION, prec);
+            if (ln != 8 + 3 * nf) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            if (nf != 1 && nf != 3) return refuse(MG_JPEG_COMPONENTS, nf);
+            if (height == 0) return refuse(MG_JPEG_DNL, 0);
+            if (width < 1 || width > max_extent || height > max_extent) return refuse(MG_JPEG_EXTENT, width > max_extent ? width : height);
+            ncomp = nf;
+            for (int i = 0; i < nf; ++i) {
+                comp_id[i] = data[body + 6 + 3 * i];
+                comp_h[i] = data[body + 7 + 3 * i] >> 4;
+                comp_v[i] = data[body + 7 + 3 * i] & 15;
+                comp_tq[i] = data[body + 8 + 3 * i];
+            }
+            if (nf == 3 && comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B') return refuse(MG_JPEG_RGB_IDS, 0);
+            for (int i = 0; i < nf; ++i)
+                if (comp_tq[i] > 3) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int hv = comp_h[0] * 16 + comp_v[0];
+            if (nf == 1) {
+                if (hv != 0x11) return refuse(MG_JPEG_SAMPLING, hv);
+            } else if ((hv != 0x11 && hv != 0x21 && hv != 0x22) || comp_h[1] != 1 || comp_v[1] != 1 || comp_h[2] != 1 || comp_v[2] != 1) {
+                return refuse(MG_JPEG_SAMPLING, hv);
+            }
+            have_frame = true;
+        } else if (m == 0xDC) {
+            return refuse(MG_JPEG_DNL, 0);
+        } else if (m == 0xEE && ln >= 14 && memcmp(data + body, "Adobe", 5) == 0) {
+            adobe = data[body + 11];
+        } else if (m == 0xDA) {
+            if (!have_frame) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            if (nscans == MG_JPEG_MAX_SCANS) return refuse(MG_JPEG_TOO_MANY_SCANS, nscans + 1);
+            const int ns = ln >= 3 ? data[body] : 0;
+            if (ns < 1 || ns > ncomp || ln != 6 + 2 * ns) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            int sc_comp[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0}, mask = 0;
+            for (int i = 0, c = 0; i < ns; ++i, ++c) {                       // the frame's components, in the frame's order
+                while (c < ncomp && comp_id[c] != data[body + 1 + 2 * i]) ++c;
+                if (c >= ncomp) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+                sc_comp[i] = c;
+                mask |= 1 << c;
+                td[i] = data[body + 2 + 2 * i] >> 4;
+                ta[i] = data[body + 2 + 2 * i] & 15;
+                if (td[i] > 3 || ta[i] > 3) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            }
+            const int ss = data[body + 1 + 2 * ns], se = data[body + 2 + 2 * ns], ah = data[body + 3 + 2 * ns] >> 4, al = data[body + 3 + 2 * ns] & 15;
+            if (adobe == 0 && ncomp == 3) return refuse(MG_JPEG_ADOBE_TRANSFORM, 0);
+            // T.81 G.1.1.1.1, and the scans before this one
+            bool legal = ss == 0 ? se == 0 : (ss <= se && se <= 63 && ns == 1);
+            if (ah != 0 && al != ah - 1) legal = false;
+            if (al > 13) legal = false;
+            for (int i = 0; legal && i < ns; ++i) {
+                const int c = sc_comp[i];
+                if (ss != 0 && bits_left[c][0] < 0) legal = false;           // AC before the component's DC
+                for (int k = ss; k <= se; ++k)
+                    if (bits_left[c][k] < 0 ? ah != 0 : (ah == 0 || ah != bits_left[c][k])) legal = false;
+            }
+            if (!legal) return refuse(MG_JPEG_ILLEGAL_PROGRESSION, nscans);
+            int64_t* const S = scan + (size_t)nscans * MG_JPEG_SCAN_INTS;
+            for (int c = 0; c < 3; ++c) S[MG_JPEG_S_DC + c] = -1;
+            S[MG_JPEG_S_AC] = -1;
+            int level = 0;
+            for (int i = 0; i < ns; ++i) {
+                const int c = sc_comp[i];
+                if (!latched[c]) {                                           // the quantisation table in force at its first scan
+                    if (!have_q[comp_tq[c]]) return refuse(MG_JPEG_MISSING_TABLES, c);
+                    memcpy(quant_out + 64 * c, quant[comp_tq[c]], 64);
+                    latched[c] = true;
+                }
+                if (ah == 0) {                                               // a refinement of DC reads no table
+                    const int tc = ss == 0 ? 0 : 1, th = ss == 0 ? td[i] : ta[i];
+                    if (!have_h[tc][th]) return refuse(MG_JPEG_MISSING_TABLES, c);
+                    const int at = pooled(tc, th);
+                    if (at < 0) return refuse(MG_JPEG_MALFORMED, c);
+                    S[ss == 0 ? MG_JPEG_S_DC + c : MG_JPEG_S_AC] = at;
+                } else if (ss != 0) {
+                    if (!have_h[1][ta[i]]) return refuse(MG_JPEG_MISSING_TABLES, c);
+                    const int at = pooled(1, ta[i]);
+                    if (at < 0) return refuse(MG_JPEG_MALFORMED, c);
+                    S[MG_JPEG_S_AC] = at;
+                }
+                if (ss != 0 && dc_level[c] + 1 > level) level = dc_level[c] + 1;
+                for (int k = ss; k <= se; ++k)
+                    if (level_of[c][k] + 1 > level) level = level_of[c][k] + 1;
+            }
+            for (int i = 0; i < ns; ++i) {
+                const int c = sc_comp[i];
+                if (ss == 0 && dc_level[c] < 0) dc_level[c] = level;
+                for (int k = ss; k <= se; ++k) bits_left[c][k] = al, level_of[c][k] = level;
+            }
+            if (level + 1 > nlevels) nlevels = level + 1;
+            // units: MCUs, or the blocks of the one component
+            const int hs = comp_h[0], vs = comp_v[0];
+            long long units;
+            if (ns > 1) {
+                units = (long long)((width + 8 * hs - 1) / (8 * hs)) * ((height + 8 * vs - 1) / (8 * vs));
+            } else {
+                const int c = sc_comp[0], h = comp_h[c], v = comp_v[c];
+                const int wc = (width * h + hs - 1) / hs, hc = (height * v + vs - 1) / vs;
+                units = (long long)((wc + 7) / 8) * ((hc + 7) / 8);
+            }
+            const long long nseg = ri ? (units + ri - 1) / ri : 1;
+            // the entropy-coded data: up to the first marker that is neither a stuffed FF, a fill byte nor RSTn
+            size_t i = end, seg_begin = end;
+            long long found = 0;
+            auto put = [&](long long j, size_t b, size_t e) {
+                if (j < nseg && (size_t)(nseg_total + j) < seg_cap) {
+                    int64_t* const g = seg + 4 * (size_t)(nseg_total + j);
+                    g[0] = (int64_t)b, g[1] = (int64_t)e;
+                    g[2] = ri ? j * ri : 0;
+                    g[3] = ri ? (units - j * ri < ri ? units - j * ri : ri) : units;
+                }
+            };
+            for (;;) {
+                while (i < n && data[i] != 0xFF) ++i;
+                if (i + 1 >= n) {
+                    i = n;
+                    break;
+                }
+                const int b = data[i + 1];
+                if (b == 0) {
+                    i += 2;
+                } else if (b == 0xFF) {
+                    i += 1;
+                } else if (b >= 0xD0 && b <= 0xD7) {
+                    put(found, seg_begin, i);
+                    ++found;
+                    i += 2;
+                    seg_begin = i;
+                } else {
+                    break;
+                }
+            }
+            put(found, seg_begin, i);
+            for (long long j = found + 1; j < nseg; ++j) put(j, i, i);
+            S[MG_JPEG_S_NS] = ns, S[MG_JPEG_S_COMPS] = mask, S[MG_JPEG_S_SS] = ss, S[MG_JPEG_S_SE] = se, S[MG_JPEG_S_AH] = ah, S[MG_JPEG_S_AL] = al;
+            S[MG_JPEG_S_RI] = ri, S[MG_JPEG_S_LEVEL] = level, S[MG_JPEG_S_SEG0] = nseg_total, S[MG_JPEG_S_NSEG] = nseg, S[MG_JPEG_S_UNITS] = units;
+            S[MG_JPEG_S_BEGIN] = (int64_t)end, S[MG_JPEG_S_END] = (int64_t)i, S[MG_JPEG_S_RESTARTS] = found;
+            nseg_total += nseg;
+            if (nseg_total > 0x7fffffffLL) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            ++nscans;
+            pos = i;
+            continue;
+        }
+        pos = end;
+    }
+    for (int c = 0; c < ncomp; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (bits_left[c][k] != 0) return refuse(MG_JPEG_INCOMPLETE_PROGRESSION, 64 * c + k);
+    info[MG_JPEG_I_WIDTH] = width;
+    info[MG_JPEG_I_HEIGHT] = height;
+    info[MG_JPEG_I_NCOMP] = ncomp;
+    info[MG_JPEG_I_HS] = comp_h[0];
+    info[MG_JPEG_I_VS] = comp_v[0];
+    info[MG_JPEG_I_NSEG] = (int32_t)nseg_total;
+    info[MG_JPEG_I_MCUX] = (width + 8 * comp_h[0] - 1) / (8 * comp_h[0]);
+    info[MG_JPEG_I_MCUY] = (height + 8 * comp_v[0] - 1) / (8 * comp_v[0]);
+    info[MG_JPEG_I_NSCANS] = nscans;
+    info[MG_JPEG_I_NTABLES] = ntables;
+    info[MG_JPEG_I_NLEVELS] = nlevels;
+    return MG_JPEG_OK;
+}

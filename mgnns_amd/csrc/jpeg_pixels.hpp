@@ -66,8 +66,12 @@ MG_HD void mg_jpeg_idct_row(const int32_t ws[8], uint8_t out[8]) {
 
 // The chroma sample at full-resolution (x, y) of a plane with dw x dh real samples (pitch bytes per row), sampled 1 / hs by 1 / vs:
 // libjpeg's "fancy" triangle filters.  Edges replicate the first / last REAL sample or row.  0 <= x < hs dw, 0 <= y < vs dh.
-MG_HD int mg_jpeg_chroma(const uint8_t* plane, int pitch, int dw, int dh, int hs, int vs, int x, int y) {
+// replicate: the plane is at most two samples wide and its samples are to be repeated, not filtered, as libjpeg does for such planes
+// (jdsample.c filters only where downsampled_width > 2).  The progressive decoder passes dw <= 2; the baseline decoder passes false
+// and keeps the pixels it always gave for files of width 2..4 ("Progressive files").
+MG_HD int mg_jpeg_chroma(const uint8_t* plane, int pitch, int dw, int dh, int hs, int vs, int x, int y, bool replicate = false) {
     if (hs == 1) return plane[(size_t)y * pitch + x];             // (vs == 1 too: 1x2 is not accepted)
+    if (replicate) return plane[(size_t)(vs == 2 ? y >> 1 : y) * pitch + (x >> 1)];
     const int i = x >> 1, odd = x & 1;
     const int in = odd ? (i + 1 < dw ? i + 1 : dw - 1) : (i > 0 ? i - 1 : 0);       // the neighbour this output leans towards
     const bool edge = x == 0 || x == 2 * dw - 1;

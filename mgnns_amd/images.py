@@ -13,7 +13,8 @@ run its passes in the other order (seen at 1000x7 -> 16 and 1000x8 -> 16) and th
 
 An image is a [H,W,3] uint8 array, or anything with __array_interface__ (a PIL image in mode RGB) -- or the bytes of a baseline JPEG
 file, which decode_jpeg / warp_jpeg / train_jpeg decode on the GPU to exactly Pillow's pixels (csrc/jpeg_decode.hip):
-the host only parses the markers.  This module does not import PIL."""
+the host only parses the markers.  ImagePrep(..., progressive=True) decodes progressive (SOF2) files as well (csrc/jpeg_progressive.hpp);
+the switch is off by default, and a progressive file is then refused with reason 3 as before.  This module does not import PIL."""
 import math
 import random
 
@@ -109,6 +110,10 @@ JPEG_REASONS = {
     7: "Adobe APP14 segment with transform 0 (RGB)", 8: "component ids R, G, B", 9: "sampling factors other than 4:4:4, 4:2:2, 4:2:0",
     10: "more than one scan, or a non-interleaved scan", 11: "height given by a DNL segment", 12: "extent out of range",
     13: "the scan refers to a table that is not defined"}
+# further codes of the progressive parser (parse_jpeg(..., progressive=True)); JPEG_REASONS stays the baseline parser's own set
+JPEG_PROGRESSIVE_REASONS = {
+    14: "incomplete progression: at the end of the file a coefficient has not had its last bit (libjpeg would smooth it)",
+    15: "illegal progression: Ss / Se / Ah / Al contradict T.81 G.1.1.1.1 or the scans before", 16: "more than 32 scans"}
 _JI = dict(reason=0, detail=1, width=2, height=3, ncomp=4, hs=5, vs=6, tq=7, td=10, ta=13, ri=16, restarts=17, nseg=18, mcux=19, mcuy=20)
 
 
@@ -118,7 +123,8 @@ class UnsupportedJpeg(ValueError):
     def __init__(self, refused, details):
         self.refused = refused
         ValueError.__init__(self, "%d JPEG file(s) cannot be decoded on the GPU (pass fallback= to decode them yourself): %s" % (
-            len(refused), "; ".join("image %d: %s (reason %d, found %s)" % (i, JPEG_REASONS.get(r, "?"), r, d) for (i, r), d in zip(refused, details))))
+            len(refused), "; ".join("image %d: %s (reason %d, found %s)" % (i, JPEG_REASONS.get(r) or JPEG_PROGRESSIVE_REASONS.get(r, "?"), r, d)
+                                   for (i, r), d in zip(refused, details))))
 
 
 def _file_bytes(f, i=0):
@@ -127,10 +133,56 @@ def _file_bytes(f, i=0):
     return np.frombuffer(f, dtype=np.uint8)
 
 
-def parse_jpeg(data, max_extent=None, _seg=None):
+_JS = dict(ns=0, comps=1, ss=2, se=3, ah=4, al=5, ri=6, level=7, dc=8, ac=11, seg0=12, nseg=13, units=14, begin=15, end=16, restarts=17)
+JPEG_MAX_SCANS, _JPEG_SCAN_INTS, _JPEG_POOL_TABLES = 32, 18, 96
+
+
+def _parse_progressive(a, max_extent, bufs=None):
+    """mgnns_jpeg_parse_progressive on one file's bytes (a uint8 array) -> parse_jpeg's dict for a progressive file."""
+    from . import _lib
+    HB = ops.jpeg_huff_bytes()
+    if bufs is None:
+        bufs = (np.zeros((JPEG_MAX_SCANS, _JPEG_SCAN_INTS), np.int64), np.zeros((256, 4), np.int64), np.zeros((_JPEG_POOL_TABLES, HB), np.uint8))
+    scans, seg, pool = bufs
+    info = np.zeros(24, np.int32)
+    quant = np.zeros(ops.JPEG_QSET, np.uint8)
+    ptr = a.ctypes.data if a.size else None
+    for _ in range(2):
+        _lib.call("mgnns_jpeg_parse_progressive", ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, scans.ctypes.data,
+                  seg.ctypes.data, seg.shape[0], pool.ctypes.data, quant.ctypes.data)
+        if info[0] != 0 or info[_JI["nseg"]] <= seg.shape[0]:
+            break
+        seg = np.zeros((int(info[_JI["nseg"]]), 4), np.int64)
+    out = dict(reason=int(info[0]), detail=int(info[1]))
+    if out["reason"] == 0:
+        for k in ("width", "height", "ncomp", "hs", "vs", "nseg", "mcux", "mcuy"):
+            out[k] = int(info[_JI[k]])
+        out["scans"] = []
+        for r in scans[:int(info[21])]:
+            d = {k: int(r[_JS[k]]) for k in ("ns", "ss", "se", "ah", "al", "ri", "level", "ac", "seg0", "nseg", "units", "restarts")}
+            d["comps"] = [c for c in range(3) if int(r[_JS["comps"]]) >> c & 1]
+            d["dc"] = [int(v) for v in r[_JS["dc"]:_JS["dc"] + 3]]
+            d["ecs"] = (int(r[_JS["begin"]]), int(r[_JS["end"]]))
+            out["scans"].append(d)
+        out["levels"] = int(info[23])
+        out["segments"] = seg[:out["nseg"]].copy()
+        out["pool"] = [pool[t].tobytes() for t in range(int(info[22]))]
+        out["quant"] = quant.tobytes()
+    return out
+
+
+def parse_jpeg(data, max_extent=None, _seg=None, progressive=False, _bufs=None):
     """The host parser (mgnns_jpeg_parse: no GPU call) on one file's bytes -> dict: reason (0 = accepted), detail, and for an accepted
     file width, height, ncomp, hs, vs (Y's sampling), tq / td / ta (table ids per component), ri, restarts (markers found), nseg, mcux,
-    mcuy, ecs (begin, end), segments (int64 [nseg,2] byte ranges) and tables (the table set's bytes)."""
+    mcuy, ecs (begin, end), segments (int64 [nseg,2] byte ranges) and tables (the table set's bytes).
+
+    progressive=True also accepts SOF2 files (mgnns_jpeg_parse_progressive, DESIGN.md 17, "Progressive files").  The dictionary then carries `scans`
+    and `levels`: for a baseline file [] and 0 beside the fields above; for a progressive file the scans in file order -- each a dict
+    of ns, comps (the frame's components in it), ss, se, ah, al, ri (in units: MCUs, or blocks of its one component), level, dc (pool
+    index of the DC table per frame component, -1 = none read), ac, seg0 / nseg (its rows of `segments`), units, ecs, restarts -- with
+    width, height, ncomp, hs, vs, mcux, mcuy, nseg (of all scans), segments (int64 [nseg,4]: begin, end, first unit, units), pool (the
+    distinct Huffman tables' bytes) and quant (192 bytes: per component the quantisation table in force at its first scan).  Scans
+    of one level touch different coefficients and decode at the same time; levels run in order."""
     from . import _lib
     a = _file_bytes(data)
     info = np.zeros(24, np.int32)
@@ -153,6 +205,10 @@ def parse_jpeg(data, max_extent=None, _seg=None):
         out["ecs"] = (int(rng[0]), int(rng[1]))
         out["segments"] = seg[:out["nseg"]].copy()
         out["tables"] = tables.tobytes()
+        if progressive:
+            out["scans"], out["levels"] = [], 0
+    elif progressive and out["reason"] == 3 and out["detail"] == 0xC2:
+        return _parse_progressive(a, max_extent, _bufs)
     return out
 
 
@@ -211,7 +267,7 @@ class Packed:
 
 class ImagePrep:
     def __init__(self, size=448, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device=None, scales=SCALES,
-                 max_distort=MAX_DISTORT, ring=2):
+                 max_distort=MAX_DISTORT, ring=2, progressive=False):
         size = int(size)
         if not 1 <= size <= ops.IMAGE_MAX_SIZE:
             raise ValueError("size must be in 1..%d, got %d" % (ops.IMAGE_MAX_SIZE, size))
@@ -222,6 +278,7 @@ class ImagePrep:
         if int(ring) < 2:
             raise ValueError("the pinned ring needs at least two batches, got %d" % ring)
         self.size = size
+        self.progressive = bool(progressive)         # decode_jpeg / warp_jpeg / train_jpeg also decode progressive (SOF2) files
         self.scales, self.max_distort = tuple(scales), int(max_distort)
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
@@ -380,10 +437,14 @@ class ImagePrep:
         one exception.  -> (files, parsed, {index: fall-back pixels}, [(W, H)])"""
         files = list(files)
         seg = np.zeros((1024, 2), np.int64)
+        bufs = None
+        if self.progressive:
+            bufs = (np.zeros((JPEG_MAX_SCANS, _JPEG_SCAN_INTS), np.int64), np.zeros((1024, 4), np.int64),
+                    np.zeros((_JPEG_POOL_TABLES, ops.jpeg_huff_bytes()), np.uint8))
         parsed, refused = [], []
         for i, f in enumerate(files):
             _file_bytes(f, i)
-            parsed.append(parse_jpeg(f, _seg=seg))
+            parsed.append(parse_jpeg(f, _seg=seg, progressive=self.progressive, _bufs=bufs))
             if parsed[-1]["reason"]:
                 refused.append((i, parsed[-1]["reason"]))
         if refused and fallback is None:
@@ -418,21 +479,31 @@ class ImagePrep:
                 desc_rows.append((offs[i], H, W, cx, cy, cw, ch, 1 if (flips is not None and bool(flips[i])) else 0, self.plan(cw), self.plan(ch)))
         # layout of the raw buffer: the accepted files at 16-byte starts, the table sets, then the fall-back images' pixels
         TB = ops.jpeg_tableset_bytes()
-        raw_off, n, sets = {}, 0, {}
+        HB = ops.jpeg_huff_bytes() if self.progressive else 0
+        raw_off, n, sets, pool, qsets = {}, 0, {}, {}, {}
         for i, f in enumerate(files):
             if i not in arrays:
                 raw_off[i] = n
                 n += (_file_bytes(f).size + ALIGN - 1) // ALIGN * ALIGN
-                sets.setdefault(parsed[i]["tables"], len(sets))
+                if "pool" in parsed[i]:                                 # a progressive file: its tables go to the batch's pool
+                    for t in parsed[i]["pool"]:
+                        pool.setdefault(t, len(pool))
+                    qsets.setdefault(parsed[i]["quant"], len(qsets))
+                else:
+                    sets.setdefault(parsed[i]["tables"], len(sets))
         tab_off = n
         n += len(sets) * TB
+        pool_off = n
+        n += len(pool) * HB
+        q_off = n
+        n += len(qsets) * ops.JPEG_QSET
         n_data = n
         fb_off = {}
         for i in arrays:
             fb_off[i] = n
             n += ends[i] - offs[i]
         img = np.zeros((B, ops.JPEG_IMG), np.int64)
-        segs, coef_off, plane_off = [], 0, 0
+        segs, psegs, coef_off, plane_off = [], [], 0, 0
         for i, p in enumerate(parsed):
             W, H = sizes[i]
             if i in arrays:
@@ -441,6 +512,25 @@ class ImagePrep:
             nmcu = p["mcux"] * p["mcuy"]
             blocks = nmcu if p["ncomp"] == 1 else nmcu * (p["hs"] * p["vs"] + 2)
             pack3 = lambda v: v[0] | v[1] << 8 | v[2] << 16
+            if "pool" in p:                      # progressive: kind 2, the latched quantisation set, a record per segment of every scan
+                img[i] = (2, W, H, p["ncomp"], p["hs"], p["vs"], p["mcux"], p["mcuy"], 0, 0, 0, qsets[p["quant"]], coef_off, plane_off,
+                          offs[i], ends[i])
+                coef_off += blocks * 64
+                plane_off += blocks * 64
+                at = [pool[t] for t in p["pool"]]
+                s = np.empty((p["nseg"], ops.JPEG_PSEG + 1), np.int64)     # (the last column, the level, is the sort key)
+                s[:, 0] = i
+                s[:, 1:3] = p["segments"][:, :2] + raw_off[i]
+                s[:, 3:5] = p["segments"][:, 2:]
+                for k, sc in enumerate(p["scans"]):
+                    rows = slice(sc["seg0"], sc["seg0"] + sc["nseg"])
+                    tabs = 0
+                    for j, t in enumerate(sc["dc"] + [sc["ac"]]):
+                        tabs |= (0xFFFF if t < 0 else at[t]) << (16 * j)
+                    s[rows, 5:] = (sum(1 << c for c in sc["comps"]), sc["ss"], sc["se"], sc["ah"], sc["al"],
+                                   tabs - (1 << 64) if tabs >= 1 << 63 else tabs, k, sc["level"])
+                psegs.append(s)
+                continue
             img[i] = (1, W, H, p["ncomp"], p["hs"], p["vs"], p["mcux"], p["mcuy"], pack3(p["tq"]), pack3(p["td"]), pack3(p["ta"]),
                       sets[p["tables"]], coef_off, plane_off, offs[i], ends[i])
             coef_off += blocks * 64
@@ -453,12 +543,18 @@ class ImagePrep:
             segs.append(s)
         seg = np.concatenate(segs) if segs else np.zeros((0, ops.JPEG_SEG), np.int64)
         S = seg.shape[0]
+        pseg = np.concatenate(psegs) if psegs else np.zeros((0, ops.JPEG_PSEG + 1), np.int64)
+        pseg = pseg[np.argsort(pseg[:, -1], kind="stable")]                # level by level; within a level image, scan, segment
+        level_counts = np.bincount(pseg[:, -1]).tolist() if len(pseg) else []
+        pseg = pseg[:, :ops.JPEG_PSEG]
+        P = pseg.shape[0]
+        nrec = B * ops.JPEG_IMG + S * ops.JPEG_SEG + P * ops.JPEG_PSEG
 
         slot = self._ring[self._next]
         self._next = (self._next + 1) % len(self._ring)
         if slot.done is not None:
             slot.done.synchronize()              # the slot's previous H2D copies have left the pinned buffers
-        slot.reserve_jpeg(n, B * ops.JPEG_IMG + S * ops.JPEG_SEG)
+        slot.reserve_jpeg(n, nrec)
         slot.reserve(0, B)
         raw = slot.raw.numpy()
         for i, f in enumerate(files):
@@ -472,20 +568,26 @@ class ImagePrep:
                 raw[o:o + _file_bytes(f).size] = _file_bytes(f)
         for t, k in sets.items():
             raw[tab_off + k * TB:tab_off + (k + 1) * TB] = np.frombuffer(t, np.uint8)
+        for t, k in pool.items():
+            raw[pool_off + k * HB:pool_off + (k + 1) * HB] = np.frombuffer(t, np.uint8)
+        for t, k in qsets.items():
+            raw[q_off + k * ops.JPEG_QSET:q_off + (k + 1) * ops.JPEG_QSET] = np.frombuffer(t, np.uint8)
         img_host = slot.rec[:B * ops.JPEG_IMG].view(B, ops.JPEG_IMG)
         seg_host = slot.rec[B * ops.JPEG_IMG:B * ops.JPEG_IMG + S * ops.JPEG_SEG].view(S, ops.JPEG_SEG)
+        pseg_host = slot.rec[nrec - P * ops.JPEG_PSEG:nrec].view(P, ops.JPEG_PSEG)
         img_host.numpy()[:] = img
         seg_host.numpy()[:] = seg
+        pseg_host.numpy()[:] = pseg
         desc = slot.desc[:B]
         if prep and B:
             desc.numpy()[:] = np.asarray(desc_rows, dtype=np.int64)
 
         with torch.cuda.device(self.device):
             raw_dev = torch.empty(max(n_data, ALIGN), dtype=torch.uint8, device=self.device)
-            rec_dev = torch.empty(max(B * ops.JPEG_IMG + S * ops.JPEG_SEG, 1), dtype=torch.int64, device=self.device)
+            rec_dev = torch.empty(max(nrec, 1), dtype=torch.int64, device=self.device)
             pix_dev = torch.empty(total, dtype=torch.uint8, device=self.device) if B else torch.zeros(total, dtype=torch.uint8, device=self.device)
             raw_dev[:n_data].copy_(slot.raw[:n_data], non_blocking=True)                # the files and the tables: one H2D
-            rec_dev[:B * ops.JPEG_IMG + S * ops.JPEG_SEG].copy_(slot.rec[:B * ops.JPEG_IMG + S * ops.JPEG_SEG], non_blocking=True)
+            rec_dev[:nrec].copy_(slot.rec[:nrec], non_blocking=True)
             for i in arrays:                                                             # fall-back images: their pixels, as pack stages them
                 pix_dev[offs[i]:ends[i]].copy_(slot.raw[fb_off[i]:fb_off[i] + ends[i] - offs[i]], non_blocking=True)
             if prep:
@@ -498,10 +600,21 @@ class ImagePrep:
             tables_dev = raw_dev[tab_off:tab_off + len(sets) * TB].view(len(sets), TB)
             batch = DecodedBatch(pix_dev, torch.tensor([(H, W) for W, H in sizes], dtype=torch.int64).reshape(B, 2),
                                  torch.tensor(offs, dtype=torch.int64))
+            if self.progressive:                 # the mixed decode: its further arguments
+                pseg_dev = rec_dev[nrec - P * ops.JPEG_PSEG:nrec].view(P, ops.JPEG_PSEG)
+                pool_dev = raw_dev[pool_off:pool_off + len(pool) * HB].view(len(pool), HB)
+                qsets_dev = raw_dev[q_off:q_off + len(qsets) * ops.JPEG_QSET].view(len(qsets), ops.JPEG_QSET)
             if staged_only:                      # (host records cloned: the slot is reused two batches later)
+                if self.progressive:
+                    return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pseg_host.clone(), pseg_dev, level_counts,
+                            pool_dev, qsets_dev, pix_dev), batch
                 return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pix_dev), batch
             try:
-                ops.jpeg_decode(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pix_dev)
+                if self.progressive:
+                    ops.jpeg_decode_progressive(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pseg_host, pseg_dev, level_counts,
+                                                pool_dev, qsets_dev, pix_dev)
+                else:
+                    ops.jpeg_decode(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pix_dev)
             except ops.JpegDecodeError as e:
                 e.batch = batch                  # every image the error does not name is decoded in it
                 raise
@@ -516,7 +629,8 @@ class ImagePrep:
         cross PCIe.  A file outside the decoder's scope (progressive, CMYK, ...: JPEG_REASONS) raises UnsupportedJpeg before any GPU
         work -- or, with fallback=callable, is decoded by the caller: fallback(file bytes) -> a [H,W,3] uint8 array, staged into the
         same pixel buffer.  A file whose scan is corrupt raises ops.JpegDecodeError (a ValueError) after the decode, naming the
-        image and the segment's status."""
+        image and the segment's status.  A prep built with progressive=True decodes progressive files as well, in any mix with
+        baseline ones; the error then names the scan too, and files of its further reasons are in JPEG_PROGRESSIVE_REASONS."""
         return self._jpeg_run(self._jpeg_headers(files, fallback))
 
     def warp_jpeg(self, files, fallback=None):

@@ -1764,15 +1764,50 @@ JPEG_MAX_GAP = 256        # bytes of padding behind an image that the decoder ze
 
 class JpegDecodeError(ValueError):
     """Some segments did not decode.  failed: [(image, segment, status word)], segment counted over the batch; pixels: the pixel
-    buffer -- every image not named in `failed` is decoded in it."""
+    buffer -- every image not named in `failed` is decoded in it.  scans: {segment: the scan's number in its file} for the segments
+    of progressive files (jpeg_decode_progressive counts the baseline segments first, then the progressive ones level by level)."""
 
-    def __init__(self, failed, pixels):
-        self.failed, self.pixels = failed, pixels
+    def __init__(self, failed, pixels, scans=None):
+        self.failed, self.pixels, self.scans = failed, pixels, dict(scans or {})
         by_image = {}
         for i, s, st in failed:
-            by_image.setdefault(i, []).append("segment %d: %s (status %d)" % (s, JPEG_STATUS.get(st, "?"), st))
+            where = "scan %d, segment %d" % (self.scans[s], s) if s in self.scans else "segment %d" % s
+            by_image.setdefault(i, []).append("%s: %s (status %d)" % (where, JPEG_STATUS.get(st, "?"), st))
         ValueError.__init__(self, "JPEG decode failed for %d image(s): %s" % (
             len(by_image), "; ".join("image %d: %s" % (i, ", ".join(v[:4]) + (" ..." if len(v) > 4 else "")) for i, v in sorted(by_image.items()))))
+
+
+def _jpeg_check_images(img, n_sets, n_q, pixels):
+    """The image records of a decode, checked on the host as the kernels check them.  n_q: latched quantisation sets of progressive
+    images (kind 2; 0 = none accepted).  -> (refuse, decoded mask, MCUs, blocks per image, workspace elements, plane bytes)"""
+    kind, W, H, nc, hs, vs, mcux, mcuy, tq, td, ta, tset, coef_off, plane_off, pix_off, pix_end = img.unbind(1)
+
+    def refuse(mask, what, rec=img, noun="image"):
+        if bool(mask.any()):
+            i = int(mask.nonzero()[0])
+            raise ValueError("%s %d: %s (record %s)" % (noun, i, what, rec[i].tolist()))
+
+    refuse((kind != 0) & (kind != 1) & ((kind != 2) | (n_q == 0)), "kind must be 0 or 1" if n_q == 0 else "kind must be 0, 1 or 2")
+    refuse((W < 1) | (W > IMAGE_MAX_EXTENT) | (H < 1) | (H > IMAGE_MAX_EXTENT), "extent outside 1..%d" % IMAGE_MAX_EXTENT)
+    refuse((pix_off < 0) | (pix_off % 16 != 0), "pixel offset is not a non-negative multiple of 16")
+    refuse((pix_end > pixels.numel()) | (pix_end - pix_off < W * H * 3) | (pix_end - pix_off - W * H * 3 > JPEG_MAX_GAP),
+           "pixels and their padding (at most %d bytes) do not fit the pixel buffer of %d bytes" % (JPEG_MAX_GAP, pixels.numel()))
+    dec, prog = kind != 0, kind == 2
+    sampling_ok = ((nc == 1) & (hs == 1) & (vs == 1)) | ((nc == 3) & (((hs == 1) & (vs == 1)) | ((hs == 2) & ((vs == 1) | (vs == 2)))))
+    refuse(dec & ~sampling_ok, "components / sampling not supported")
+    hs1, vs1 = hs.clamp(1, 2), vs.clamp(1, 2)
+    refuse(dec & ((mcux != (W + 8 * hs1 - 1) // (8 * hs1)) | (mcuy != (H + 8 * vs1 - 1) // (8 * vs1))), "MCU counts do not match the extent")
+    refuse(dec & ~prog & ((tset < 0) | (tset >= n_sets)), "table set outside 0..%d" % (n_sets - 1))
+    refuse(prog & ((tset < 0) | (tset >= n_q)), "quantisation set outside 0..%d" % (n_q - 1))
+    refuse(dec & ~prog & ((tq < 0) | (td < 0) | (ta < 0) | (((tq | td | ta) & ~0x030303) != 0)), "table ids must be 0..3")
+    nmcu = mcux * mcuy
+    blocks = torch.where(nc == 1, nmcu, nmcu * (hs * vs + 2)) * dec
+    refuse(dec & ((coef_off < 0) | (coef_off % 64 != 0) | (plane_off < 0) | (plane_off % 64 != 0)), "workspace offsets must be non-negative multiples of 64")
+    coef_elems = int((coef_off * dec + blocks * 64).max())
+    plane_bytes = int((plane_off * dec + blocks * 64).max())
+    if coef_elems > (1 << 34):
+        raise ValueError("the batch needs a coefficient workspace of %d int16 -- decode it in smaller batches" % coef_elems)
+    return refuse, dec, nmcu, blocks, coef_elems, plane_bytes
 
 
 def jpeg_tableset_bytes():
@@ -1810,37 +1845,13 @@ def jpeg_decode(data, img, img_dev, seg, seg_dev, tables, pixels, stages=7, chec
     status = torch.zeros(S, dtype=torch.int32, device=data.device)
     if B == 0 or S == 0:
         return status
-    kind, W, H, nc, hs, vs, mcux, mcuy, tq, td, ta, tset, coef_off, plane_off, pix_off, pix_end = img.unbind(1)
-
-    def refuse(mask, what, rec=img, noun="image"):
-        if bool(mask.any()):
-            i = int(mask.nonzero()[0])
-            raise ValueError("%s %d: %s (record %s)" % (noun, i, what, rec[i].tolist()))
-
-    refuse((kind != 0) & (kind != 1), "kind must be 0 or 1")
-    refuse((W < 1) | (W > IMAGE_MAX_EXTENT) | (H < 1) | (H > IMAGE_MAX_EXTENT), "extent outside 1..%d" % IMAGE_MAX_EXTENT)
-    refuse((pix_off < 0) | (pix_off % 16 != 0), "pixel offset is not a non-negative multiple of 16")
-    refuse((pix_end > pixels.numel()) | (pix_end - pix_off < W * H * 3) | (pix_end - pix_off - W * H * 3 > JPEG_MAX_GAP),
-           "pixels and their padding (at most %d bytes) do not fit the pixel buffer of %d bytes" % (JPEG_MAX_GAP, pixels.numel()))
-    dec = kind == 1
-    sampling_ok = ((nc == 1) & (hs == 1) & (vs == 1)) | ((nc == 3) & (((hs == 1) & (vs == 1)) | ((hs == 2) & ((vs == 1) | (vs == 2)))))
-    refuse(dec & ~sampling_ok, "components / sampling not supported")
-    hs1, vs1 = hs.clamp(1, 2), vs.clamp(1, 2)
-    refuse(dec & ((mcux != (W + 8 * hs1 - 1) // (8 * hs1)) | (mcuy != (H + 8 * vs1 - 1) // (8 * vs1))), "MCU counts do not match the extent")
-    refuse(dec & ((tset < 0) | (tset >= n_sets)), "table set outside 0..%d" % (n_sets - 1))
-    refuse(dec & ((tq < 0) | (td < 0) | (ta < 0) | (((tq | td | ta) & ~0x030303) != 0)), "table ids must be 0..3")
-    nmcu = mcux * mcuy
-    blocks = torch.where(nc == 1, nmcu, nmcu * (hs * vs + 2)) * dec
-    refuse(dec & ((coef_off < 0) | (coef_off % 64 != 0) | (plane_off < 0) | (plane_off % 64 != 0)), "workspace offsets must be non-negative multiples of 64")
-    coef_elems = int((coef_off * dec + blocks * 64).max())
-    plane_bytes = int((plane_off * dec + blocks * 64).max())
+    refuse, dec, nmcu, blocks, coef_elems, plane_bytes = _jpeg_check_images(img, n_sets, 0, pixels)
+    W, H = img[:, 1], img[:, 2]
     si, sb, se, m0, mn = seg.unbind(1)
     refuse((si < 0) | (si >= B), "image index outside the batch", seg, "segment")
     refuse(~dec[si], "segment of an image that is not decoded", seg, "segment")
     refuse((sb < 0) | (sb > se) | (se > data.numel()), "byte range outside the data buffer of %d bytes" % data.numel(), seg, "segment")
     refuse((m0 < 0) | (mn < 1) | (m0 > nmcu[si] - mn), "MCU range outside the image", seg, "segment")
-    if coef_elems > (1 << 34):
-        raise ValueError("the batch needs a coefficient workspace of %d int16 -- decode it in smaller batches" % coef_elems)
     coef = torch.empty(max(coef_elems, 64), dtype=torch.int16, device=data.device)
     planes = torch.empty(max(plane_bytes, 64), dtype=torch.uint8, device=data.device)
     _launch("mgnns_jpeg_decode_fwd", _p(data), data.numel(), _p(img_dev), B, _p(seg_dev), S, _p(tables), n_sets, _p(coef), coef.numel(),
@@ -1851,6 +1862,99 @@ def jpeg_decode(data, img, img_dev, seg, seg_dev, tables, pixels, stages=7, chec
         bad = st.nonzero().flatten().tolist()
         if bad:
             raise JpegDecodeError([(int(si[s]), s, int(st[s])) for s in bad], pixels)
+    return status
+
+
+JPEG_PSEG = 12            # int64 per segment of a progressive scan: image, begin, end, first unit, units, component mask, Ss, Se, Ah, Al,
+#                           pool indices (16 bits each: DC of component 0, 1, 2, AC; 0xFFFF = none), the scan's number in its file
+JPEG_QSET = 192           # bytes of one latched quantisation set: [3][64], a table per component in natural order
+JPEG_MAX_LEVELS = 64
+
+
+def jpeg_huff_bytes():
+    return int(_lib.lib().mgnns_jpeg_huff_bytes())
+
+
+def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=7, check=True):
+    """Decode a batch that may mix baseline and progressive files into `pixels` (include/mgnns_jpeg_progressive.h): the workspace zeroed, jpeg_decode's entropy kernel over the baseline segments, one launch of the progressive entropy
+    kernel per level, then the IDCT and colour kernels over all images -- on the current stream.  As jpeg_decode, and: an image of
+    kind 2 is progressive (its table-set field counts `qsets`); pseg [P,12] int64 HOST tensor sorted by level, pseg_dev its device
+    copy; level_counts: segments per level (a list); pool: uint8 [n_pool, jpeg_huff_bytes()] and qsets: uint8 [n_q, 192] on the
+    GPU; stages: jpeg_decode's mask (1 = every entropy launch).  -> the status tensor [S + P]: the baseline segments' words, then the
+    progressive ones' in pseg's order."""
+    _chk(data, "data", torch.uint8, 1)
+    _chk(pixels, "pixels", torch.uint8, 1)
+    _chk(tables, "tables", torch.uint8, 2)
+    _chk(pool, "pool", torch.uint8, 2)
+    _chk(qsets, "qsets", torch.uint8, 2)
+    _chk_host(img, "img", torch.int64, JPEG_IMG)
+    _chk_host(seg, "seg", torch.int64, JPEG_SEG)
+    _chk_host(pseg, "pseg", torch.int64, JPEG_PSEG)
+    _chk(img_dev, "img_dev", torch.int64, 2)
+    _chk(seg_dev, "seg_dev", torch.int64, 2)
+    _chk(pseg_dev, "pseg_dev", torch.int64, 2)
+    B, S, P, n_sets, n_pool, n_q = img.shape[0], seg.shape[0], pseg.shape[0], tables.shape[0], pool.shape[0], qsets.shape[0]
+    for host, dev, name in ((img, img_dev, "img_dev"), (seg, seg_dev, "seg_dev"), (pseg, pseg_dev, "pseg_dev")):
+        if tuple(dev.shape) != tuple(host.shape):
+            raise ValueError("%s %s must have the shape of its host copy %s" % (name, tuple(dev.shape), tuple(host.shape)))
+    if tables.shape[1] != jpeg_tableset_bytes() or pool.shape[1] != jpeg_huff_bytes() or qsets.shape[1] != JPEG_QSET:
+        raise ValueError("tables must be [n_sets,%d], pool [n_pool,%d], qsets [n_q,%d], got %s, %s, %s" % (
+            jpeg_tableset_bytes(), jpeg_huff_bytes(), JPEG_QSET, tuple(tables.shape), tuple(pool.shape), tuple(qsets.shape)))
+    for t, name in ((img_dev, "img_dev"), (seg_dev, "seg_dev"), (pseg_dev, "pseg_dev"), (tables, "tables"), (pool, "pool"), (qsets, "qsets"),
+                    (pixels, "pixels")):
+        if t.device != data.device:
+            raise ValueError("%s is on %s, data on %s" % (name, t.device, data.device))
+    if B > 65535:
+        raise ValueError("at most 65535 images per batch, got %d" % B)
+    level_counts = [int(v) for v in level_counts]
+    if len(level_counts) > JPEG_MAX_LEVELS or any(v < 0 for v in level_counts) or sum(level_counts) != P:
+        raise ValueError("level_counts must be at most %d non-negative counts that add up to the %d progressive segments, got %s"
+                         % (JPEG_MAX_LEVELS, P, level_counts))
+    if n_pool >= 0xFFFF:
+        raise ValueError("at most 65534 tables in the pool, got %d" % n_pool)
+    if int(stages) < 1 or int(stages) > 7:
+        raise ValueError("stages is a mask of 1 (entropy), 2 (IDCT), 4 (colour), got %s" % (stages,))
+    status = torch.zeros(S + P, dtype=torch.int32, device=data.device)
+    if B == 0 or S + P == 0:
+        return status
+    refuse, dec, nmcu, blocks, coef_elems, plane_bytes = _jpeg_check_images(img, n_sets, n_q, pixels)
+    kind, W, H, nc, hs, vs, mcux = (img[:, k] for k in range(7))
+    si, sb, se, m0, mn = seg.unbind(1)
+    refuse((si < 0) | (si >= B), "image index outside the batch", seg, "segment")
+    refuse(kind[si] != 1, "baseline segment of an image that is not a baseline file", seg, "segment")
+    refuse((sb < 0) | (sb > se) | (se > data.numel()), "byte range outside the data buffer of %d bytes" % data.numel(), seg, "segment")
+    refuse((m0 < 0) | (mn < 1) | (m0 > nmcu[si] - mn), "MCU range outside the image", seg, "segment")
+    pi, pb, pe, u0, un, comps, ss, se_, ah, al, tabs, _ = pseg.unbind(1)
+    noun = "progressive segment"
+    refuse((pi < 0) | (pi >= B), "image index outside the batch", pseg, noun)
+    refuse(kind[pi] != 2, "segment of an image that is not a progressive file", pseg, noun)
+    refuse((pb < 0) | (pb > pe) | (pe > data.numel()), "byte range outside the data buffer of %d bytes" % data.numel(), pseg, noun)
+    refuse((comps < 1) | (comps > torch.where(nc[pi] == 1, 1, 7)), "component mask outside the frame", pseg, noun)
+    single = (comps == 1) | (comps == 2) | (comps == 4)
+    refuse(torch.where(ss == 0, se_ != 0, (ss < 1) | (se_ < ss) | (se_ > 63) | ~single), "Ss / Se are no band of a progressive scan", pseg, noun)
+    refuse((al < 0) | (al > 13) | ((ah != 0) & (ah != al + 1)), "Ah / Al are no successive approximation", pseg, noun)
+    hp, vp, Wp, Hp = hs[pi], vs[pi], W[pi], H[pi]
+    hc, vc = torch.where(comps == 1, hp, 1), torch.where(comps == 1, vp, 1)
+    units = torch.where(single, ((((Wp * hc + hp - 1) // hp) + 7) // 8) * ((((Hp * vc + vp - 1) // vp) + 7) // 8), nmcu[pi])
+    refuse((u0 < 0) | (un < 1) | (u0 > units - un), "unit range outside the scan", pseg, noun)
+    t4 = torch.stack([(tabs >> (16 * k)) & 0xFFFF for k in range(4)], 1)
+    refuse(((t4 != 0xFFFF) & (t4 >= n_pool)).any(1), "table outside the pool of %d" % n_pool, pseg, noun)
+    need = torch.stack([(ss == 0) & (ah == 0) & ((comps >> c) & 1 == 1) for c in range(3)] + [ss != 0], 1)
+    refuse((need & (t4 == 0xFFFF)).any(1), "the scan reads a table the record does not name", pseg, noun)
+    lv = torch.tensor(level_counts, dtype=torch.int32)
+    coef = torch.empty(max(coef_elems, 64), dtype=torch.int16, device=data.device)
+    planes = torch.empty(max(plane_bytes, 64), dtype=torch.uint8, device=data.device)
+    _launch("mgnns_jpeg_decode_progressive_fwd", _p(data), data.numel(), _p(img_dev), B, _p(seg_dev) if S else None, S,
+            _p(tables) if n_sets else None, n_sets, _p(pseg_dev) if P else None, lv.data_ptr() if len(level_counts) else None, len(level_counts),
+            _p(pool) if n_pool else None, n_pool, _p(qsets) if n_q else None, n_q, _p(coef), coef.numel(), _p(planes), planes.numel(),
+            _p(pixels), pixels.numel(), max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1), int(stages), _p(status), _stream(),
+            key=(B, S, tuple(level_counts)))
+    if check:
+        st = status.cpu()                      # one small D2H on the current stream; it also ends the workspaces' use
+        bad = st.nonzero().flatten().tolist()
+        if bad:
+            raise JpegDecodeError([(int(si[s]) if s < S else int(pi[s - S]), s, int(st[s])) for s in bad], pixels,
+                                  {s: int(pseg[s - S, 11]) for s in bad if s >= S})
     return status
 
 

@@ -8,7 +8,11 @@ images/s, the bytes that cross PCIe (files + tables + records) against the raw-p
 a batch), Pillow's own decode time per image on this host, and the two trunks' eval forward (ResNet-101 + ResNet-50 at 448) for the
 same 256 images in the same process: the yardstick a decode launched beside them should stay under.  One JSON line.
 
-    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks]
+--progressive adds, per size, the same photographs saved as progressive files and decoded by ImagePrep(progressive=True): the whole
+decode, the entropy stage as a whole and level by level (the entropy stage with the levels after l left out, minus the same with l
+left out too), IDCT and colour, and Pillow's time for those files; the baseline leg runs in the same process as before.
+
+    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks] [--progressive]
 """
 import glob
 import io
@@ -52,12 +56,12 @@ def photograph(w, h, seed):
     return np.clip(base + rs.normal(0.0, 12.0, size=(h, w, 3)), 0, 255).astype(np.uint8)
 
 
-def encode(w, h, B, restart_rows):
+def encode(w, h, B, restart_rows, progressive=False):
     from PIL import Image
     distinct = []
     for k in range(8):
         buf = io.BytesIO()
-        opts = dict(quality=90, subsampling=2)
+        opts = dict(quality=90, subsampling=2, progressive=progressive)
         if restart_rows:
             opts["restart_marker_rows"] = restart_rows
         Image.fromarray(photograph(w, h, k)).save(buf, "JPEG", **opts)
@@ -105,6 +109,55 @@ def case(prep, files, n):
     return res, t
 
 
+def case_progressive(prep, files, n):
+    """the --progressive leg: the method of case(), on ops.jpeg_decode_progressive"""
+    B = len(files)
+    t0 = time.perf_counter()
+    headers = prep._jpeg_headers(files, None)
+    t1 = time.perf_counter()
+    args, batch = prep._jpeg_run(headers, staged_only=True)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, counts, pool, qsets, pixels = args
+    run = lambda stages=7: ops.jpeg_decode_progressive(*args, stages=stages, check=False)
+    assert not bool(run().any())
+    first = batch.pixels.clone()
+
+    def upto(l):                                 # the entropy stage with the levels after l left out (l = -1: the zeroing alone)
+        k = sum(counts[:l + 1])
+        return lambda: ops.jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg[:k], pseg_dev[:k], counts[:l + 1], pool, qsets,
+                                                   pixels, stages=1, check=False)
+
+    fns = {"whole": run, "entropy": lambda: run(1), "idct": lambda: run(2), "colour": lambda: run(4)}
+    fns.update({"upto%d" % l: upto(l) for l in range(-1, len(counts))})
+    once = timeit(run, 2, warm=0)
+    if once * n > 4e6:
+        n = max(10, int(4e6 / once))
+    ts = {k: [] for k in fns}
+    for _ in range(3):
+        for k, fn in fns.items():
+            ts[k].append(timeit(fn, n))
+    run()
+    assert torch.equal(batch.pixels, first)
+    best = {k: min(v) for k, v in ts.items()}
+    t = best["whole"]
+    res = {"B": B, "iters_used": n, "us": round(t, 1), "images_per_s": round(B / t * 1e6),
+           "stage_us": {k: round(best[k], 1) for k in ("entropy", "idct", "colour")}, "zeroing_us": round(best["upto-1"], 1),
+           "level_us": [round(best["upto%d" % l] - best["upto%d" % (l - 1)], 1) for l in range(len(counts))], "level_segments": list(counts),
+           "tables_in_pool": int(pool.shape[0]), "file_MB": round(sum(len(f) for f in files) / 1e6, 2),
+           "host_parse_ms": round((t1 - t0) * 1e3, 2), "host_stage_ms": round((t2 - t1) * 1e3, 2), "runs_us": [round(v, 1) for v in ts["whole"]]}
+    try:
+        from PIL import Image
+        t0 = time.perf_counter()
+        for f in files[:64]:
+            Image.open(io.BytesIO(f)).convert("RGB")
+        res["pillow_ms_per_image"] = round((time.perf_counter() - t0) / min(64, B) * 1e3, 3)
+        assert torch.equal(batch.image(0).cpu(), torch.from_numpy(np.asarray(Image.open(io.BytesIO(files[0])).convert("RGB"))))
+    except ImportError:
+        pass
+    return res, t
+
+
 def main():
     B, n, rr = arg("--batch", 256), arg("--iters", 100), arg("--restart-rows", 0)
     built = _lib.check_sources("tools/bench_jpeg.py")
@@ -119,6 +172,9 @@ def main():
     else:
         for name, (w, h) in (("500x375", (500, 375)), ("1024x768", (1024, 768))):
             res[name], times[name] = case(prep, encode(w, h, B, rr), n)
+            if "--progressive" in sys.argv:
+                key = name + "_progressive"
+                res[key], times[key] = case_progressive(ImagePrep(448, device=DEV, progressive=True), encode(w, h, B, rr, True), n)
     if "--no-trunks" not in sys.argv:
         obj = trunk.ResNetFeatures(synth.fill_trunk_(trunk.resnet101(), 1)).to(DEV).eval()
         place = trunk.ResNetFeatures(synth.fill_trunk_(trunk.resnet50(365), 2)).to(DEV).eval()
