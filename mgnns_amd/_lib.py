@@ -16,6 +16,8 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "mgnns_hip.h")
 # Extension headers: entry points added without an ABI bump are declared beside mgnns_hip.h, which stays the surface of the ABI as it
 # stood.  They are parsed by the same rules into tables of their own (EXTENSION_SIGNATURES / EXTENSION_SIZE_GETTERS).
 EXTENSION_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_progressive.h"),)
+# ... and so are the headers added after those tables were pinned down: tables of their own again (SPLIT_SIGNATURES).
+SPLIT_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_split.h"),)
 
 
 class MgnnsLibraryError(RuntimeError):
@@ -106,6 +108,9 @@ def _read_extensions(paths, base):
 _EXT_DECLS = _read_extensions(EXTENSION_HEADERS, _DECLS)
 EXTENSION_SIGNATURES = {n: a for n, (r, a) in _EXT_DECLS.items() if r is ctypes.c_int}
 EXTENSION_SIZE_GETTERS = {n: a for n, (r, a) in _EXT_DECLS.items() if r is ctypes.c_size_t}
+_SPLIT_DECLS = _read_extensions(SPLIT_HEADERS, {**_DECLS, **_EXT_DECLS})
+SPLIT_SIGNATURES = {n: a for n, (r, a) in _SPLIT_DECLS.items() if r is ctypes.c_int}
+SPLIT_SIZE_GETTERS = {n: a for n, (r, a) in _SPLIT_DECLS.items() if r is ctypes.c_size_t}
 
 _lib = None
 _bound = {}          # name -> bound function: call() does no getattr on the CDLL per launch
@@ -113,7 +118,7 @@ _bound = {}          # name -> bound function: call() does no getattr on the CDL
 
 def _bind(L, name):
     fn = getattr(L, name)          # AttributeError if the symbol is missing
-    fn.restype, fn.argtypes = _DECLS[name] if name in _DECLS else _EXT_DECLS[name]
+    fn.restype, fn.argtypes = _DECLS[name] if name in _DECLS else _EXT_DECLS[name] if name in _EXT_DECLS else _SPLIT_DECLS[name]
 
 
 def lib():
@@ -130,7 +135,7 @@ def lib():
         _bind(L, name)
     if L.mgnns_abi_version() != ABI_VERSION:
         raise MgnnsLibraryError("libmgnns_hip.so ABI %d != binding ABI %d; rebuild" % (L.mgnns_abi_version(), ABI_VERSION))
-    for name in list(_DECLS) + list(_EXT_DECLS):
+    for name in list(_DECLS) + list(_EXT_DECLS) + list(_SPLIT_DECLS):
         _bind(L, name)
     _lib = L
     _register_status_word(L)

@@ -16,11 +16,17 @@
 // and 3.  Their entropy stage is jpeg_progressive_kernel (jpeg_progressive.hpp), one lane per segment of one SCAN, launched once
 // per LEVEL of the batch: scans of one level touch different (component, coefficient) pairs, so their lanes write different int16
 // elements of a block and need neither atomics nor a fence; the stream orders the levels.
+//
+// Split scans (mgnns_jpeg_decode_split_fwd, DESIGN.md 17, "Split scans"): a long baseline segment -- a restart-free scan is one --
+// gets a WORKGROUP of jpeg_split_kernel, a lane per chunk of its bytes (jpeg_split.hpp), and the serial decoder's result byte for
+// byte; jpeg_entropy_kernel decodes the short ones, one lane each, in the same status array.
 #include "common.hpp"
 #include "../../include/mgnns_jpeg_progressive.h"
+#include "../../include/mgnns_jpeg_split.h"
 #include "jpeg_parse.hpp"
 #include "jpeg_pixels.hpp"
 #include "jpeg_progressive.hpp"
+#include "jpeg_split.hpp"
 
 namespace {
 
@@ -33,6 +39,11 @@ constexpr int NT = 256;
 constexpr int IDCT_BLOCKS = NT / 8;
 constexpr int ENT_NT = 64;      // the entropy kernel's workgroup: one wave, of which the first `lanes` lanes decode a segment each
 constexpr int LDS_SETS = 2;     // table sets kept in LDS (11 648 bytes each)
+#ifndef MG_JPEG_SPLIT_LANES     // (an instrumented build for the sweep of DESIGN.md 17: MGNNS_HIPCC_FLAGS=-DMG_JPEG_SPLIT_LANES=256)
+#define MG_JPEG_SPLIT_LANES 512
+#endif
+constexpr int SPLIT_NT = MG_JPEG_SPLIT_LANES;   // lanes of the split kernel's workgroup; a multiple of 64 up to MG_JPEG_SPLIT_MAX_LANES
+static_assert(SPLIT_NT % 64 == 0 && SPLIT_NT <= MG_JPEG_SPLIT_MAX_LANES, "whole waves, one lane per LDS record");
 static_assert(sizeof(MgJpegTables) % 16 == 0, "table sets are copied 16 bytes at a time");
 
 struct Img {
@@ -73,11 +84,17 @@ __device__ __forceinline__ bool load_img(const int64_t* __restrict__ r, int n_se
     return true;
 }
 
+// Which of the two baseline entropy kernels decodes the segment of bytes [b, e): the split kernel takes a record whose byte range is
+// sound and long enough (jpeg_split.hpp); every other one -- a bad range too, which is status 4 -- is the one-lane kernel's.
+__device__ __forceinline__ bool split_takes(long long b, long long e, size_t data_bytes, int split_chunk) {
+    return b >= 0 && b <= e && (unsigned long long)e <= data_bytes && mg_jpeg_split_takes(e - b, split_chunk);
+}
+
 __global__ __launch_bounds__(ENT_NT) void jpeg_entropy_kernel(const uint8_t* __restrict__ data, size_t data_bytes,
                                     const int64_t* __restrict__ img, int B, const int64_t* __restrict__ seg, int S, int lanes,
                                     const MgJpegTables* __restrict__ tables, int n_sets,
                                     int16_t* __restrict__ coef, size_t coef_elems, size_t plane_bytes, size_t pixel_bytes,
-                                    int32_t* __restrict__ status) {
+                                    int32_t* __restrict__ status, int split_chunk) {
     // The batch's first LDS_SETS table sets -- nearly always all of them -- are copied into LDS: the look-up of a symbol is the one
     // load every trip of the loop waits for, and it depends on the bits just read.  A lane of another set reads global memory.
     __shared__ __attribute__((aligned(16))) MgJpegTables s_tables[LDS_SETS];
@@ -92,6 +109,7 @@ __global__ __launch_bounds__(ENT_NT) void jpeg_entropy_kernel(const uint8_t* __r
     if ((int)threadIdx.x >= lanes || s >= S) return;
     const int64_t* const r = seg + s * SEG;
     const long long im = r[0], b = r[1], e = r[2], mcu0 = r[3], nmcu = r[4];
+    if (split_takes(b, e, data_bytes, split_chunk)) return;      // jpeg_split_kernel's (split_chunk = 0: none)
     Img m;
     int st = MG_JPEG_SEG_BAD_RECORD;
     if (im >= 0 && im < B && b >= 0 && b <= e && (unsigned long long)e <= data_bytes && mcu0 >= 0 && nmcu >= 1 &&
@@ -107,6 +125,113 @@ __global__ __launch_bounds__(ENT_NT) void jpeg_entropy_kernel(const uint8_t* __r
         st = mg_jpeg_decode_segment(data + b, data + e, T, g, c0, c1, c2);
     }
     status[s] = st;
+}
+
+// Inclusive prefix sum over the wave's 64 lanes.
+__device__ __forceinline__ uint32_t wave_prefix(uint32_t v) {
+    const int l = (int)(threadIdx.x & 63);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, 64);
+        if (l >= d) v += o;
+    }
+    return v;
+}
+
+// One WORKGROUP per baseline segment record the routing gives it (the others return at once), a lane per chunk: the four steps of
+// jpeg_split.hpp through LDS and workgroup barriers -- no flag in global memory, no wait on another workgroup.  Every barrier is
+// reached by the whole workgroup: what a lane skips is its walk, never a barrier, and the synchronisation loop's trip count comes
+// from the barrier's own OR, so it is uniform.  It is bounded by the number of chunks.
+__global__ __launch_bounds__(SPLIT_NT) void jpeg_split_kernel(const uint8_t* __restrict__ data, size_t data_bytes,
+                                    const int64_t* __restrict__ img, int B, const int64_t* __restrict__ seg, int S,
+                                    const MgJpegTables* __restrict__ tables, int n_sets,
+                                    int16_t* __restrict__ coef, size_t coef_elems, size_t plane_bytes, size_t pixel_bytes,
+                                    int32_t* __restrict__ status, int split_chunk) {
+    __shared__ __attribute__((aligned(16))) MgJpegTables s_tables[LDS_SETS];
+    __shared__ uint64_t s_exit[SPLIT_NT];                 // a lane's exit state: the next lane's entry
+    __shared__ uint32_t s_wave[5][SPLIT_NT / 64];         // the waves' totals of the carry step
+    __shared__ int s_status;
+    const long long s = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    if (s >= S) return;
+    const int64_t* const r = seg + s * SEG;
+    const long long im = r[0], b = r[1], e = r[2], mcu0 = r[3], nmcu = r[4];
+    if (!split_takes(b, e, data_bytes, split_chunk)) return;     // jpeg_entropy_kernel's (uniform over the workgroup)
+    {
+        const int n16 = (n_sets < LDS_SETS ? n_sets : LDS_SETS) * (int)(sizeof(MgJpegTables) / 16);
+        const u32x4* const src = reinterpret_cast<const u32x4*>(tables);
+        u32x4* const dst = reinterpret_cast<u32x4*>(s_tables);
+        for (int i = lane; i < n16; i += SPLIT_NT) dst[i] = src[i];
+    }
+    if (lane == 0) s_status = 0x7fffffff;
+    Img m;
+    if (!(im >= 0 && im < B && mcu0 >= 0 && nmcu >= 1 && load_img(img + im * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) &&
+          m.kind == 1 && mcu0 <= m.nmcu - nmcu)) {               // (uniform: every lane read the same record)
+        if (lane == 0) status[s] = MG_JPEG_SEG_BAD_RECORD;
+        return;
+    }
+    MgJpegSegment g;
+    g.ncomp = m.ncomp, g.hs = m.hs, g.vs = m.vs, g.mcux = m.mcux, g.mcu_total = (int)m.nmcu, g.mcu0 = (int)mcu0, g.nmcu = (int)nmcu;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g.td[c] = m.td[c], g.ta[c] = m.ta[c];
+    int16_t* const c0 = coef + m.coef_off;
+    int16_t* const c1 = c0 + m.blocks0 * 64;
+    int16_t* const c2 = c1 + m.nmcu * 64;
+    const MgJpegTables* const T = m.set < LDS_SETS ? &s_tables[m.set] : tables + m.set;
+    const uint8_t* const p = data + b, * const end = data + e;
+    const MgJpegSplit sp = mg_jpeg_split_geometry(reinterpret_cast<uintptr_t>(p), e - b, split_chunk, SPLIT_NT);
+    const int n = sp.chunks;                                     // 2..SPLIT_NT
+    const bool active = lane < n;
+    __syncthreads();                                             // the tables are in LDS
+
+    // 1. speculate
+    MgJpegWalk w;
+    uint64_t entry = MG_JPEG_STATE_INVALID;
+    w.exit = MG_JPEG_STATE_INVALID, w.blocks = 0, w.failed = 0, w.dc[0] = w.dc[1] = w.dc[2] = 0;
+    w.limit = active ? sp.end(lane) : 0;
+    if (active) {
+        entry = lane == 0 ? mg_jpeg_state(0, 0, 0) : mg_jpeg_split_guess(p, sp, lane, 0, 0);
+        w.entry = entry;
+        mg_jpeg_walk<MG_JPEG_WALK_SCAN>(p, end, T, g, nullptr, nullptr, nullptr, &w);
+    }
+    s_exit[lane] = w.exit;
+    __syncthreads();
+    // 2. synchronise
+    for (int round = 0; round < n; ++round) {
+        const uint64_t in = active && lane > 0 ? s_exit[lane - 1] : entry;
+        __syncthreads();                                         // every exit is read before one is replaced
+        int changed = 0;
+        if (in != entry) {
+            const uint64_t before = w.exit;
+            w.entry = entry = in;
+            mg_jpeg_walk<MG_JPEG_WALK_SCAN>(p, end, T, g, nullptr, nullptr, nullptr, &w);
+            s_exit[lane] = w.exit;
+            changed = w.exit != before;
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+    // 3. carry: exclusive prefix sums over the lanes
+    uint32_t own[5] = {w.blocks, w.failed, w.dc[0], w.dc[1], w.dc[2]}, sum[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        sum[i] = wave_prefix(own[i]);
+        if ((lane & 63) == 63) s_wave[i][lane >> 6] = sum[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        uint32_t before = 0;
+        for (int j = 0; j < (lane >> 6); ++j) before += s_wave[i][j];
+        sum[i] += before - own[i];
+    }
+    // 4. write
+    if (active && entry != MG_JPEG_STATE_INVALID && sum[1] == 0) {
+        w.block0 = sum[0], w.dc[0] = sum[2], w.dc[1] = sum[3], w.dc[2] = sum[4];
+        const int st = mg_jpeg_walk<MG_JPEG_WALK_WRITE>(p, end, T, g, c0, c1, c2, &w);
+        if (st != MG_JPEG_SEG_OK) atomicMin(&s_status, (lane << 3) | st);        // the lowest lane's
+    }
+    __syncthreads();
+    if (lane == 0) status[s] = s_status == 0x7fffffff ? MG_JPEG_SEG_OK : (s_status & 7);
 }
 
 // One lane per segment of a progressive scan, segments [first, first + count) of pseg: one level of the batch.  A record:
@@ -259,7 +384,7 @@ extern "C" int mgnns_jpeg_decode_fwd(const void* data, size_t data_bytes, const 
         while (lanes < 64 && (long long)lanes * 4 * cus < S) lanes *= 2;
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((S + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
                            data_bytes, img, B, seg, S, lanes, (const MgJpegTables*)tables, n_sets, (int16_t*)coef, coef_elems, plane_bytes,
-                           pixel_bytes, status);
+                           pixel_bytes, status, 0);
         MG_CHECK_LAUNCH("mgnns_jpeg_decode_fwd (entropy)");
     }
     if (stages & 2) {
@@ -286,36 +411,47 @@ extern "C" int mgnns_jpeg_parse_progressive(const void* data, size_t bytes, int 
     return 0;
 }
 
-extern "C" int mgnns_jpeg_decode_progressive_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
-                                                 const void* tables, int n_sets, const int64_t* pseg, const int32_t* level_counts, int n_levels,
-                                                 const void* pool, int n_pool, const void* qsets, int n_q, void* coef, size_t coef_elems,
-                                                 void* planes, size_t plane_bytes, void* pixels, size_t pixel_bytes, long long max_blocks,
-                                                 long long max_pixels, int stages, int32_t* status, mgnns_stream_t stream) {
-    MG_REQUIRE(stages >= 1 && stages <= 7, "mgnns_jpeg_decode_progressive_fwd: stages=%d is no mask of 1 (entropy), 2 (IDCT), 4 (colour)", stages);
-    MG_REQUIRE(B >= 0 && B <= 65535 && S >= 0 && n_levels >= 0 && n_levels <= 64, "mgnns_jpeg_decode_progressive_fwd: B=%d (0..65535), S=%d, n_levels=%d (0..64)",
+// The launch sequence of a batch that may mix baseline and progressive files, for mgnns_jpeg_decode_progressive_fwd (split_chunk = 0)
+// and mgnns_jpeg_decode_split_fwd: zero the workspace; the baseline segments -- with split_chunk, jpeg_split_kernel over the
+// segments mg_jpeg_split_takes takes and jpeg_entropy_kernel over the others, each skipping the other's; the progressive levels;
+// IDCT; colour.  `who` names the entry point in error messages.
+#define MG_JPEG_LAUNCHED(stage)                                  \
+    do {                                                         \
+        char where_[96];                                         \
+        snprintf(where_, sizeof where_, "%s (" stage ")", who);  \
+        MG_CHECK_LAUNCH(where_);                                 \
+    } while (0)
+
+static int jpeg_decode_batch(const char* who, int split_chunk, const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg,
+                             int S, const void* tables, int n_sets, const int64_t* pseg, const int32_t* level_counts, int n_levels,
+                             const void* pool, int n_pool, const void* qsets, int n_q, void* coef, size_t coef_elems, void* planes,
+                             size_t plane_bytes, void* pixels, size_t pixel_bytes, long long max_blocks, long long max_pixels, int stages,
+                             int32_t* status, mgnns_stream_t stream) {
+    MG_REQUIRE(stages >= 1 && stages <= 7, "%s: stages=%d is no mask of 1 (entropy), 2 (IDCT), 4 (colour)", who, stages);
+    MG_REQUIRE(B >= 0 && B <= 65535 && S >= 0 && n_levels >= 0 && n_levels <= 64, "%s: B=%d (0..65535), S=%d, n_levels=%d (0..64)", who,
                B, S, n_levels);
-    MG_REQUIRE(n_sets >= 0 && n_pool >= 0 && n_q >= 0, "mgnns_jpeg_decode_progressive_fwd: n_sets=%d, n_pool=%d, n_q=%d", n_sets, n_pool, n_q);
-    MG_REQUIRE(n_levels == 0 || level_counts, "mgnns_jpeg_decode_progressive_fwd: null level_counts");
+    MG_REQUIRE(n_sets >= 0 && n_pool >= 0 && n_q >= 0, "%s: n_sets=%d, n_pool=%d, n_q=%d", who, n_sets, n_pool, n_q);
+    MG_REQUIRE(n_levels == 0 || level_counts, "%s: null level_counts", who);
     long long P = 0;
     for (int l = 0; l < n_levels; ++l) {
-        MG_REQUIRE(level_counts[l] >= 0, "mgnns_jpeg_decode_progressive_fwd: level_counts[%d]=%d", l, level_counts[l]);
+        MG_REQUIRE(level_counts[l] >= 0, "%s: level_counts[%d]=%d", who, l, level_counts[l]);
         P += level_counts[l];
     }
-    MG_REQUIRE(S + P <= 0x7fffffffLL, "mgnns_jpeg_decode_progressive_fwd: %lld segments", S + P);
+    MG_REQUIRE(S + P <= 0x7fffffffLL, "%s: %lld segments", who, S + P);
     if (B == 0 || S + P == 0) return 0;            // nothing to decode (every image staged by the host, or none at all)
-    MG_REQUIRE(data && img && coef && planes && pixels && status, "mgnns_jpeg_decode_progressive_fwd: null pointer");
-    MG_REQUIRE(S == 0 || (seg && tables && n_sets >= 1), "mgnns_jpeg_decode_progressive_fwd: baseline segments without a table set");
+    MG_REQUIRE(data && img && coef && planes && pixels && status, "%s: null pointer", who);
+    MG_REQUIRE(S == 0 || (seg && tables && n_sets >= 1), "%s: baseline segments without a table set", who);
     MG_REQUIRE(P == 0 || (pseg && pool && n_pool >= 1 && n_pool < 0xFFFF && qsets && n_q >= 1),
-               "mgnns_jpeg_decode_progressive_fwd: progressive segments without a table pool or quantisation sets");
+               "%s: progressive segments without a table pool or quantisation sets", who);
     MG_REQUIRE(mg_aligned16(coef) && mg_aligned16(planes) && mg_aligned16(pixels) && mg_aligned16(tables) && mg_aligned16(pool),
-               "mgnns_jpeg_decode_progressive_fwd: coef, planes, pixels, tables and pool must be 16-byte aligned");
+               "%s: coef, planes, pixels, tables and pool must be 16-byte aligned", who);
     MG_REQUIRE(max_blocks >= 1 && max_blocks <= 6LL * (MAXEXT / 8) * (MAXEXT / 8) && max_pixels >= 1 && max_pixels <= (long long)MAXEXT * MAXEXT,
-               "mgnns_jpeg_decode_progressive_fwd: max_blocks=%lld, max_pixels=%lld", max_blocks, max_pixels);
+               "%s: max_blocks=%lld, max_pixels=%lld", who, max_blocks, max_pixels);
     hipStream_t st = (hipStream_t)stream;
     if (stages & 1) {
         hipError_t e = hipMemsetAsync(coef, 0, coef_elems * sizeof(int16_t), st);
         if (e != hipSuccess) {
-            mgnns_set_error("mgnns_jpeg_decode_progressive_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
+            mgnns_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
             return MGNNS_ERR_LAUNCH;
         }
     }
@@ -326,12 +462,17 @@ extern "C" int mgnns_jpeg_decode_progressive_fwd(const void* data, size_t data_b
         while (lanes < 64 && (long long)lanes * 4 * cus < n) lanes *= 2;
         return lanes;
     };
+    if ((stages & 1) && S > 0 && split_chunk > 0) {
+        hipLaunchKernelGGL(jpeg_split_kernel, dim3((unsigned)S), dim3(SPLIT_NT), 0, st, (const uint8_t*)data, data_bytes, img, B, seg, S,
+                           (const MgJpegTables*)tables, n_sets, (int16_t*)coef, coef_elems, plane_bytes, pixel_bytes, status, split_chunk);
+        MG_JPEG_LAUNCHED("split entropy");
+    }
     if ((stages & 1) && S > 0) {
         const int lanes = lanes_for(S);
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((S + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
                            data_bytes, img, B, seg, S, lanes, (const MgJpegTables*)tables, n_sets, (int16_t*)coef, coef_elems, plane_bytes,
-                           pixel_bytes, status);
-        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (baseline entropy)");
+                           pixel_bytes, status, split_chunk);
+        MG_JPEG_LAUNCHED("baseline entropy");
     }
     int first = 0;
     for (int l = 0; (stages & 1) && l < n_levels; ++l) {
@@ -341,19 +482,44 @@ extern "C" int mgnns_jpeg_decode_progressive_fwd(const void* data, size_t data_b
         hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)((count + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
                            data_bytes, img, B, pseg, first, count, lanes, (const MgJpegHuff*)pool, n_pool, n_sets, n_q, (int16_t*)coef, coef_elems,
                            plane_bytes, pixel_bytes, status + S);
-        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (progressive entropy)");
+        MG_JPEG_LAUNCHED("progressive entropy");
         first += count;
     }
     if (stages & 2) {
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)B), dim3(NT), 0, st, img,
                            (const MgJpegTables*)tables, n_sets, (const int16_t*)coef, coef_elems, (uint8_t*)planes, plane_bytes, pixel_bytes,
                            (const uint8_t*)qsets, n_q);
-        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (idct)");
+        MG_JPEG_LAUNCHED("idct");
     }
     if (stages & 4) {
         hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((max_pixels + NT - 1) / NT), (unsigned)B), dim3(NT), 0, st, img, n_sets, coef_elems,
                            (const uint8_t*)planes, plane_bytes, (uint8_t*)pixels, pixel_bytes, n_q);
-        MG_CHECK_LAUNCH("mgnns_jpeg_decode_progressive_fwd (colour)");
+        MG_JPEG_LAUNCHED("colour");
     }
     return 0;
+}
+
+#undef MG_JPEG_LAUNCHED
+
+extern "C" int mgnns_jpeg_decode_progressive_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
+                                                 const void* tables, int n_sets, const int64_t* pseg, const int32_t* level_counts, int n_levels,
+                                                 const void* pool, int n_pool, const void* qsets, int n_q, void* coef, size_t coef_elems,
+                                                 void* planes, size_t plane_bytes, void* pixels, size_t pixel_bytes, long long max_blocks,
+                                                 long long max_pixels, int stages, int32_t* status, mgnns_stream_t stream) {
+    return jpeg_decode_batch("mgnns_jpeg_decode_progressive_fwd", 0, data, data_bytes, img, B, seg, S, tables, n_sets, pseg, level_counts, n_levels,
+                             pool, n_pool, qsets, n_q, coef, coef_elems, planes, plane_bytes, pixels, pixel_bytes, max_blocks, max_pixels, stages,
+                             status, stream);
+}
+
+extern "C" int mgnns_jpeg_decode_split_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
+                                           const void* tables, int n_sets, const int64_t* pseg, const int32_t* level_counts, int n_levels,
+                                           const void* pool, int n_pool, const void* qsets, int n_q, void* coef, size_t coef_elems, void* planes,
+                                           size_t plane_bytes, void* pixels, size_t pixel_bytes, long long max_blocks, long long max_pixels,
+                                           int stages, int32_t* status, mgnns_stream_t stream, int chunk_bytes) {
+    MG_REQUIRE(chunk_bytes >= MG_JPEG_SPLIT_MIN_CHUNK && chunk_bytes <= MG_JPEG_SPLIT_MAX_CHUNK && chunk_bytes % 8 == 0,
+               "mgnns_jpeg_decode_split_fwd: chunk_bytes=%d is no multiple of 8 in %d..%d", chunk_bytes, MG_JPEG_SPLIT_MIN_CHUNK,
+               MG_JPEG_SPLIT_MAX_CHUNK);
+    return jpeg_decode_batch("mgnns_jpeg_decode_split_fwd", chunk_bytes, data, data_bytes, img, B, seg, S, tables, n_sets, pseg, level_counts,
+                             n_levels, pool, n_pool, qsets, n_q, coef, coef_elems, planes, plane_bytes, pixels, pixel_bytes, max_blocks, max_pixels,
+                             stages, status, stream);
 }

@@ -14,7 +14,9 @@ run its passes in the other order (seen at 1000x7 -> 16 and 1000x8 -> 16) and th
 An image is a [H,W,3] uint8 array, or anything with __array_interface__ (a PIL image in mode RGB) -- or the bytes of a baseline JPEG
 file, which decode_jpeg / warp_jpeg / train_jpeg decode on the GPU to exactly Pillow's pixels (csrc/jpeg_decode.hip):
 the host only parses the markers.  ImagePrep(..., progressive=True) decodes progressive (SOF2) files as well (csrc/jpeg_progressive.hpp);
-the switch is off by default, and a progressive file is then refused with reason 3 as before.  This module does not import PIL."""
+the switch is off by default, and a progressive file is then refused with reason 3 as before.  ImagePrep(..., split=True) decodes a
+long baseline scan -- a file without restart markers is one -- on many lanes instead of one, to the same pixels (csrc/jpeg_split.hpp;
+DESIGN.md 17, "Split scans"); off by default as well.  This module does not import PIL."""
 import math
 import random
 
@@ -265,9 +267,22 @@ class Packed:
         self.pixels, self.desc, self.slot = pixels, desc, slot
 
 
+def split_chunk(split):
+    """ImagePrep's `split` argument -> the chunk size in bytes: 0 / False is off, True the default chunk (ops.JPEG_SPLIT_CHUNK), an
+    integer a chunk size -- a multiple of 8 in 8..65536."""
+    if split is None or split is False or (not isinstance(split, bool) and isinstance(split, int) and split == 0):
+        return 0
+    if split is True:
+        return ops.JPEG_SPLIT_CHUNK
+    if not isinstance(split, int) or split < 8 or split > 65536 or split % 8:
+        raise ValueError("split must be False / 0 (off), True (chunks of %d bytes) or a chunk size, a multiple of 8 in 8..65536; got %r"
+                         % (ops.JPEG_SPLIT_CHUNK, split))
+    return split
+
+
 class ImagePrep:
     def __init__(self, size=448, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device=None, scales=SCALES,
-                 max_distort=MAX_DISTORT, ring=2, progressive=False):
+                 max_distort=MAX_DISTORT, ring=2, progressive=False, split=0):
         size = int(size)
         if not 1 <= size <= ops.IMAGE_MAX_SIZE:
             raise ValueError("size must be in 1..%d, got %d" % (ops.IMAGE_MAX_SIZE, size))
@@ -279,6 +294,7 @@ class ImagePrep:
             raise ValueError("the pinned ring needs at least two batches, got %d" % ring)
         self.size = size
         self.progressive = bool(progressive)         # decode_jpeg / warp_jpeg / train_jpeg also decode progressive (SOF2) files
+        self.split = split_chunk(split)              # ... and decode long baseline scans on many lanes, in chunks of so many bytes (0: off)
         self.scales, self.max_distort = tuple(scales), int(max_distort)
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
@@ -457,7 +473,8 @@ class ImagePrep:
         """Stage one batch of parsed files into the next slot of the pinned ring -- the files' bytes, the distinct table sets, the
         image and segment records, the pixels of fall-back images -- copy them over and decode.  With prep=True the descriptors of
         (crops, flips) follow and image_prep runs on the decoded buffer.  -> DecodedBatch, or the [B,3,size,size] tensor.
-        staged_only=True stops before the decode and returns (ops.jpeg_decode's arguments, DecodedBatch): tools/bench_jpeg.py."""
+        staged_only=True stops before the decode and returns (ops.jpeg_decode's arguments, DecodedBatch): tools/bench_jpeg.py
+        (with progressive or split: ops.jpeg_decode_progressive's, which are ops.jpeg_decode_split's)."""
         if self.device is None:
             raise RuntimeError("ImagePrep was built without a device: JPEG files are decoded on the GPU only (no CPU path)")
         files, parsed, arrays, sizes = headers
@@ -479,7 +496,8 @@ class ImagePrep:
                 desc_rows.append((offs[i], H, W, cx, cy, cw, ch, 1 if (flips is not None and bool(flips[i])) else 0, self.plan(cw), self.plan(ch)))
         # layout of the raw buffer: the accepted files at 16-byte starts, the table sets, then the fall-back images' pixels
         TB = ops.jpeg_tableset_bytes()
-        HB = ops.jpeg_huff_bytes() if self.progressive else 0
+        mixed = self.progressive or self.split > 0          # the decode that takes the progressive arguments (empty with split alone)
+        HB = ops.jpeg_huff_bytes() if mixed else 0
         raw_off, n, sets, pool, qsets = {}, 0, {}, {}, {}
         for i, f in enumerate(files):
             if i not in arrays:
@@ -600,17 +618,20 @@ class ImagePrep:
             tables_dev = raw_dev[tab_off:tab_off + len(sets) * TB].view(len(sets), TB)
             batch = DecodedBatch(pix_dev, torch.tensor([(H, W) for W, H in sizes], dtype=torch.int64).reshape(B, 2),
                                  torch.tensor(offs, dtype=torch.int64))
-            if self.progressive:                 # the mixed decode: its further arguments
+            if mixed:                            # the mixed decode: its further arguments
                 pseg_dev = rec_dev[nrec - P * ops.JPEG_PSEG:nrec].view(P, ops.JPEG_PSEG)
                 pool_dev = raw_dev[pool_off:pool_off + len(pool) * HB].view(len(pool), HB)
                 qsets_dev = raw_dev[q_off:q_off + len(qsets) * ops.JPEG_QSET].view(len(qsets), ops.JPEG_QSET)
             if staged_only:                      # (host records cloned: the slot is reused two batches later)
-                if self.progressive:
+                if mixed:
                     return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pseg_host.clone(), pseg_dev, level_counts,
                             pool_dev, qsets_dev, pix_dev), batch
                 return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pix_dev), batch
             try:
-                if self.progressive:
+                if self.split:
+                    ops.jpeg_decode_split(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pseg_host, pseg_dev, level_counts,
+                                          pool_dev, qsets_dev, pix_dev, chunk_bytes=self.split)
+                elif self.progressive:
                     ops.jpeg_decode_progressive(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pseg_host, pseg_dev, level_counts,
                                                 pool_dev, qsets_dev, pix_dev)
                 else:

@@ -1875,7 +1875,8 @@ def jpeg_huff_bytes():
     return int(_lib.lib().mgnns_jpeg_huff_bytes())
 
 
-def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=7, check=True):
+def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=7, check=True,
+                            _split=0):
     """Decode a batch that may mix baseline and progressive files into `pixels` (include/mgnns_jpeg_progressive.h): the workspace zeroed, jpeg_decode's entropy kernel over the baseline segments, one launch of the progressive entropy
     kernel per level, then the IDCT and colour kernels over all images -- on the current stream.  As jpeg_decode, and: an image of
     kind 2 is progressive (its table-set field counts `qsets`); pseg [P,12] int64 HOST tensor sorted by level, pseg_dev its device
@@ -1944,11 +1945,13 @@ def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg
     lv = torch.tensor(level_counts, dtype=torch.int32)
     coef = torch.empty(max(coef_elems, 64), dtype=torch.int16, device=data.device)
     planes = torch.empty(max(plane_bytes, 64), dtype=torch.uint8, device=data.device)
-    _launch("mgnns_jpeg_decode_progressive_fwd", _p(data), data.numel(), _p(img_dev), B, _p(seg_dev) if S else None, S,
+    # (_split: jpeg_decode_split's chunk size -- the same arguments and one more, to the entry point of include/mgnns_jpeg_split.h)
+    _launch("mgnns_jpeg_decode_split_fwd" if _split else "mgnns_jpeg_decode_progressive_fwd", _p(data), data.numel(), _p(img_dev), B,
+            _p(seg_dev) if S else None, S,
             _p(tables) if n_sets else None, n_sets, _p(pseg_dev) if P else None, lv.data_ptr() if len(level_counts) else None, len(level_counts),
             _p(pool) if n_pool else None, n_pool, _p(qsets) if n_q else None, n_q, _p(coef), coef.numel(), _p(planes), planes.numel(),
             _p(pixels), pixels.numel(), max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1), int(stages), _p(status), _stream(),
-            key=(B, S, tuple(level_counts)))
+            *((int(_split),) if _split else ()), key=(B, S, tuple(level_counts)))
     if check:
         st = status.cpu()                      # one small D2H on the current stream; it also ends the workspaces' use
         bad = st.nonzero().flatten().tolist()
@@ -1956,6 +1959,21 @@ def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg
             raise JpegDecodeError([(int(si[s]) if s < S else int(pi[s - S]), s, int(st[s])) for s in bad], pixels,
                                   {s: int(pseg[s - S, 11]) for s in bad if s >= S})
     return status
+
+
+JPEG_SPLIT_CHUNK = 128    # the default chunk of a split scan, in bytes ("Split scans": the sweep)
+
+
+def jpeg_decode_split(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, chunk_bytes=JPEG_SPLIT_CHUNK,
+                      stages=7, check=True):
+    """jpeg_decode_progressive with long baseline segments -- a restart-free scan is one -- decoded by a workgroup each, a lane per
+    chunk of `chunk_bytes` bytes (a multiple of 8 in 8..65536; include/mgnns_jpeg_split.h, DESIGN.md 17 "Split scans").  The same
+    arguments, validation, workspaces, status tensor and JpegDecodeError, and the same bytes in `pixels`: only the time differs.
+    The progressive arguments may be empty (pseg [0,12], no levels, pool [0,n], qsets [0,192])."""
+    if isinstance(chunk_bytes, bool) or not isinstance(chunk_bytes, int) or chunk_bytes < 8 or chunk_bytes > 65536 or chunk_bytes % 8:
+        raise ValueError("chunk_bytes must be a multiple of 8 in 8..65536, got %r" % (chunk_bytes,))
+    return jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=stages,
+                                   check=check, _split=chunk_bytes)
 
 
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------

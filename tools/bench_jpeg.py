@@ -12,7 +12,11 @@ same 256 images in the same process: the yardstick a decode launched beside them
 decode, the entropy stage as a whole and level by level (the entropy stage with the levels after l left out, minus the same with l
 left out too), IDCT and colour, and Pillow's time for those files; the baseline leg runs in the same process as before.
 
-    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks] [--progressive]
+--split [CHUNK] adds, per size, the same baseline files decoded by ImagePrep(split=CHUNK) (ops.jpeg_decode_split; without a number
+the default chunk): the whole decode and the stages by the same method, the segments the split kernel took, and the pixel buffer
+compared with the switch-off leg's.
+
+    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks] [--progressive] [--split [CHUNK]]
 """
 import glob
 import io
@@ -158,6 +162,33 @@ def case_progressive(prep, files, n):
     return res, t
 
 
+def case_split(prep, files, n, want):
+    """the --split leg: the method of case(), on ops.jpeg_decode_split; `want`: the switch-off leg's pixel buffer"""
+    B = len(files)
+    args, batch = prep._jpeg_run(prep._jpeg_headers(files, None), staged_only=True)
+    torch.cuda.synchronize()
+    run = lambda stages=7: ops.jpeg_decode_split(*args, chunk_bytes=prep.split, stages=stages, check=False)
+    assert not bool(run().any())
+    assert torch.equal(batch.pixels, want)
+    fns = {"whole": run, "entropy": lambda: run(1), "idct": lambda: run(2), "colour": lambda: run(4)}
+    once = timeit(run, 2, warm=0)
+    if once * n > 4e6:
+        n = max(10, int(4e6 / once))
+    ts = {k: [] for k in fns}
+    for _ in range(3):
+        for k, fn in fns.items():
+            ts[k].append(timeit(fn, n))
+    run()
+    assert torch.equal(batch.pixels, want)
+    best = {k: min(v) for k, v in ts.items()}
+    seg = args[3]
+    taken = int(((seg[:, 2] - seg[:, 1]) >= 2 * prep.split).sum())
+    res = {"B": B, "chunk_bytes": prep.split, "iters_used": n, "us": round(best["whole"], 1), "images_per_s": round(B / best["whole"] * 1e6),
+           "stage_us": {k: round(best[k], 1) for k in ("entropy", "idct", "colour")}, "segments": int(seg.shape[0]), "segments_split": taken,
+           "runs_us": [round(v, 1) for v in ts["whole"]]}
+    return res, best["whole"]
+
+
 def main():
     B, n, rr = arg("--batch", 256), arg("--iters", 100), arg("--restart-rows", 0)
     built = _lib.check_sources("tools/bench_jpeg.py")
@@ -171,7 +202,14 @@ def main():
         res["files"], times["files"] = case(prep, files, n)
     else:
         for name, (w, h) in (("500x375", (500, 375)), ("1024x768", (1024, 768))):
-            res[name], times[name] = case(prep, encode(w, h, B, rr), n)
+            files = encode(w, h, B, rr)
+            res[name], times[name] = case(prep, files, n)
+            if "--split" in sys.argv:
+                at = sys.argv.index("--split") + 1
+                chunk = int(sys.argv[at]) if at < len(sys.argv) and sys.argv[at].isdigit() else True
+                want = prep.decode_jpeg(files).pixels
+                key = name + "_split"
+                res[key], times[key] = case_split(ImagePrep(448, device=DEV, split=chunk), files, n, want)
             if "--progressive" in sys.argv:
                 key = name + "_progressive"
                 res[key], times[key] = case_progressive(ImagePrep(448, device=DEV, progressive=True), encode(w, h, B, rr, True), n)
