@@ -18,6 +18,8 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "mgnns_hip.h")
 EXTENSION_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_progressive.h"),)
 # ... and so are the headers added after those tables were pinned down: tables of their own again (SPLIT_SIGNATURES).
 SPLIT_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_split.h"),)
+# ... and the JPEG files of other component layouts (LAYOUT_SIGNATURES)
+LAYOUT_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_layouts.h"),)
 
 
 class MgnnsLibraryError(RuntimeError):
@@ -111,6 +113,9 @@ EXTENSION_SIZE_GETTERS = {n: a for n, (r, a) in _EXT_DECLS.items() if r is ctype
 _SPLIT_DECLS = _read_extensions(SPLIT_HEADERS, {**_DECLS, **_EXT_DECLS})
 SPLIT_SIGNATURES = {n: a for n, (r, a) in _SPLIT_DECLS.items() if r is ctypes.c_int}
 SPLIT_SIZE_GETTERS = {n: a for n, (r, a) in _SPLIT_DECLS.items() if r is ctypes.c_size_t}
+_LAYOUT_DECLS = _read_extensions(LAYOUT_HEADERS, {**_DECLS, **_EXT_DECLS, **_SPLIT_DECLS})
+LAYOUT_SIGNATURES = {n: a for n, (r, a) in _LAYOUT_DECLS.items() if r is ctypes.c_int}
+LAYOUT_SIZE_GETTERS = {n: a for n, (r, a) in _LAYOUT_DECLS.items() if r is ctypes.c_size_t}
 
 _lib = None
 _bound = {}          # name -> bound function: call() does no getattr on the CDLL per launch
@@ -118,7 +123,11 @@ _bound = {}          # name -> bound function: call() does no getattr on the CDL
 
 def _bind(L, name):
     fn = getattr(L, name)          # AttributeError if the symbol is missing
-    fn.restype, fn.argtypes = _DECLS[name] if name in _DECLS else _EXT_DECLS[name] if name in _EXT_DECLS else _SPLIT_DECLS[name]
+    for decls in (_DECLS, _EXT_DECLS, _SPLIT_DECLS, _LAYOUT_DECLS):
+        if name in decls:
+            fn.restype, fn.argtypes = decls[name]
+            return
+    raise MgnnsLibraryError("no header declares %s" % name)
 
 
 def lib():
@@ -135,7 +144,7 @@ def lib():
         _bind(L, name)
     if L.mgnns_abi_version() != ABI_VERSION:
         raise MgnnsLibraryError("libmgnns_hip.so ABI %d != binding ABI %d; rebuild" % (L.mgnns_abi_version(), ABI_VERSION))
-    for name in list(_DECLS) + list(_EXT_DECLS) + list(_SPLIT_DECLS):
+    for name in list(_DECLS) + list(_EXT_DECLS) + list(_SPLIT_DECLS) + list(_LAYOUT_DECLS):
         _bind(L, name)
     _lib = L
     _register_status_word(L)

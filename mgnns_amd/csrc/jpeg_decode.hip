@@ -23,10 +23,12 @@
 #include "common.hpp"
 #include "../../include/mgnns_jpeg_progressive.h"
 #include "../../include/mgnns_jpeg_split.h"
+#include "../../include/mgnns_jpeg_layouts.h"
 #include "jpeg_parse.hpp"
 #include "jpeg_pixels.hpp"
 #include "jpeg_progressive.hpp"
 #include "jpeg_split.hpp"
+#include "jpeg_layouts.hpp"
 
 namespace {
 
@@ -343,6 +345,166 @@ __global__ __launch_bounds__(NT) void jpeg_colour_kernel(const int64_t* __restri
     o[2] = rgb[2];
 }
 
+// ---- other component layouts (jpeg_layouts.hpp; DESIGN.md 17, "Other component layouts") -----------------------------------------
+// An image record of kind 3, with a check of its own: load_img and the kernels above do not know the kind and skip the record.
+struct LImg {
+    int W, H, ncomp, model, mcux, mcuy, set, hmax, vmax;
+    uint32_t h, v, tq, td, ta;            // h, v: a nibble per component; the table ids: a byte per component in the record, 0..3
+    long long coef_off, plane_off, pix_off, pix_end;
+    long long nmcu, blocks;               // MCUs; blocks of all components
+    long long nb0, nb1, nb2, nb3;         // blocks per component, 0 for one the image does not have
+};
+
+__device__ __forceinline__ bool load_layout_img(const int64_t* __restrict__ r, int n_sets, size_t coef_elems, size_t plane_bytes,
+                                                size_t pixel_bytes, LImg& m) {
+    const long long kind = r[0], W = r[1], H = r[2], nm = r[3], hp = r[4], vp = r[5], mcux = r[6], mcuy = r[7], set = r[11];
+    m.coef_off = r[12], m.plane_off = r[13], m.pix_off = r[14], m.pix_end = r[15];
+    if (kind != 3) return false;
+    if (W < 1 || W > MAXEXT || H < 1 || H > MAXEXT) return false;
+    if (m.pix_off < 0 || (m.pix_off & 15) || m.pix_end < m.pix_off || (unsigned long long)m.pix_end > pixel_bytes ||
+        W * H * 3 > m.pix_end - m.pix_off)
+        return false;
+    const long long nc = nm & 0xFF, model = nm >> 8;
+    if (nm < 0 || hp < 0 || hp > 0xFFFF || vp < 0 || vp > 0xFFFF) return false;
+    const int bpm = mg_jpeg_layout_mcu_blocks((int)nc, (uint32_t)hp, (uint32_t)vp);
+    if (bpm == 0) return false;
+    if (!((nc == 1 && model == MG_JPEG_MODEL_GRAY) || (nc == 3 && (model == MG_JPEG_MODEL_YCC || model == MG_JPEG_MODEL_RGB)) ||
+          (nc == 4 && (model == MG_JPEG_MODEL_CMYK || model == MG_JPEG_MODEL_YCCK))))
+        return false;
+    m.W = (int)W, m.H = (int)H, m.ncomp = (int)nc, m.model = (int)model, m.h = (uint32_t)hp, m.v = (uint32_t)vp;
+    m.hmax = m.vmax = 1;
+    long long nb[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < m.ncomp) {
+            const int hc = mg_jpeg_nibble(m.h, c), vc = mg_jpeg_nibble(m.v, c);
+            m.hmax = hc > m.hmax ? hc : m.hmax, m.vmax = vc > m.vmax ? vc : m.vmax;
+            nb[c] = (long long)hc * vc;
+        }
+    if (mcux != (W + 8 * m.hmax - 1) / (8 * m.hmax) || mcuy != (H + 8 * m.vmax - 1) / (8 * m.vmax)) return false;
+    if (set < 0 || set >= n_sets) return false;
+    m.mcux = (int)mcux, m.mcuy = (int)mcuy, m.set = (int)set;
+    m.nmcu = mcux * mcuy;
+    m.nb0 = nb[0] * m.nmcu, m.nb1 = nb[1] * m.nmcu, m.nb2 = nb[2] * m.nmcu, m.nb3 = nb[3] * m.nmcu;
+    m.blocks = m.nmcu * bpm;
+    if (m.coef_off < 0 || (m.coef_off & 63) || (unsigned long long)m.coef_off + (unsigned long long)m.blocks * 64 > coef_elems) return false;
+    if (m.plane_off < 0 || (m.plane_off & 63) || (unsigned long long)m.plane_off + (unsigned long long)m.blocks * 64 > plane_bytes) return false;
+    m.tq = m.td = m.ta = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        m.tq |= (uint32_t)((r[8] >> (8 * c)) & 3) << (2 * c);
+        m.td |= (uint32_t)((r[9] >> (8 * c)) & 3) << (2 * c);
+        m.ta |= (uint32_t)((r[10] >> (8 * c)) & 3) << (2 * c);
+    }
+    return true;
+}
+
+// One lane per segment record of lseg, placed as jpeg_entropy_kernel places its lanes, with the batch's first table sets in LDS.
+// A segment is one lane's from its first byte to its last: these segments are never split.
+__global__ __launch_bounds__(ENT_NT) void jpeg_layout_entropy_kernel(const uint8_t* __restrict__ data, size_t data_bytes,
+                                    const int64_t* __restrict__ img, int B, const int64_t* __restrict__ seg, int S, int lanes,
+                                    const MgJpegTables* __restrict__ tables, int n_sets,
+                                    int16_t* __restrict__ coef, size_t coef_elems, size_t plane_bytes, size_t pixel_bytes,
+                                    int32_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) MgJpegTables s_tables[LDS_SETS];
+    {
+        const int n16 = (n_sets < LDS_SETS ? n_sets : LDS_SETS) * (int)(sizeof(MgJpegTables) / 16);
+        const u32x4* const src = reinterpret_cast<const u32x4*>(tables);
+        u32x4* const dst = reinterpret_cast<u32x4*>(s_tables);
+        for (int i = threadIdx.x; i < n16; i += ENT_NT) dst[i] = src[i];
+    }
+    __syncthreads();
+    const long long s = (long long)blockIdx.x * lanes + threadIdx.x;
+    if ((int)threadIdx.x >= lanes || s >= S) return;
+    const int64_t* const r = seg + s * SEG;
+    const long long im = r[0], b = r[1], e = r[2], mcu0 = r[3], nmcu = r[4];
+    LImg m;
+    int st = MG_JPEG_SEG_BAD_RECORD;
+    if (im >= 0 && im < B && b >= 0 && b <= e && (unsigned long long)e <= data_bytes && mcu0 >= 0 && nmcu >= 1 &&
+        load_layout_img(img + im * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m) && mcu0 <= m.nmcu - nmcu) {
+        MgJpegLayoutSegment g;
+        g.ncomp = m.ncomp, g.h = m.h, g.v = m.v, g.td = m.td, g.ta = m.ta;
+        g.mcux = m.mcux, g.mcu_total = (int)m.nmcu, g.mcu0 = (int)mcu0, g.nmcu = (int)nmcu;
+        int16_t* const c0 = coef + m.coef_off;
+        int16_t* const c1 = c0 + m.nb0 * 64;
+        int16_t* const c2 = c1 + m.nb1 * 64;
+        int16_t* const c3 = c2 + m.nb2 * 64;
+        const MgJpegTables* const T = m.set < LDS_SETS ? &s_tables[m.set] : tables + m.set;
+        st = mg_jpeg_decode_layout_segment(data + b, data + e, T, g, c0, c1, c2, c3);
+    }
+    status[s] = st;
+}
+
+// jpeg_idct_kernel over the images of kind 3: component c's blocks lie behind those of component c - 1, mcux h_c to a block row
+__global__ __launch_bounds__(NT) void jpeg_layout_idct_kernel(const int64_t* __restrict__ img, const MgJpegTables* __restrict__ tables, int n_sets,
+                                                              const int16_t* __restrict__ coef, size_t coef_elems, uint8_t* __restrict__ planes,
+                                                              size_t plane_bytes, size_t pixel_bytes) {
+    __shared__ int32_t s_ws[IDCT_BLOCKS][8][9];
+    LImg m;
+    const bool ok = load_layout_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m);   // (block-uniform)
+    if (!ok || (long long)blockIdx.x * IDCT_BLOCKS >= m.blocks) return;
+    const int lb = threadIdx.x >> 3, t = threadIdx.x & 7;
+    const long long gb = (long long)blockIdx.x * IDCT_BLOCKS + lb;
+    const bool live = gb < m.blocks;
+    const int c = gb < m.nb0 ? 0 : (gb < m.nb0 + m.nb1 ? 1 : (gb < m.nb0 + m.nb1 + m.nb2 ? 2 : 3));
+    if (live) {
+        int32_t ws[8];
+        mg_jpeg_idct_column(coef + m.coef_off + gb * 64, tables[m.set].quant[(m.tq >> (2 * c)) & 3u], t, ws);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) s_ws[lb][r][t] = ws[r];
+    }
+    __syncthreads();
+    if (live) {
+        int32_t ws[8];
+#pragma unroll
+        for (int x = 0; x < 8; ++x) ws[x] = s_ws[lb][t][x];
+        union {
+            uint8_t b[8];
+            uint2 v;
+        } o;
+        mg_jpeg_idct_row(ws, o.b);
+        const long long first = c == 0 ? 0 : (c == 1 ? m.nb0 : (c == 2 ? m.nb0 + m.nb1 : m.nb0 + m.nb1 + m.nb2));
+        const long long bi = gb - first;
+        const int bw = m.mcux * mg_jpeg_nibble(m.h, c);
+        const long long by = bi / bw, bx = bi - by * bw;
+        // 8 bytes at a multiple of 8: plane offsets are multiples of 64, the pitch 8 bw
+        *reinterpret_cast<uint2*>(planes + m.plane_off + first * 64 + (by * 8 + t) * (8LL * bw) + bx * 8) = o.v;
+    }
+}
+
+// One thread per pixel of an image of kind 3: every component upsampled to the largest, the colour model, RGB8 at the image's
+// offset; the padding behind the image is zeroed.
+__global__ __launch_bounds__(NT) void jpeg_layout_colour_kernel(const int64_t* __restrict__ img, int n_sets, size_t coef_elems,
+                                                                const uint8_t* __restrict__ planes, size_t plane_bytes,
+                                                                uint8_t* __restrict__ pixels, size_t pixel_bytes) {
+    LImg m;
+    if (!load_layout_img(img + (size_t)blockIdx.y * IMG, n_sets, coef_elems, plane_bytes, pixel_bytes, m)) return;
+    const long long npix = (long long)m.W * m.H, p = (long long)blockIdx.x * NT + threadIdx.x;
+    if (blockIdx.x == 0) {                              // the padding up to the next image's start (behind the last: the slack too)
+        const long long z = m.pix_off + npix * 3 + threadIdx.x;
+        if (z < m.pix_end) pixels[z] = 0;               // (NT bytes at most: ops.jpeg_decode_layouts refuses a longer gap)
+    }
+    if (p >= npix) return;
+    const int y = (int)(p / m.W), x = (int)(p - (long long)y * m.W);
+    const uint8_t* plane = planes + m.plane_off;
+    const long long nb[4] = {m.nb0, m.nb1, m.nb2, m.nb3};
+    int s[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < m.ncomp) {
+            const int hc = mg_jpeg_nibble(m.h, c), vc = mg_jpeg_nibble(m.v, c);
+            const int dw = (m.W * hc + m.hmax - 1) / m.hmax, dh = (m.H * vc + m.vmax - 1) / m.vmax;
+            s[c] = mg_jpeg_layout_sample(plane, 8 * m.mcux * hc, dw, dh, m.hmax / hc, m.vmax / vc, x, y);
+            plane += nb[c] * 64;
+        }
+    uint8_t rgb[3];
+    mg_jpeg_layout_rgb(m.model, s[0], s[1], s[2], s[3], rgb);
+    uint8_t* const o = pixels + m.pix_off + p * 3;
+    o[0] = rgb[0];
+    o[1] = rgb[1];
+    o[2] = rgb[2];
+}
+
 }  // namespace
 
 extern "C" size_t mgnns_jpeg_tableset_bytes(void) { return sizeof(MgJpegTables); }
@@ -522,4 +684,67 @@ extern "C" int mgnns_jpeg_decode_split_fwd(const void* data, size_t data_bytes, 
     return jpeg_decode_batch("mgnns_jpeg_decode_split_fwd", chunk_bytes, data, data_bytes, img, B, seg, S, tables, n_sets, pseg, level_counts,
                              n_levels, pool, n_pool, qsets, n_q, coef, coef_elems, planes, plane_bytes, pixels, pixel_bytes, max_blocks, max_pixels,
                              stages, status, stream);
+}
+
+extern "C" int mgnns_jpeg_parse_layout(const void* data, size_t bytes, int max_extent, int32_t* info, int64_t* range, int64_t* seg,
+                                       size_t seg_cap, void* tables) {
+    MG_REQUIRE(info && range && tables && (seg || seg_cap == 0) && (data || bytes == 0), "mgnns_jpeg_parse_layout: null pointer");
+    MG_REQUIRE(max_extent >= 1 && max_extent <= MAXEXT, "mgnns_jpeg_parse_layout: max_extent=%d (1..%d)", max_extent, MAXEXT);
+    static const uint8_t none = 0;
+    mg_jpeg_parse_layout(data ? (const uint8_t*)data : &none, bytes, max_extent, info, range, seg, seg_cap, (MgJpegTables*)tables);
+    return 0;
+}
+
+extern "C" int mgnns_jpeg_decode_layouts_fwd(const void* data, size_t data_bytes, const int64_t* img, int B, const int64_t* seg, int S,
+                                             const void* tables, int n_sets, const int64_t* pseg, const int32_t* level_counts, int n_levels,
+                                             const void* pool, int n_pool, const void* qsets, int n_q, const int64_t* lseg, int L, void* coef,
+                                             size_t coef_elems, void* planes, size_t plane_bytes, void* pixels, size_t pixel_bytes,
+                                             long long max_blocks, long long max_pixels, long long lmax_blocks, long long lmax_pixels,
+                                             int stages, int32_t* status, mgnns_stream_t stream, int chunk_bytes) {
+    const char* const who = "mgnns_jpeg_decode_layouts_fwd";
+    MG_REQUIRE(chunk_bytes == 0 || (chunk_bytes >= MG_JPEG_SPLIT_MIN_CHUNK && chunk_bytes <= MG_JPEG_SPLIT_MAX_CHUNK && chunk_bytes % 8 == 0),
+               "%s: chunk_bytes=%d is neither 0 nor a multiple of 8 in %d..%d", who, chunk_bytes, MG_JPEG_SPLIT_MIN_CHUNK, MG_JPEG_SPLIT_MAX_CHUNK);
+    MG_REQUIRE(L >= 0 && S >= 0 && n_levels >= 0, "%s: L=%d, S=%d, n_levels=%d", who, L, S, n_levels);
+    // the images of kind 0, 1 and 2: the launches of the earlier entry points, unchanged (none if there is no such segment)
+    const int rc = jpeg_decode_batch(who, chunk_bytes, data, data_bytes, img, B, seg, S, tables, n_sets, pseg, level_counts, n_levels, pool, n_pool,
+                                     qsets, n_q, coef, coef_elems, planes, plane_bytes, pixels, pixel_bytes, max_blocks, max_pixels, stages, status,
+                                     stream);
+    if (rc != 0 || B == 0 || L == 0) return rc;
+    long long P = 0;
+    for (int l = 0; l < n_levels; ++l) P += level_counts[l];
+    MG_REQUIRE(S + P + L <= 0x7fffffffLL, "%s: %lld segments", who, S + P + L);
+    MG_REQUIRE(data && img && lseg && tables && n_sets >= 1 && coef && planes && pixels && status, "%s: null pointer or no table set", who);
+    MG_REQUIRE(mg_aligned16(coef) && mg_aligned16(planes) && mg_aligned16(pixels) && mg_aligned16(tables),
+               "%s: coef, planes, pixels and tables must be 16-byte aligned", who);
+    MG_REQUIRE(lmax_blocks >= 1 && lmax_blocks <= 16LL * (MAXEXT / 8) * (MAXEXT / 8) && lmax_pixels >= 1 && lmax_pixels <= (long long)MAXEXT * MAXEXT,
+               "%s: lmax_blocks=%lld, lmax_pixels=%lld", who, lmax_blocks, lmax_pixels);
+    hipStream_t st = (hipStream_t)stream;
+    if ((stages & 1) && S + P == 0) {              // (with S + P > 0 the launches above have zeroed the workspace)
+        hipError_t e = hipMemsetAsync(coef, 0, coef_elems * sizeof(int16_t), st);
+        if (e != hipSuccess) {
+            mgnns_set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+            return MGNNS_ERR_LAUNCH;
+        }
+    }
+    if (stages & 1) {
+        const int cus = mg_cu_count();
+        if (cus <= 0) return MGNNS_ERR_LAUNCH;
+        int lanes = 1;                             // one lane per wave until every SIMD (4 per CU) has one
+        while (lanes < 64 && (long long)lanes * 4 * cus < L) lanes *= 2;
+        hipLaunchKernelGGL(jpeg_layout_entropy_kernel, dim3((unsigned)((L + lanes - 1) / lanes)), dim3(ENT_NT), 0, st, (const uint8_t*)data,
+                           data_bytes, img, B, lseg, L, lanes, (const MgJpegTables*)tables, n_sets, (int16_t*)coef, coef_elems, plane_bytes,
+                           pixel_bytes, status + S + P);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_layouts_fwd (layout entropy)");
+    }
+    if (stages & 2) {
+        hipLaunchKernelGGL(jpeg_layout_idct_kernel, dim3((unsigned)((lmax_blocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), (unsigned)B), dim3(NT), 0, st,
+                           img, (const MgJpegTables*)tables, n_sets, (const int16_t*)coef, coef_elems, (uint8_t*)planes, plane_bytes, pixel_bytes);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_layouts_fwd (layout idct)");
+    }
+    if (stages & 4) {
+        hipLaunchKernelGGL(jpeg_layout_colour_kernel, dim3((unsigned)((lmax_pixels + NT - 1) / NT), (unsigned)B), dim3(NT), 0, st, img, n_sets,
+                           coef_elems, (const uint8_t*)planes, plane_bytes, (uint8_t*)pixels, pixel_bytes);
+        MG_CHECK_LAUNCH("mgnns_jpeg_decode_layouts_fwd (layout colour)");
+    }
+    return 0;
 }

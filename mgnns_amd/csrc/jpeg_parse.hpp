@@ -600,3 +600,252 @@ inline int mg_jpeg_parse_progressive(const uint8_t* data, size_t n, int max_exte
     info[MG_JPEG_I_NLEVELS] = nlevels;
     return MG_JPEG_OK;
 }
+
+// ---- other component layouts ("Other component layouts") -----------------------------------------------------------
+// further reason codes, of mg_jpeg_parse_layout alone
+enum {
+    MG_JPEG_FRACTIONAL_SAMPLING = 17,      // a sampling factor that is no integral fraction of the largest (libjpeg fails on it too); detail = h v
+    MG_JPEG_SAMPLING_RANGE = 18,           // a sampling factor outside 1..4 (detail = h v), or more than 10 blocks per MCU (detail = the count)
+};
+// the colour model of the components, by libjpeg's default_decompress_parms
+enum { MG_JPEG_COLOUR_GRAY = 0, MG_JPEG_COLOUR_YCC = 1, MG_JPEG_COLOUR_RGB = 2, MG_JPEG_COLOUR_CMYK = 3, MG_JPEG_COLOUR_YCCK = 4 };
+// fields of info[MG_JPEG_LAYOUT_INFO_INTS]; 0..4 are REASON, DETAIL, WIDTH, HEIGHT, NCOMP as above
+enum {
+    MG_JPEG_L_HMAX = 5, MG_JPEG_L_VMAX = 6,
+    MG_JPEG_L_H = 7, MG_JPEG_L_V = 11,     // 4 each: the sampling factors per component (a one-component file: 1, whatever it says)
+    MG_JPEG_L_TQ = 15, MG_JPEG_L_TD = 19, MG_JPEG_L_TA = 23,       // 4 each: table ids per component
+    MG_JPEG_L_RI = 27, MG_JPEG_L_RESTARTS = 28, MG_JPEG_L_NSEG = 29, MG_JPEG_L_MCUX = 30, MG_JPEG_L_MCUY = 31,
+    MG_JPEG_L_COLOUR = 32,                 // MG_JPEG_COLOUR_*
+    MG_JPEG_L_SOF = 33,                    // 0xC0 or 0xC1
+    MG_JPEG_L_BLOCKS = 34,                 // blocks per MCU: the sum of h v over the components
+    MG_JPEG_LAYOUT_INFO_INTS = 40,
+};
+constexpr int MG_JPEG_MAX_MCU_BLOCKS = 10;                     // T.81 B.2.3
+
+// Parse one file of SOF0 or SOF1, 8 bit, Huffman, one scan that interleaves all of its 1, 3 or 4 components, each sampled h x v
+// with h, v in 1..4 that divide the largest, at most 10 blocks per MCU.  The segment logic, range, seg and tables are
+// mg_jpeg_parse's; an MCU covers 8 hmax x 8 vmax pixels and segment j the MCUs [j Ri, (j+1) Ri).  The colour model follows
+// libjpeg: three components are YCbCr with a JFIF segment, else what an Adobe segment's transform says (0: RGB), else RGB if the
+// ids are 'R','G','B', else YCbCr; four are YCCK if an Adobe segment's transform is not 0, else CMYK.  A progressive file gets
+// reason 3 with detail 0xC2.
+inline int mg_jpeg_parse_layout(const uint8_t* data, size_t n, int max_extent, int32_t* info, int64_t* range, int64_t* seg, size_t seg_cap,
+                                MgJpegTables* tables) {
+    using namespace mgjpeg;
+    const Reader R{data, n};
+    memset(info, 0, sizeof(int32_t) * MG_JPEG_LAYOUT_INFO_INTS);
+    memset(tables, 0, sizeof(*tables));
+    range[0] = range[1] = 0;
+    auto refuse = [&](int reason, long long detail) {
+        info[MG_JPEG_I_REASON] = reason;
+        info[MG_JPEG_I_DETAIL] = (int32_t)(detail > 0x7fffffffLL ? 0x7fffffffLL : detail);
+        return reason;
+    };
+    if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return refuse(MG_JPEG_NOT_JPEG, 0);
+
+    uint8_t quant[4][64];
+    uint8_t hbits[2][4][16], hvals[2][4][256];
+    int hcount[2][4];
+    bool have_q[4] = {false, false, false, false}, have_h[2][4] = {{false, false, false, false}, {false, false, false, false}};
+    bool have_frame = false, jfif = false;
+    int width = 0, height = 0, ncomp = 0, sof = 0, comp_id[4] = {0, 0, 0, 0}, comp_h[4] = {1, 1, 1, 1}, comp_v[4] = {1, 1, 1, 1};
+    int comp_tq[4] = {0, 0, 0, 0}, td[4] = {0, 0, 0, 0}, ta[4] = {0, 0, 0, 0}, ri = 0, adobe = -1, hmax = 1, vmax = 1, mcu_blocks = 1;
+    static const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+    size_t pos = 2;
+    for (;;) {
+        if (!R.has(pos, 2) || data[pos] != 0xFF) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        while (pos + 1 < n && data[pos + 1] == 0xFF) ++pos;                  // fill bytes
+        if (!R.has(pos, 2)) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        const int m = data[pos + 1];
+        pos += 2;
+        if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;    // stand-alone markers
+        if (m == 0xD9) return refuse(MG_JPEG_MALFORMED, (long long)pos);     // EOI before any scan
+        if (!R.has(pos, 2)) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        const int ln = R.u16(pos);
+        if (ln < 2 || !R.has(pos, (size_t)ln)) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+        const size_t body = pos + 2, end = pos + (size_t)ln;
+        if (m == 0xDB) {
+            size_t p = body;
+            while (p < end) {
+                const int pq = data[p] >> 4, tq = data[p] & 15;
+                if (pq != 0) return refuse(MG_JPEG_PRECISION, 16);
+                if (tq > 3 || p + 65 > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                for (int k = 0; k < 64; ++k) quant[tq][ZIGZAG[k]] = data[p + 1 + k];
+                have_q[tq] = true;
+                p += 65;
+            }
+        } else if (m == 0xC4) {
+            size_t p = body;
+            while (p < end) {
+                if (p + 17 > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                const int tc = data[p] >> 4, th = data[p] & 15;
+                int cnt = 0;
+                for (int i = 0; i < 16; ++i) cnt += data[p + 1 + i];
+                if (tc > 1 || th > 3 || cnt > 256 || p + 17 + (size_t)cnt > end) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                int code = 0;
+                for (int l = 1; l <= 16; ++l) {
+                    code += data[p + l];
+                    if (code > (1 << l)) return refuse(MG_JPEG_MALFORMED, (long long)p);
+                    code <<= 1;
+                }
+                memcpy(hbits[tc][th], data + p + 1, 16);
+                memcpy(hvals[tc][th], data + p + 17, (size_t)cnt);
+                hcount[tc][th] = cnt;
+                have_h[tc][th] = true;
+                p += 17 + (size_t)cnt;
+            }
+        } else if (m == 0xDD) {
+            if (ln != 4) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            ri = R.u16(body);
+        } else if (m == 0xCC || (m >= 0xC9 && m <= 0xCF)) {
+            return refuse(MG_JPEG_ARITHMETIC, m);
+        } else if (m == 0xC2 || m == 0xC3 || m == 0xC5 || m == 0xC6 || m == 0xC7 || m == 0xC8) {
+            return refuse(MG_JPEG_UNSUPPORTED_SOF, m);
+        } else if (m == 0xC0 || m == 0xC1) {
+            if (have_frame || ln < 8) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int prec = data[body], nf = data[body + 5];
+            height = R.u16(body + 1);
+            width = R.u16(body + 3);
+            if (prec != 8) return refuse(MG_JPEG_PRECISION, prec);
+            if (ln != 8 + 3 * nf) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            if (nf != 1 && nf != 3 && nf != 4) return refuse(MG_JPEG_COMPONENTS, nf);
+            if (height == 0) return refuse(MG_JPEG_DNL, 0);
+            if (width < 1 || width > max_extent || height > max_extent) return refuse(MG_JPEG_EXTENT, width > max_extent ? width : height);
+            ncomp = nf, sof = m;
+            for (int i = 0; i < nf; ++i) {
+                comp_id[i] = data[body + 6 + 3 * i];
+                comp_h[i] = data[body + 7 + 3 * i] >> 4;
+                comp_v[i] = data[body + 7 + 3 * i] & 15;
+                comp_tq[i] = data[body + 8 + 3 * i];
+            }
+            for (int i = 0; i < nf; ++i)
+                if (comp_tq[i] > 3) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            for (int i = 0; i < nf; ++i)
+                if (comp_h[i] < 1 || comp_h[i] > 4 || comp_v[i] < 1 || comp_v[i] > 4) return refuse(MG_JPEG_SAMPLING_RANGE, comp_h[i] * 16 + comp_v[i]);
+            if (nf == 1) comp_h[0] = comp_v[0] = 1;                          // one component: its factors mean nothing (T.81 A.2.2)
+            hmax = vmax = 1, mcu_blocks = 0;
+            for (int i = 0; i < nf; ++i) {
+                hmax = comp_h[i] > hmax ? comp_h[i] : hmax;
+                vmax = comp_v[i] > vmax ? comp_v[i] : vmax;
+                mcu_blocks += comp_h[i] * comp_v[i];
+            }
+            for (int i = 0; i < nf; ++i)
+                if (hmax % comp_h[i] || vmax % comp_v[i]) return refuse(MG_JPEG_FRACTIONAL_SAMPLING, comp_h[i] * 16 + comp_v[i]);
+            if (mcu_blocks > MG_JPEG_MAX_MCU_BLOCKS) return refuse(MG_JPEG_SAMPLING_RANGE, mcu_blocks);
+            have_frame = true;
+        } else if (m == 0xDC) {
+            return refuse(MG_JPEG_DNL, 0);
+        } else if (m == 0xE0 && ln >= 16 && memcmp(data + body, "JFIF", 5) == 0) {
+            jfif = true;
+        } else if (m == 0xEE && ln >= 14 && memcmp(data + body, "Adobe", 5) == 0) {
+            adobe = data[body + 11];
+        } else if (m == 0xDA) {
+            if (!have_frame) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            const int ns = ln >= 3 ? data[body] : 0;
+            if (ns != ncomp) return refuse(MG_JPEG_SCANS, ns);
+            if (ln != 6 + 2 * ns) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            for (int i = 0; i < ns; ++i) {
+                if (data[body + 1 + 2 * i] != comp_id[i]) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+                td[i] = data[body + 2 + 2 * i] >> 4;
+                ta[i] = data[body + 2 + 2 * i] & 15;
+                if (td[i] > 3 || ta[i] > 3) return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            }
+            if (data[body + 1 + 2 * ns] != 0 || data[body + 2 + 2 * ns] != 63 || data[body + 3 + 2 * ns] != 0)
+                return refuse(MG_JPEG_MALFORMED, (long long)pos);
+            for (int i = 0; i < ns; ++i)
+                if (!have_q[comp_tq[i]] || !have_h[0][td[i]] || !have_h[1][ta[i]]) return refuse(MG_JPEG_MISSING_TABLES, i);
+            pos = end;
+            break;
+        }
+        pos = end;
+    }
+
+    // the entropy-coded data: up to the first marker that is neither a stuffed FF, a fill byte nor RSTn
+    const int mcux = (width + 8 * hmax - 1) / (8 * hmax), mcuy = (height + 8 * vmax - 1) / (8 * vmax);
+    const long long nmcu = (long long)mcux * mcuy;
+    const long long nseg = ri ? (nmcu + ri - 1) / ri : 1;
+    const size_t begin = pos;
+    size_t i = pos, seg_begin = pos;
+    long long found = 0;
+    auto put = [&](long long j, size_t b, size_t e) {
+        if (j < nseg && (size_t)j < seg_cap) {
+            seg[2 * j] = (int64_t)b;
+            seg[2 * j + 1] = (int64_t)e;
+        }
+    };
+    for (;;) {
+        while (i < n && data[i] != 0xFF) ++i;
+        if (i + 1 >= n) {
+            i = n;
+            break;
+        }
+        const int b = data[i + 1];
+        if (b == 0) {
+            i += 2;
+        } else if (b == 0xFF) {
+            i += 1;
+        } else if (b >= 0xD0 && b <= 0xD7) {
+            put(found, seg_begin, i);
+            ++found;
+            i += 2;
+            seg_begin = i;
+        } else {
+            break;
+        }
+    }
+    const size_t ecs_end = i;
+    put(found, seg_begin, ecs_end);
+    for (long long j = found + 1; j < nseg; ++j) put(j, ecs_end, ecs_end);
+    // what follows: another scan or DNL is refused; anything else (EOI, nothing, rubbish) ends the file
+    while (i + 1 < n && data[i] == 0xFF) {
+        const int b = data[i + 1];
+        if (b == 0xFF) {
+            ++i;
+            continue;
+        }
+        if (b == 0xD9) break;
+        if (b == 0xDA) return refuse(MG_JPEG_SCANS, 2);
+        if (b == 0xDC) return refuse(MG_JPEG_DNL, 0);
+        if (i + 4 > n) break;
+        i += 2 + (size_t)R.u16(i + 2);
+    }
+
+    for (int c = 0; c < ncomp; ++c) {
+        memcpy(tables->quant[comp_tq[c]], quant[comp_tq[c]], 64);
+        if (!mgjpeg::derive(hbits[0][td[c]], hvals[0][td[c]], hcount[0][td[c]], &tables->dc[td[c]]) ||
+            !mgjpeg::derive(hbits[1][ta[c]], hvals[1][ta[c]], hcount[1][ta[c]], &tables->ac[ta[c]]))
+            return refuse(MG_JPEG_MALFORMED, c);
+    }
+    int colour = MG_JPEG_COLOUR_GRAY;
+    if (ncomp == 3) {
+        const bool ids_rgb = comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B';
+        colour = jfif ? MG_JPEG_COLOUR_YCC : adobe >= 0 ? (adobe == 0 ? MG_JPEG_COLOUR_RGB : MG_JPEG_COLOUR_YCC)
+                                                        : (ids_rgb ? MG_JPEG_COLOUR_RGB : MG_JPEG_COLOUR_YCC);
+    } else if (ncomp == 4) {
+        colour = adobe > 0 ? MG_JPEG_COLOUR_YCCK : MG_JPEG_COLOUR_CMYK;
+    }
+    info[MG_JPEG_I_WIDTH] = width;
+    info[MG_JPEG_I_HEIGHT] = height;
+    info[MG_JPEG_I_NCOMP] = ncomp;
+    info[MG_JPEG_L_HMAX] = hmax;
+    info[MG_JPEG_L_VMAX] = vmax;
+    for (int c = 0; c < 4; ++c) {
+        info[MG_JPEG_L_H + c] = c < ncomp ? comp_h[c] : 0;
+        info[MG_JPEG_L_V + c] = c < ncomp ? comp_v[c] : 0;
+        info[MG_JPEG_L_TQ + c] = comp_tq[c];
+        info[MG_JPEG_L_TD + c] = td[c];
+        info[MG_JPEG_L_TA + c] = ta[c];
+    }
+    info[MG_JPEG_L_RI] = ri;
+    info[MG_JPEG_L_RESTARTS] = (int32_t)(found > 0x7fffffffLL ? 0x7fffffffLL : found);
+    info[MG_JPEG_L_NSEG] = (int32_t)nseg;
+    info[MG_JPEG_L_MCUX] = mcux;
+    info[MG_JPEG_L_MCUY] = mcuy;
+    info[MG_JPEG_L_COLOUR] = colour;
+    info[MG_JPEG_L_SOF] = sof;
+    info[MG_JPEG_L_BLOCKS] = mcu_blocks;
+    range[0] = (int64_t)begin;
+    range[1] = (int64_t)ecs_end;
+    return MG_JPEG_OK;
+}

@@ -16,7 +16,10 @@ file, which decode_jpeg / warp_jpeg / train_jpeg decode on the GPU to exactly Pi
 the host only parses the markers.  ImagePrep(..., progressive=True) decodes progressive (SOF2) files as well (csrc/jpeg_progressive.hpp);
 the switch is off by default, and a progressive file is then refused with reason 3 as before.  ImagePrep(..., split=True) decodes a
 long baseline scan -- a file without restart markers is one -- on many lanes instead of one, to the same pixels (csrc/jpeg_split.hpp;
-DESIGN.md 17, "Split scans"); off by default as well.  This module does not import PIL."""
+DESIGN.md 17, "Split scans"); off by default as well.  ImagePrep(..., layouts=True) also decodes the other component layouts of
+SOF0 / SOF1 files -- CMYK and YCCK, RGB, 4:4:0, 4:1:1 and every other interleaved layout of 1, 3 or 4 components whose sampling
+factors divide the largest -- to Pillow's convert('RGB') pixels (csrc/jpeg_layouts.hpp; DESIGN.md 17, "Other component layouts");
+off by default, and such a file is then refused with reason 3, 6, 7, 8 or 9 as before.  This module does not import PIL."""
 import math
 import random
 
@@ -116,6 +119,14 @@ JPEG_REASONS = {
 JPEG_PROGRESSIVE_REASONS = {
     14: "incomplete progression: at the end of the file a coefficient has not had its last bit (libjpeg would smooth it)",
     15: "illegal progression: Ss / Se / Ah / Al contradict T.81 G.1.1.1.1 or the scans before", 16: "more than 32 scans"}
+# further codes of the layout parser (parse_jpeg(..., layouts=True))
+JPEG_LAYOUT_REASONS = {
+    17: "a sampling factor that is no integral fraction of the largest (libjpeg refuses it too)",
+    18: "a sampling factor outside 1..4, or more than 10 blocks per MCU"}
+JPEG_COLOUR_MODELS = ops.JPEG_COLOUR_MODELS
+_JL = dict(reason=0, detail=1, width=2, height=3, ncomp=4, hmax=5, vmax=6, h=7, v=11, tq=15, td=19, ta=23, ri=27, restarts=28, nseg=29, mcux=30,
+           mcuy=31, colour=32, sof=33, mcu_blocks=34)
+_JPEG_LAYOUT_INFO_INTS = 40
 _JI = dict(reason=0, detail=1, width=2, height=3, ncomp=4, hs=5, vs=6, tq=7, td=10, ta=13, ri=16, restarts=17, nseg=18, mcux=19, mcuy=20)
 
 
@@ -125,7 +136,8 @@ class UnsupportedJpeg(ValueError):
     def __init__(self, refused, details):
         self.refused = refused
         ValueError.__init__(self, "%d JPEG file(s) cannot be decoded on the GPU (pass fallback= to decode them yourself): %s" % (
-            len(refused), "; ".join("image %d: %s (reason %d, found %s)" % (i, JPEG_REASONS.get(r) or JPEG_PROGRESSIVE_REASONS.get(r, "?"), r, d)
+            len(refused), "; ".join("image %d: %s (reason %d, found %s)"
+                                   % (i, JPEG_REASONS.get(r) or JPEG_PROGRESSIVE_REASONS.get(r) or JPEG_LAYOUT_REASONS.get(r, "?"), r, d)
                                    for (i, r), d in zip(refused, details))))
 
 
@@ -173,7 +185,34 @@ def _parse_progressive(a, max_extent, bufs=None):
     return out
 
 
-def parse_jpeg(data, max_extent=None, _seg=None, progressive=False, _bufs=None):
+def _parse_layout(a, max_extent, seg=None):
+    """mgnns_jpeg_parse_layout on one file's bytes (a uint8 array) -> parse_jpeg's dict for a file of another component layout."""
+    from . import _lib
+    info = np.zeros(_JPEG_LAYOUT_INFO_INTS, np.int32)
+    rng = np.zeros(2, np.int64)
+    tables = np.zeros(ops.jpeg_tableset_bytes(), np.uint8)
+    seg = np.zeros((64, 2), np.int64) if seg is None else seg
+    ptr = a.ctypes.data if a.size else None
+    for _ in range(2):
+        _lib.call("mgnns_jpeg_parse_layout", ptr, a.size, int(max_extent or ops.IMAGE_MAX_EXTENT), info.ctypes.data, rng.ctypes.data,
+                  seg.ctypes.data, seg.shape[0], tables.ctypes.data)
+        if info[0] != 0 or info[_JL["nseg"]] <= seg.shape[0]:
+            break
+        seg = np.zeros((int(info[_JL["nseg"]]), 2), np.int64)
+    out = dict(reason=int(info[0]), detail=int(info[1]))
+    if out["reason"] == 0:
+        for k in ("width", "height", "ncomp", "hmax", "vmax", "ri", "restarts", "nseg", "mcux", "mcuy", "colour", "sof", "mcu_blocks"):
+            out[k] = int(info[_JL[k]])
+        for k in ("h", "v", "tq", "td", "ta"):
+            out[k] = [int(x) for x in info[_JL[k]:_JL[k] + out["ncomp"]]]
+        out["layout"] = True
+        out["ecs"] = (int(rng[0]), int(rng[1]))
+        out["segments"] = seg[:out["nseg"]].copy()
+        out["tables"] = tables.tobytes()
+    return out
+
+
+def parse_jpeg(data, max_extent=None, _seg=None, progressive=False, _bufs=None, layouts=False):
     """The host parser (mgnns_jpeg_parse: no GPU call) on one file's bytes -> dict: reason (0 = accepted), detail, and for an accepted
     file width, height, ncomp, hs, vs (Y's sampling), tq / td / ta (table ids per component), ri, restarts (markers found), nseg, mcux,
     mcuy, ecs (begin, end), segments (int64 [nseg,2] byte ranges) and tables (the table set's bytes).
@@ -184,7 +223,13 @@ def parse_jpeg(data, max_extent=None, _seg=None, progressive=False, _bufs=None):
     index of the DC table per frame component, -1 = none read), ac, seg0 / nseg (its rows of `segments`), units, ecs, restarts -- with
     width, height, ncomp, hs, vs, mcux, mcuy, nseg (of all scans), segments (int64 [nseg,4]: begin, end, first unit, units), pool (the
     distinct Huffman tables' bytes) and quant (192 bytes: per component the quantisation table in force at its first scan).  Scans
-    of one level touch different coefficients and decode at the same time; levels run in order."""
+    of one level touch different coefficients and decode at the same time; levels run in order.
+
+    layouts=True hands a file the baseline parser has refused with reason 3 (detail 0xC1: SOF1), 6, 7, 8 or 9 to the layout parser
+    (mgnns_jpeg_parse_layout, DESIGN.md 17, "Other component layouts").  An accepted one has layout=True, width, height, ncomp (1, 3 or
+    4), hmax, vmax, h / v / tq / td / ta (per component), colour (JPEG_COLOUR_MODELS), sof, mcu_blocks, ri, restarts, nseg, mcux, mcuy
+    (MCUs of 8 hmax x 8 vmax pixels), ecs, segments and tables; a refused one a reason of JPEG_REASONS or JPEG_LAYOUT_REASONS.  A file
+    the baseline parser accepts is the baseline parser's, with the dictionary it always had."""
     from . import _lib
     a = _file_bytes(data)
     info = np.zeros(24, np.int32)
@@ -211,6 +256,8 @@ def parse_jpeg(data, max_extent=None, _seg=None, progressive=False, _bufs=None):
             out["scans"], out["levels"] = [], 0
     elif progressive and out["reason"] == 3 and out["detail"] == 0xC2:
         return _parse_progressive(a, max_extent, _bufs)
+    elif layouts and (out["reason"] in (6, 7, 8, 9) or (out["reason"] == 3 and out["detail"] == 0xC1)):
+        return _parse_layout(a, max_extent, _seg)
     return out
 
 
@@ -282,7 +329,7 @@ def split_chunk(split):
 
 class ImagePrep:
     def __init__(self, size=448, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device=None, scales=SCALES,
-                 max_distort=MAX_DISTORT, ring=2, progressive=False, split=0):
+                 max_distort=MAX_DISTORT, ring=2, progressive=False, split=0, layouts=False):
         size = int(size)
         if not 1 <= size <= ops.IMAGE_MAX_SIZE:
             raise ValueError("size must be in 1..%d, got %d" % (ops.IMAGE_MAX_SIZE, size))
@@ -295,6 +342,7 @@ class ImagePrep:
         self.size = size
         self.progressive = bool(progressive)         # decode_jpeg / warp_jpeg / train_jpeg also decode progressive (SOF2) files
         self.split = split_chunk(split)              # ... and decode long baseline scans on many lanes, in chunks of so many bytes (0: off)
+        self.layouts = bool(layouts)                 # ... and CMYK, YCCK, RGB, 4:4:0, 4:1:1 and the other interleaved layouts
         self.scales, self.max_distort = tuple(scales), int(max_distort)
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
@@ -460,7 +508,7 @@ class ImagePrep:
         parsed, refused = [], []
         for i, f in enumerate(files):
             _file_bytes(f, i)
-            parsed.append(parse_jpeg(f, _seg=seg, progressive=self.progressive, _bufs=bufs))
+            parsed.append(parse_jpeg(f, _seg=seg, progressive=self.progressive, _bufs=bufs, layouts=self.layouts))
             if parsed[-1]["reason"]:
                 refused.append((i, parsed[-1]["reason"]))
         if refused and fallback is None:
@@ -474,7 +522,8 @@ class ImagePrep:
         image and segment records, the pixels of fall-back images -- copy them over and decode.  With prep=True the descriptors of
         (crops, flips) follow and image_prep runs on the decoded buffer.  -> DecodedBatch, or the [B,3,size,size] tensor.
         staged_only=True stops before the decode and returns (ops.jpeg_decode's arguments, DecodedBatch): tools/bench_jpeg.py
-        (with progressive or split: ops.jpeg_decode_progressive's, which are ops.jpeg_decode_split's)."""
+        (with progressive or split: ops.jpeg_decode_progressive's, which are ops.jpeg_decode_split's; with layouts:
+        ops.jpeg_decode_layouts's)."""
         if self.device is None:
             raise RuntimeError("ImagePrep was built without a device: JPEG files are decoded on the GPU only (no CPU path)")
         files, parsed, arrays, sizes = headers
@@ -496,7 +545,7 @@ class ImagePrep:
                 desc_rows.append((offs[i], H, W, cx, cy, cw, ch, 1 if (flips is not None and bool(flips[i])) else 0, self.plan(cw), self.plan(ch)))
         # layout of the raw buffer: the accepted files at 16-byte starts, the table sets, then the fall-back images' pixels
         TB = ops.jpeg_tableset_bytes()
-        mixed = self.progressive or self.split > 0          # the decode that takes the progressive arguments (empty with split alone)
+        mixed = self.progressive or self.split > 0 or self.layouts     # the decode that takes the progressive arguments (maybe empty)
         HB = ops.jpeg_huff_bytes() if mixed else 0
         raw_off, n, sets, pool, qsets = {}, 0, {}, {}, {}
         for i, f in enumerate(files):
@@ -521,13 +570,26 @@ class ImagePrep:
             fb_off[i] = n
             n += ends[i] - offs[i]
         img = np.zeros((B, ops.JPEG_IMG), np.int64)
-        segs, psegs, coef_off, plane_off = [], [], 0, 0
+        segs, psegs, lsegs, coef_off, plane_off = [], [], [], 0, 0
         for i, p in enumerate(parsed):
             W, H = sizes[i]
             if i in arrays:
                 img[i] = (0, W, H, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, offs[i], ends[i])
                 continue
             nmcu = p["mcux"] * p["mcuy"]
+            if p.get("layout"):                  # another component layout: kind 3, segments of its own (never split)
+                pack = lambda v, bits: sum(x << (bits * c) for c, x in enumerate(v))
+                img[i] = (ops.JPEG_LAYOUT_KIND, W, H, p["ncomp"] | p["colour"] << 8, pack(p["h"], 4), pack(p["v"], 4), p["mcux"], p["mcuy"],
+                          pack(p["tq"], 8), pack(p["td"], 8), pack(p["ta"], 8), sets[p["tables"]], coef_off, plane_off, offs[i], ends[i])
+                coef_off += nmcu * p["mcu_blocks"] * 64
+                plane_off += nmcu * p["mcu_blocks"] * 64
+                s = np.empty((p["nseg"], ops.JPEG_SEG), np.int64)
+                s[:, 0] = i
+                s[:, 1:3] = p["segments"] + raw_off[i]
+                s[:, 3] = np.arange(p["nseg"]) * p["ri"]
+                s[:, 4] = np.minimum(p["ri"], nmcu - s[:, 3]) if p["ri"] else nmcu
+                lsegs.append(s)
+                continue
             blocks = nmcu if p["ncomp"] == 1 else nmcu * (p["hs"] * p["vs"] + 2)
             pack3 = lambda v: v[0] | v[1] << 8 | v[2] << 16
             if "pool" in p:                      # progressive: kind 2, the latched quantisation set, a record per segment of every scan
@@ -566,7 +628,10 @@ class ImagePrep:
         level_counts = np.bincount(pseg[:, -1]).tolist() if len(pseg) else []
         pseg = pseg[:, :ops.JPEG_PSEG]
         P = pseg.shape[0]
-        nrec = B * ops.JPEG_IMG + S * ops.JPEG_SEG + P * ops.JPEG_PSEG
+        lseg = np.concatenate(lsegs) if lsegs else np.zeros((0, ops.JPEG_SEG), np.int64)
+        L = lseg.shape[0]
+        lseg_at = B * ops.JPEG_IMG + S * ops.JPEG_SEG                       # the layout segments lie between seg and pseg
+        nrec = lseg_at + L * ops.JPEG_SEG + P * ops.JPEG_PSEG
 
         slot = self._ring[self._next]
         self._next = (self._next + 1) % len(self._ring)
@@ -593,8 +658,10 @@ class ImagePrep:
         img_host = slot.rec[:B * ops.JPEG_IMG].view(B, ops.JPEG_IMG)
         seg_host = slot.rec[B * ops.JPEG_IMG:B * ops.JPEG_IMG + S * ops.JPEG_SEG].view(S, ops.JPEG_SEG)
         pseg_host = slot.rec[nrec - P * ops.JPEG_PSEG:nrec].view(P, ops.JPEG_PSEG)
+        lseg_host = slot.rec[lseg_at:lseg_at + L * ops.JPEG_SEG].view(L, ops.JPEG_SEG)
         img_host.numpy()[:] = img
         seg_host.numpy()[:] = seg
+        lseg_host.numpy()[:] = lseg
         pseg_host.numpy()[:] = pseg
         desc = slot.desc[:B]
         if prep and B:
@@ -622,13 +689,20 @@ class ImagePrep:
                 pseg_dev = rec_dev[nrec - P * ops.JPEG_PSEG:nrec].view(P, ops.JPEG_PSEG)
                 pool_dev = raw_dev[pool_off:pool_off + len(pool) * HB].view(len(pool), HB)
                 qsets_dev = raw_dev[q_off:q_off + len(qsets) * ops.JPEG_QSET].view(len(qsets), ops.JPEG_QSET)
+                lseg_dev = rec_dev[lseg_at:lseg_at + L * ops.JPEG_SEG].view(L, ops.JPEG_SEG)
             if staged_only:                      # (host records cloned: the slot is reused two batches later)
+                if self.layouts:
+                    return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pseg_host.clone(), pseg_dev, level_counts,
+                            pool_dev, qsets_dev, lseg_host.clone(), lseg_dev, pix_dev), batch
                 if mixed:
                     return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pseg_host.clone(), pseg_dev, level_counts,
                             pool_dev, qsets_dev, pix_dev), batch
                 return (raw_dev, img_host.clone(), img_dev, seg_host.clone(), seg_dev, tables_dev, pix_dev), batch
             try:
-                if self.split:
+                if self.layouts:
+                    ops.jpeg_decode_layouts(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pseg_host, pseg_dev, level_counts,
+                                            pool_dev, qsets_dev, lseg_host, lseg_dev, pix_dev, chunk_bytes=self.split)
+                elif self.split:
                     ops.jpeg_decode_split(raw_dev, img_host, img_dev, seg_host, seg_dev, tables_dev, pseg_host, pseg_dev, level_counts,
                                           pool_dev, qsets_dev, pix_dev, chunk_bytes=self.split)
                 elif self.progressive:
@@ -651,7 +725,8 @@ class ImagePrep:
         work -- or, with fallback=callable, is decoded by the caller: fallback(file bytes) -> a [H,W,3] uint8 array, staged into the
         same pixel buffer.  A file whose scan is corrupt raises ops.JpegDecodeError (a ValueError) after the decode, naming the
         image and the segment's status.  A prep built with progressive=True decodes progressive files as well, in any mix with
-        baseline ones; the error then names the scan too, and files of its further reasons are in JPEG_PROGRESSIVE_REASONS."""
+        baseline ones; the error then names the scan too, and files of its further reasons are in JPEG_PROGRESSIVE_REASONS.  A prep
+        built with layouts=True decodes CMYK, YCCK, RGB, 4:4:0, 4:1:1 and the other interleaved layouts as well (JPEG_LAYOUT_REASONS)."""
         return self._jpeg_run(self._jpeg_headers(files, fallback))
 
     def warp_jpeg(self, files, fallback=None):

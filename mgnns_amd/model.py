@@ -335,14 +335,15 @@ class Multi_GCN_Multihead_Att(nn.Module):
     def set_label_query(self, q):
         self.label_query = torch.as_tensor(q).float().to(self.embedding.weight.device)
 
-    def image_prep(self, size=448, progressive=False, split=0):
+    def image_prep(self, size=448, progressive=False, split=0, layouts=False):
         """The reference's image transforms on this model's device with its image_normalization_mean / std (mgnns_amd/images.py):
         prep.warp(images) for eval, prep.train(images) for training -> the [B,3,size,size] fp32 tensor forward() takes.
         progressive=True: warp_jpeg / train_jpeg / decode_jpeg also decode progressive JPEG files on the GPU.
-        split=True (or a chunk size in bytes): they decode a baseline file without restart markers on many lanes, to the same pixels."""
+        split=True (or a chunk size in bytes): they decode a baseline file without restart markers on many lanes, to the same pixels.
+        layouts=True: they also decode CMYK, YCCK, RGB, 4:4:0, 4:1:1 and the other interleaved component layouts, as Pillow does."""
         from .images import ImagePrep
         return ImagePrep(size, self.image_normalization_mean, self.image_normalization_std, device=self.embedding.weight.device,
-                         progressive=progressive, split=split)
+                         progressive=progressive, split=split, layouts=layouts)
 
     def init_weights(self, emb_type, pad_idx):
         if emb_type == 'random':

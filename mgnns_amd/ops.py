@@ -1876,7 +1876,7 @@ def jpeg_huff_bytes():
 
 
 def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=7, check=True,
-                            _split=0):
+                            _split=0, _layouts=None):
     """Decode a batch that may mix baseline and progressive files into `pixels` (include/mgnns_jpeg_progressive.h): the workspace zeroed, jpeg_decode's entropy kernel over the baseline segments, one launch of the progressive entropy
     kernel per level, then the IDCT and colour kernels over all images -- on the current stream.  As jpeg_decode, and: an image of
     kind 2 is progressive (its table-set field counts `qsets`); pseg [P,12] int64 HOST tensor sorted by level, pseg_dev its device
@@ -1895,6 +1895,15 @@ def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg
     _chk(seg_dev, "seg_dev", torch.int64, 2)
     _chk(pseg_dev, "pseg_dev", torch.int64, 2)
     B, S, P, n_sets, n_pool, n_q = img.shape[0], seg.shape[0], pseg.shape[0], tables.shape[0], pool.shape[0], qsets.shape[0]
+    L = 0
+    if _layouts is not None:                   # (jpeg_decode_layouts: the segment records of the images of kind 3, host and device)
+        lseg, lseg_dev = _layouts
+        _chk_host(lseg, "lseg", torch.int64, JPEG_SEG)
+        _chk(lseg_dev, "lseg_dev", torch.int64, 2)
+        L = lseg.shape[0]
+        if tuple(lseg_dev.shape) != tuple(lseg.shape) or lseg_dev.device != data.device:
+            raise ValueError("lseg_dev %s on %s must have the shape of its host copy %s and lie on %s"
+                             % (tuple(lseg_dev.shape), lseg_dev.device, tuple(lseg.shape), data.device))
     for host, dev, name in ((img, img_dev, "img_dev"), (seg, seg_dev, "seg_dev"), (pseg, pseg_dev, "pseg_dev")):
         if tuple(dev.shape) != tuple(host.shape):
             raise ValueError("%s %s must have the shape of its host copy %s" % (name, tuple(dev.shape), tuple(host.shape)))
@@ -1915,10 +1924,28 @@ def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg
         raise ValueError("at most 65534 tables in the pool, got %d" % n_pool)
     if int(stages) < 1 or int(stages) > 7:
         raise ValueError("stages is a mask of 1 (entropy), 2 (IDCT), 4 (colour), got %s" % (stages,))
-    status = torch.zeros(S + P, dtype=torch.int32, device=data.device)
-    if B == 0 or S + P == 0:
+    status = torch.zeros(S + P + L, dtype=torch.int32, device=data.device)
+    if B == 0 or S + P + L == 0:
         return status
+    full = img
+    if _layouts is not None:                   # the records of kind 3 have a check of their own; here they count as staged pixels
+        img = img.clone()
+        img[full[:, 0] == 3, 0] = 0
     refuse, dec, nmcu, blocks, coef_elems, plane_bytes = _jpeg_check_images(img, n_sets, n_q, pixels)
+    lblocks = lpixels = 0
+    if _layouts is not None:
+        lay, lmcu, lb = _jpeg_check_layouts(full, n_sets, refuse)
+        li, lb_, le, l0, ln = lseg.unbind(1)
+        refuse((li < 0) | (li >= B), "image index outside the batch", lseg, "layout segment")
+        refuse(~lay[li], "layout segment of an image that is not of kind 3", lseg, "layout segment")
+        refuse((lb_ < 0) | (lb_ > le) | (le > data.numel()), "byte range outside the data buffer of %d bytes" % data.numel(), lseg, "layout segment")
+        refuse((l0 < 0) | (ln < 1) | (l0 > lmcu[li] - ln), "MCU range outside the image", lseg, "layout segment")
+        if bool(lay.any()):
+            coef_elems = max(coef_elems, int(((full[:, 12] + lb * 64) * lay).max()))
+            plane_bytes = max(plane_bytes, int(((full[:, 13] + lb * 64) * lay).max()))
+            lblocks, lpixels = int(lb.max()), int((full[:, 1] * full[:, 2] * lay).max())
+        if coef_elems > (1 << 34):
+            raise ValueError("the batch needs a coefficient workspace of %d int16 -- decode it in smaller batches" % coef_elems)
     kind, W, H, nc, hs, vs, mcux = (img[:, k] for k in range(7))
     si, sb, se, m0, mn = seg.unbind(1)
     refuse((si < 0) | (si >= B), "image index outside the batch", seg, "segment")
@@ -1946,18 +1973,26 @@ def jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg
     coef = torch.empty(max(coef_elems, 64), dtype=torch.int16, device=data.device)
     planes = torch.empty(max(plane_bytes, 64), dtype=torch.uint8, device=data.device)
     # (_split: jpeg_decode_split's chunk size -- the same arguments and one more, to the entry point of include/mgnns_jpeg_split.h)
-    _launch("mgnns_jpeg_decode_split_fwd" if _split else "mgnns_jpeg_decode_progressive_fwd", _p(data), data.numel(), _p(img_dev), B,
-            _p(seg_dev) if S else None, S,
-            _p(tables) if n_sets else None, n_sets, _p(pseg_dev) if P else None, lv.data_ptr() if len(level_counts) else None, len(level_counts),
-            _p(pool) if n_pool else None, n_pool, _p(qsets) if n_q else None, n_q, _p(coef), coef.numel(), _p(planes), planes.numel(),
-            _p(pixels), pixels.numel(), max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1), int(stages), _p(status), _stream(),
-            *((int(_split),) if _split else ()), key=(B, S, tuple(level_counts)))
+    if _layouts is not None:                   # (include/mgnns_jpeg_layouts.h: the same launches, then those of the images of kind 3)
+        _launch("mgnns_jpeg_decode_layouts_fwd", _p(data), data.numel(), _p(img_dev), B, _p(seg_dev) if S else None, S,
+                _p(tables) if n_sets else None, n_sets, _p(pseg_dev) if P else None, lv.data_ptr() if len(level_counts) else None,
+                len(level_counts), _p(pool) if n_pool else None, n_pool, _p(qsets) if n_q else None, n_q, _p(lseg_dev) if L else None, L,
+                _p(coef), coef.numel(), _p(planes), planes.numel(), _p(pixels), pixels.numel(), max(int(blocks.max()), 1),
+                max(int((W * H * dec).max()), 1), max(lblocks, 1), max(lpixels, 1), int(stages), _p(status), _stream(), int(_split),
+                key=(B, S, tuple(level_counts), L))
+    else:
+        _launch("mgnns_jpeg_decode_split_fwd" if _split else "mgnns_jpeg_decode_progressive_fwd", _p(data), data.numel(), _p(img_dev), B,
+                _p(seg_dev) if S else None, S,
+                _p(tables) if n_sets else None, n_sets, _p(pseg_dev) if P else None, lv.data_ptr() if len(level_counts) else None, len(level_counts),
+                _p(pool) if n_pool else None, n_pool, _p(qsets) if n_q else None, n_q, _p(coef), coef.numel(), _p(planes), planes.numel(),
+                _p(pixels), pixels.numel(), max(int(blocks.max()), 1), max(int((W * H * dec).max()), 1), int(stages), _p(status), _stream(),
+                *((int(_split),) if _split else ()), key=(B, S, tuple(level_counts)))
     if check:
         st = status.cpu()                      # one small D2H on the current stream; it also ends the workspaces' use
         bad = st.nonzero().flatten().tolist()
         if bad:
-            raise JpegDecodeError([(int(si[s]) if s < S else int(pi[s - S]), s, int(st[s])) for s in bad], pixels,
-                                  {s: int(pseg[s - S, 11]) for s in bad if s >= S})
+            owner = lambda s: int(si[s]) if s < S else int(pi[s - S]) if s < S + P else int(li[s - S - P])
+            raise JpegDecodeError([(owner(s), s, int(st[s])) for s in bad], pixels, {s: int(pseg[s - S, 11]) for s in bad if S <= s < S + P})
     return status
 
 
@@ -1974,6 +2009,52 @@ def jpeg_decode_split(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, 
         raise ValueError("chunk_bytes must be a multiple of 8 in 8..65536, got %r" % (chunk_bytes,))
     return jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=stages,
                                    check=check, _split=chunk_bytes)
+
+
+JPEG_LAYOUT_KIND = 3      # an image record of another component layout: kind 3, width, height, components | colour model << 8, h and v
+#                           (a nibble per component), MCUs per row, MCU rows, quantisation / DC / AC table ids (a byte per component,
+#                           four of them), table set, coefficient / plane / pixel offset, end of the padding
+JPEG_COLOUR_MODELS = {0: "gray", 1: "YCbCr", 2: "RGB", 3: "CMYK", 4: "YCCK"}
+
+
+def _jpeg_check_layouts(img, n_sets, refuse):
+    """The image records of kind 3, checked on the host as the layout kernels check them.  -> (mask of kind 3, MCUs, blocks per image)"""
+    kind, W, H, nm, hp, vp, mcux, mcuy, tq, td, ta, tset, coef_off, plane_off = (img[:, k] for k in range(14))
+    lay = kind == 3
+    nc, model = nm & 0xFF, nm >> 8
+    refuse(lay & ((nm < 0) | ((nc != 1) & (nc != 3) & (nc != 4))), "a layout has 1, 3 or 4 components")
+    refuse(lay & ~(((nc == 1) & (model == 0)) | ((nc == 3) & ((model == 1) | (model == 2))) | ((nc == 4) & ((model == 3) | (model == 4)))),
+           "the colour model does not fit the components")
+    refuse(lay & ((hp < 0) | (hp > 0xFFFF) | (vp < 0) | (vp > 0xFFFF)), "sampling factors are a nibble per component")
+    h = torch.stack([(hp >> (4 * c)) & 15 for c in range(4)], 1)
+    v = torch.stack([(vp >> (4 * c)) & 15 for c in range(4)], 1)
+    has = torch.arange(4)[None, :] < nc[:, None]
+    refuse(lay & ((has & ((h < 1) | (h > 4) | (v < 1) | (v > 4))) | (~has & ((h != 0) | (v != 0)))).any(1), "sampling factors outside 1..4")
+    hmax, vmax = (h * has).max(1).values.clamp(min=1), (v * has).max(1).values.clamp(min=1)
+    h1, v1 = torch.where(has, h, 1).clamp(min=1), torch.where(has, v, 1).clamp(min=1)
+    refuse(lay & ((hmax[:, None] % h1 != 0) | (vmax[:, None] % v1 != 0)).any(1), "a sampling factor is no integral fraction of the largest")
+    bpm = (h * v * has).sum(1)
+    refuse(lay & ((bpm > 10) | ((nc == 1) & (bpm != 1))), "more than 10 blocks per MCU, or one component that is not 1 x 1")
+    refuse(lay & ((mcux != (W + 8 * hmax - 1) // (8 * hmax)) | (mcuy != (H + 8 * vmax - 1) // (8 * vmax))), "MCU counts do not match the extent")
+    refuse(lay & ((tset < 0) | (tset >= n_sets)), "table set outside 0..%d" % (n_sets - 1))
+    refuse(lay & ((tq < 0) | (td < 0) | (ta < 0) | (((tq | td | ta) & ~0x03030303) != 0)), "table ids must be 0..3")
+    refuse(lay & ((coef_off < 0) | (coef_off % 64 != 0) | (plane_off < 0) | (plane_off % 64 != 0)), "workspace offsets must be non-negative multiples of 64")
+    lmcu = mcux * mcuy
+    return lay, lmcu, lmcu * bpm * lay
+
+
+def jpeg_decode_layouts(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, lseg, lseg_dev, pixels,
+                        chunk_bytes=0, stages=7, check=True):
+    """jpeg_decode_progressive (chunk_bytes = 0) or jpeg_decode_split for a batch that also holds files of other component layouts
+    (include/mgnns_jpeg_layouts.h; DESIGN.md 17, "Other component layouts"): CMYK, YCCK, RGB, 4:4:0, 4:1:1 and every other
+    interleaved layout of 1, 3 or 4 components.  Such an image is a record of kind 3 (JPEG_LAYOUT_KIND) and its segments are the
+    rows of lseg [L,5] (host; lseg_dev its device copy), seg's layout; its tables lie in `tables`.  The launches for the other
+    images are the same as without this entry point; three more follow for the images of kind 3, one lane per segment -- these
+    segments are never split.  The same validation, workspaces and JpegDecodeError; -> the status tensor [S + P + L]."""
+    if chunk_bytes and (isinstance(chunk_bytes, bool) or not isinstance(chunk_bytes, int) or chunk_bytes < 8 or chunk_bytes > 65536 or chunk_bytes % 8):
+        raise ValueError("chunk_bytes must be 0 or a multiple of 8 in 8..65536, got %r" % (chunk_bytes,))
+    return jpeg_decode_progressive(data, img, img_dev, seg, seg_dev, tables, pseg, pseg_dev, level_counts, pool, qsets, pixels, stages=stages,
+                                   check=check, _split=int(chunk_bytes or 0), _layouts=(lseg, lseg_dev))
 
 
 # ---- measurement aid: in-graph timestamps --------------------------------------------------------------------------

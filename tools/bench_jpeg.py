@@ -16,7 +16,12 @@ left out too), IDCT and colour, and Pillow's time for those files; the baseline 
 the default chunk): the whole decode and the stages by the same method, the segments the split kernel took, and the pixel buffer
 compared with the switch-off leg's.
 
-    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks] [--progressive] [--split [CHUNK]]
+--layouts adds, at 500 x 375, the baseline files decoded by ImagePrep(layouts=True) (ops.jpeg_decode_layouts: the baseline route with
+the switch on, its pixel buffer compared with the switch-off leg's), the baseline files with a restart marker per MCU row, and the
+same photographs as files of other component layouts, each without restart markers and with one per MCU row of its source: CMYK
+(4:4:4), and 375 x 500 4:4:0 relabelled from the 500 x 375 4:2:2 files (47 x 32 MCUs either way).
+
+    python tools/bench_jpeg.py [DIR] [--batch 256] [--iters 100] [--restart-rows N] [--no-trunks] [--progressive] [--split [CHUNK]] [--layouts]
 """
 import glob
 import io
@@ -189,6 +194,66 @@ def case_split(prep, files, n, want):
     return res, best["whole"]
 
 
+def layout_files(w, h, B):
+    """{name: files}: the photographs as CMYK and as 4:4:0 relabelled from 4:2:2 (h x w), restart-free and with a marker per MCU row"""
+    from PIL import Image
+    out = {}
+    for rows in (0, 1):
+        cmyk, s440 = [], []
+        for k in range(8):
+            opts = dict(quality=90, restart_marker_rows=rows) if rows else dict(quality=90)
+            rgb = photograph(w, h, k)
+            buf = io.BytesIO()
+            Image.fromarray(np.concatenate([rgb, rgb[:, ::-1, :1]], 2), "CMYK").save(buf, "JPEG", subsampling=0, **opts)
+            cmyk.append(buf.getvalue())
+            buf = io.BytesIO()
+            Image.fromarray(rgb).save(buf, "JPEG", subsampling=1, **opts)
+            d = bytearray(buf.getvalue())
+            pos = 2
+            while d[pos + 1] != 0xC0:
+                pos += 2 + (d[pos + 2] << 8 | d[pos + 3])
+            assert d[pos + 11] == 0x21                   # (ceil(w / 16) x ceil(h / 8) MCUs become ceil(h / 8) x ceil(w / 16))
+            d[pos + 5:pos + 9] = bytes([w >> 8, w & 255, h >> 8, h & 255])          # height = w, width = h
+            d[pos + 11] = 0x12
+            s440.append(bytes(d))
+        tag = "_rst1" if rows else ""
+        out["cmyk" + tag] = [cmyk[i % 8] for i in range(B)]
+        out["s440" + tag] = [s440[i % 8] for i in range(B)]
+    return out
+
+
+def case_layouts(prep, files, n, want=None):
+    """the --layouts leg: the method of case(), on ops.jpeg_decode_layouts; `want`: the switch-off leg's pixel buffer, if there is one"""
+    B = len(files)
+    args, batch = prep._jpeg_run(prep._jpeg_headers(files, None), staged_only=True)
+    torch.cuda.synchronize()
+    run = lambda stages=7: ops.jpeg_decode_layouts(*args, chunk_bytes=prep.split, stages=stages, check=False)
+    assert not bool(run().any())
+    first = batch.pixels.clone()
+    assert want is None or torch.equal(first, want)
+    fns = {"whole": run, "entropy": lambda: run(1), "idct": lambda: run(2), "colour": lambda: run(4)}
+    once = timeit(run, 2, warm=0)
+    if once * n > 4e6:
+        n = max(10, int(4e6 / once))
+    ts = {k: [] for k in fns}
+    for _ in range(3):
+        for k, fn in fns.items():
+            ts[k].append(timeit(fn, n))
+    run()
+    assert torch.equal(batch.pixels, first)
+    best = {k: min(v) for k, v in ts.items()}
+    res = {"B": B, "iters_used": n, "us": round(best["whole"], 1), "images_per_s": round(B / best["whole"] * 1e6),
+           "stage_us": {k: round(best[k], 1) for k in ("entropy", "idct", "colour")}, "segments": int(args[3].shape[0]),
+           "layout_segments": int(args[11].shape[0]), "file_MB": round(sum(len(f) for f in files) / 1e6, 2),
+           "runs_us": [round(v, 1) for v in ts["whole"]]}
+    try:
+        from PIL import Image
+        assert torch.equal(batch.image(0).cpu(), torch.from_numpy(np.asarray(Image.open(io.BytesIO(files[0])).convert("RGB"))))
+    except ImportError:
+        pass
+    return res, best["whole"]
+
+
 def main():
     B, n, rr = arg("--batch", 256), arg("--iters", 100), arg("--restart-rows", 0)
     built = _lib.check_sources("tools/bench_jpeg.py")
@@ -210,6 +275,12 @@ def main():
                 want = prep.decode_jpeg(files).pixels
                 key = name + "_split"
                 res[key], times[key] = case_split(ImagePrep(448, device=DEV, split=chunk), files, n, want)
+            if "--layouts" in sys.argv and name == "500x375":
+                on = ImagePrep(448, device=DEV, layouts=True)
+                res[name + "_layouts_on"], times[name + "_layouts_on"] = case_layouts(on, files, n, prep.decode_jpeg(files).pixels)
+                res[name + "_rst1"], times[name + "_rst1"] = case(prep, encode(w, h, B, 1), n)
+                for key, fs in layout_files(w, h, B).items():
+                    res[name + "_" + key], times[name + "_" + key] = case_layouts(on, fs, n)
             if "--progressive" in sys.argv:
                 key = name + "_progressive"
                 res[key], times[key] = case_progressive(ImagePrep(448, device=DEV, progressive=True), encode(w, h, B, rr, True), n)
