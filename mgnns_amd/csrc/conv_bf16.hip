@@ -583,7 +583,8 @@ extern "C" int mgnns_conv_bf16_nhwc_fwd(const void* x, int B, int H, int W, int 
     a.cin_shift = __builtin_ctz((unsigned)Cin);
     a.OH = (H + 2 * pad - KH) / stride + 1;
     a.OW = (W + 2 * pad - KW) / stride + 1;
-    MG_REQUIRE(a.OH > 0 && a.OW > 0, "mgnns_conv_bf16_nhwc_fwd: empty output");
+    // (the quotient truncates towards zero: an image smaller than the kernel must be refused by its size, not by OH)
+    MG_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, "mgnns_conv_bf16_nhwc_fwd: empty output");
     const long long M = (long long)B * a.OH * a.OW;
     MG_REQUIRE(M < (1ll << 31) - TM, "mgnns_conv_bf16_nhwc_fwd: B*OH*OW = %lld does not fit 31 bits", M);
     const long long ybytes = M * Cout * (out_nchw_f32 ? 4 : 2);

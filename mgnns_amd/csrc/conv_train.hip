@@ -336,9 +336,11 @@ int conv_train_geometry(const char* who, int B, int H, int W, int Cin, int Cout,
                Cin, Cout);
     MG_REQUIRE((stride == 1 || stride == 2) && pad >= 0 && pad <= KH / 2, "%s: bad stride %d / padding %d (%dx%d, C_in=%d C_out=%d)", who,
                stride, pad, KH, KW, Cin, Cout);
+    // an image smaller than the kernel has no output pixel; C's division truncates towards zero, so (H + 2 pad - KH) / stride + 1
+    // alone calls H = 2, 3x3, pad 0, stride 2 one pixel
+    MG_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, "%s: empty output (H=%d W=%d k=%d stride=%d pad=%d)", who, H, W, KH, stride, pad);
     OH = (H + 2 * pad - KH) / stride + 1;
     OW = (W + 2 * pad - KW) / stride + 1;
-    MG_REQUIRE(OH > 0 && OW > 0, "%s: empty output (H=%d W=%d k=%d stride=%d pad=%d)", who, H, W, KH, stride, pad);
     MG_REQUIRE((long long)B * H * W < (1ll << 31) - 256 && (long long)B * OH * OW < (1ll << 31) - 256,
                "%s: B*H*W = %lld does not fit 31 bits", who, (long long)B * H * W);
     return 0;

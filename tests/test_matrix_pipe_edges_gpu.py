@@ -357,6 +357,7 @@ CONV_REFUSALS = [
     ("pad 1 on 1 x 1", r"bad stride 1 / padding 1", dict(k=1, pad=1)),
     ("stride 0", r"bad stride 0 / padding 0", dict(stride=0)),
     ("empty output", r"empty output", dict(k=3, pad=0, Hh=2, Ww=2)),
+    ("empty output at stride 2", r"empty output", dict(k=3, pad=0, Hh=2, Ww=2, stride=2)),     # (2 - 3) / 2 + 1 truncates to one pixel
     ("misaligned x", r"16-byte aligned", dict(off_x=2)),
     ("misaligned y", r"16-byte aligned", dict(off_y=2)),
 ]
