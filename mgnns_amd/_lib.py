@@ -20,6 +20,8 @@ EXTENSION_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_progressiv
 SPLIT_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_split.h"),)
 # ... and the JPEG files of other component layouts (LAYOUT_SIGNATURES)
 LAYOUT_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_jpeg_layouts.h"),)
+# ... and the tail of a training step: loss, gradient norm, Adam (STEP_SIGNATURES, STEP_SIZE_GETTERS, STEP_CONSTANTS)
+STEP_HEADERS = (os.path.join(_HERE, "..", "include", "mgnns_step.h"),)
 
 
 class MgnnsLibraryError(RuntimeError):
@@ -89,13 +91,14 @@ SIGNATURES = {n: a for n, (r, a) in _DECLS.items() if r is ctypes.c_int and n no
 SIZE_GETTERS = {n: a for n, (r, a) in _DECLS.items() if r is ctypes.c_size_t}
 
 
-def _read_extensions(paths, base):
-    """{name: (restype, [argtypes])} of the extension headers; a name mgnns_hip.h or another extension declares is an error."""
+def _read_extensions(paths, base, constants=None):
+    """{name: (restype, [argtypes])} of the extension headers; a name mgnns_hip.h or another extension declares is an error.
+    The headers' integer #defines are added to `constants` if one is given."""
     out = {}
     for path in paths:
         try:
             with open(path) as f:
-                decls, _ = parse_header(f.read(), path)
+                decls, defines = parse_header(f.read(), path)
         except OSError as e:
             raise MgnnsLibraryError("cannot read the C header %s (%s): the binding is derived from it" % (path, e))
         if not decls:
@@ -104,6 +107,8 @@ def _read_extensions(paths, base):
             if n in base or n in out:
                 raise MgnnsLibraryError("%s declares %s a second time" % (path, n))
         out.update(decls)
+        if constants is not None:
+            constants.update(defines)
     return out
 
 
@@ -116,6 +121,10 @@ SPLIT_SIZE_GETTERS = {n: a for n, (r, a) in _SPLIT_DECLS.items() if r is ctypes.
 _LAYOUT_DECLS = _read_extensions(LAYOUT_HEADERS, {**_DECLS, **_EXT_DECLS, **_SPLIT_DECLS})
 LAYOUT_SIGNATURES = {n: a for n, (r, a) in _LAYOUT_DECLS.items() if r is ctypes.c_int}
 LAYOUT_SIZE_GETTERS = {n: a for n, (r, a) in _LAYOUT_DECLS.items() if r is ctypes.c_size_t}
+STEP_CONSTANTS = {}          # the #defines of include/mgnns_step.h (CONSTANTS stays what mgnns_hip.h defines)
+_STEP_DECLS = _read_extensions(STEP_HEADERS, {**_DECLS, **_EXT_DECLS, **_SPLIT_DECLS, **_LAYOUT_DECLS}, STEP_CONSTANTS)
+STEP_SIGNATURES = {n: a for n, (r, a) in _STEP_DECLS.items() if r is ctypes.c_int}
+STEP_SIZE_GETTERS = {n: a for n, (r, a) in _STEP_DECLS.items() if r is ctypes.c_size_t}
 
 _lib = None
 _bound = {}          # name -> bound function: call() does no getattr on the CDLL per launch
@@ -123,7 +132,7 @@ _bound = {}          # name -> bound function: call() does no getattr on the CDL
 
 def _bind(L, name):
     fn = getattr(L, name)          # AttributeError if the symbol is missing
-    for decls in (_DECLS, _EXT_DECLS, _SPLIT_DECLS, _LAYOUT_DECLS):
+    for decls in (_DECLS, _EXT_DECLS, _SPLIT_DECLS, _LAYOUT_DECLS, _STEP_DECLS):
         if name in decls:
             fn.restype, fn.argtypes = decls[name]
             return
@@ -144,7 +153,7 @@ def lib():
         _bind(L, name)
     if L.mgnns_abi_version() != ABI_VERSION:
         raise MgnnsLibraryError("libmgnns_hip.so ABI %d != binding ABI %d; rebuild" % (L.mgnns_abi_version(), ABI_VERSION))
-    for name in list(_DECLS) + list(_EXT_DECLS) + list(_SPLIT_DECLS) + list(_LAYOUT_DECLS):
+    for name in list(_DECLS) + list(_EXT_DECLS) + list(_SPLIT_DECLS) + list(_LAYOUT_DECLS) + list(_STEP_DECLS):
         _bind(L, name)
     _lib = L
     _register_status_word(L)

@@ -20,7 +20,9 @@ FLAGS += os.environ.get("MGNNS_HIPCC_FLAGS", "").split()      # e.g. -DMG_MHA_TR
 # per-file additions.  sq_mha_bf16: the SLP vectoriser packs the epilogues' fp32 FMAs into v_pk_fma_f32, which issue no
 # faster next to a partner wave's MFMAs and cost the kernel 3 % (60.5 -> 58.6 us)
 FILE_FLAGS = {"sq_mha_bf16.hip": ["-fno-slp-vectorize"], "sq_mha32_bf16.hip": ["-fno-slp-vectorize"],
-              "sq_mha_split_bf16.hip": ["-fno-slp-vectorize"]}
+              "sq_mha_split_bf16.hip": ["-fno-slp-vectorize"],
+              # step_tail: the Adam kernel is specified one rounding per operation; the file says so itself by pragma
+              "step_tail.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -2560,3 +2560,75 @@ def textgcn_train_backward(dy, tok, node_hidden, edge_w, pmi_dev, saved, need_no
     if need_edges:
         de = keyed_row_sum(keyE, Eg.view(-1, 1), ew.shape[0]).view(-1)
     return dn, de
+
+
+# ---- the tail of a training step: loss, gradient norm, Adam (include/mgnns_step.h, csrc/step_tail.hip) --------
+_SC = _lib.STEP_CONSTANTS
+STEP_CHUNK = _SC["MGNNS_STEP_CHUNK"]                 # elements of one chunk at most
+STEP_CHUNK_WORDS = 5                                 # a chunk record as int64 words: p, g, m, v, n | group << 32
+STEP_GROUP_FLOATS = _SC["MGNNS_STEP_GROUP_FLOATS"]   # -(lr / bc1), sqrt(bc2), 1 - b1, b2, 1 - b2, eps, wd, unused
+CE_MAX_NL = _SC["MGNNS_CE_MAX_NL"]
+CE_IGNORE_INDEX = -100
+
+
+def ce_loss(logits, target):
+    """mgnns_ce_loss_fwd_bwd: (loss 0-d fp32, dlogits [B, NL] fp32) of the mean cross-entropy over the rows whose target is not
+    -100, in fp64 inside the kernel and rounded once; dlogits = (softmax - onehot) / n_live.  Any other target outside [0, NL)
+    gives a NaN loss and a NaN row (nothing outside the row is touched)."""
+    _chk(logits, "logits", ndim=2)
+    _chk(target, "target", torch.int64, 1)
+    B, NL = logits.shape
+    if target.shape[0] != B or target.device != logits.device:
+        raise ValueError("target must be [%d] on %s, got %s on %s" % (B, logits.device, tuple(target.shape), target.device))
+    if B < 1 or not 1 <= NL <= CE_MAX_NL:
+        raise ValueError("ce_loss takes B >= 1 and 1 <= NL <= %d, got logits %s" % (CE_MAX_NL, tuple(logits.shape)))
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits)
+    _launch("mgnns_ce_loss_fwd_bwd", _p(logits), _p(target), B, NL, _p(loss), _p(dlogits), _stream())
+    return loss, dlogits
+
+
+def _chk_chunks(chunks, n_chunks):
+    _chk(chunks, "chunk table", torch.int64, 2)
+    if chunks.shape[1] != STEP_CHUNK_WORDS or not 0 <= n_chunks <= chunks.shape[0]:
+        raise ValueError("chunk table must be [>= %d, %d] int64, got %s" % (n_chunks, STEP_CHUNK_WORDS, tuple(chunks.shape)))
+    return int(n_chunks)
+
+
+def grad_sumsq(chunks, n_chunks, partial):
+    """mgnns_grad_sumsq: partial[c] = the fp64 sum of g * g over chunk c of the table (mgnns_amd/optim.py builds it)."""
+    n = _chk_chunks(chunks, n_chunks)
+    _chk(partial, "partial", torch.float64, 1)
+    if partial.shape[0] < n or partial.device != chunks.device:
+        raise ValueError("partial must hold %d fp64 on %s" % (n, chunks.device))
+    _launch("mgnns_grad_sumsq", _p(chunks), n, _p(partial), _stream())
+    return partial
+
+
+def grad_clip_coef(partial, n_chunks, max_norm, out):
+    """mgnns_grad_clip_coef: out[0] = total_norm = (float)sqrt(sum of the partials), out[1] = min(1, max_norm / (total_norm + 1e-6))."""
+    _chk(partial, "partial", torch.float64, 1)
+    _chk(out, "out", ndim=1)
+    max_norm = float(max_norm)
+    if not 0 <= n_chunks <= partial.shape[0] or out.shape[0] < 2 or out.device != partial.device:
+        raise ValueError("grad_clip_coef: %d partials of %d, out %s" % (n_chunks, partial.shape[0], tuple(out.shape)))
+    if not max_norm >= 0.0:
+        raise ValueError("max_norm=%r must be a number >= 0" % max_norm)
+    _launch("mgnns_grad_clip_coef", _p(partial), int(n_chunks), max_norm, _p(out), _stream())
+    return out
+
+
+def adam_step(chunks, n_chunks, groups, clip_coef):
+    """mgnns_adam_step: one fused Adam pass over the chunk table with the per-group scalar rows `groups` [R, STEP_GROUP_FLOATS] and
+    the gradient coefficient clip_coef (a 1-element fp32 tensor on the device); a run of row -1 only has its gradient multiplied
+    by the coefficient in place.  Writes p, exp_avg and exp_avg_sq through their addresses: the caller bumps the parameters'
+    versions (optim.Adam.step does)."""
+    n = _chk_chunks(chunks, n_chunks)
+    _chk(groups, "groups", ndim=2)
+    _chk(clip_coef, "clip_coef")
+    if groups.shape[1] != STEP_GROUP_FLOATS or groups.shape[0] < 1 or clip_coef.numel() < 1:
+        raise ValueError("groups must be [R >= 1, %d] and clip_coef hold one element, got %s and %s"
+                         % (STEP_GROUP_FLOATS, tuple(groups.shape), tuple(clip_coef.shape)))
+    if groups.device != chunks.device or clip_coef.device != chunks.device:
+        raise ValueError("the chunk table, the scalar rows and clip_coef must be on one device")
+    _launch("mgnns_adam_step", _p(chunks), n, _p(groups), groups.shape[0], _p(clip_coef), _stream())

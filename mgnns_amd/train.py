@@ -155,6 +155,27 @@ def linear(x, lin_or_w, b=None):
     return y.view(*shp[:-1], y.shape[-1])
 
 
+class CrossEntropyFunction(torch.autograd.Function):
+    """loss = F.cross_entropy(logits, target) (mean over the targets that are not -100), 0-d fp32; forward and gradient in one launch
+    (ops.ce_loss, fp64 inside), backward = the saved dlogits times the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target):
+        loss, dlogits = ops.ce_loss(logits, target)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dlogits, = ctx.saved_tensors
+        return dlogits * dloss, None
+
+
+def cross_entropy(logits, target):
+    """nn.CrossEntropyLoss()(logits, target) for logits [B, NL] fp32 (NL <= ops.CE_MAX_NL) and class indices target [B] int64."""
+    return CrossEntropyFunction.apply(logits.contiguous(), target.contiguous())
+
+
 BANK_PRECISIONS = ('fp32', 'bf16x3')
 
 
