@@ -18,6 +18,8 @@ __host__ __device__ constexpr int kind_word(int align, int rows, int samp) { ret
 
 // plan = int32 [PLAN_HDR + 4 B + 2 B]: [0] number of groups, [1] B, [2] kind_word(ALIGN, ROWS, SAMP), [3] 0; group g at PLAN_HDR + 4 g: first sample, samples, rows;
 // sample b at PLAN_HDR + 4 B + 2 b: first row inside its group, live rows (last unmasked position + 1).
+// The buffer has room for B groups (every sample alone); only the plan[0] records in use are written (the fourth word of each as 0).
+// The records of groups plan[0] .. B - 1 are left as they were found and no consumer reads them: each walks g < plan[0].
 // Greedy first fit in batch order (a group closes at 16 samples or when the next sample's 8-aligned rows would pass 128),
 // computed without a serial pass over the samples: every sample finds where a group STARTING at it would end (<= 16 steps,
 // all samples at once), one thread follows that chain from sample 0 (one hop per group), every group lays out its samples.

@@ -968,7 +968,9 @@ def pack_kv_weights_bf16(wk, wv, n_head, d_kv, form=None):
 
 def sq_mha_plan(mask):
     """Packing plan of a [B, L] mask (L <= 128) for sq_mha_core_bf16(plan=...): which samples share a workgroup.  One launch;
-    build it once per batch, every attention launch on that mask takes it."""
+    build it once per batch, every attention launch on that mask takes it.  The buffer holds 4 header ints, B group records of 4
+    ints and B sample records of 2; of the group records only the first plan[0] are written (csrc/sq_mha_plan.hpp), the rest
+    is unwritten memory that no kernel reads."""
     _chk(mask, "mask", ndim=2)
     B, L_ = mask.shape
     if B > PLAN_MAX_B:
@@ -1055,7 +1057,7 @@ SPLIT_PLAN_MAX_L = 112
 
 def sq_mha_split_plan(mask):
     """Group plan of a [B, L] mask (L <= 112) for sq_mha_core_split(plan=...): which samples share a workgroup (whole 16-row tiles,
-    at most 7 tiles and 7 samples per group).  One launch; once per batch."""
+    at most 7 tiles and 7 samples per group).  One launch; once per batch.  Layout and unwritten part as sq_mha_plan's."""
     _chk(mask, "mask", ndim=2)
     B, L_ = mask.shape
     if B > PLAN_MAX_B or L_ > SPLIT_PLAN_MAX_L:
